@@ -12,6 +12,8 @@ Workloads:
     train : forward + the reference's loss graph + backward + (N>1: one RCCL all-reduce of the flat gradient bucket) + Adam
     fwd   : forward only (BASELINE.json configs[1] plus voting + proposal)
 Inputs are resident in HBM before the timed region.  One JSON line on rank 0.
+--dump-outputs DIR: what the last timed step returned (train: also the loss terms and the gradient) as DIR/<name>.npy; for train,
+that step starts from the seeded parameters (see init_flat in main), so two runs with the same arguments agree up to rounding.
 """
 import gc
 import argparse
@@ -50,6 +52,8 @@ def parse():
                          "Works at --gpus 1 too (a one-rank RCCL communicator still runs both collectives)")
     ap.add_argument("--no-pipeline", action="store_true",
                     help="do not compute the coordinate-only geometry of the next batch underneath the current step")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32; see dump_outputs)")
     return ap.parse_args()
 
 
@@ -315,6 +319,29 @@ def emit(line):
     os.write(_REAL_STDOUT if _REAL_STDOUT is not None else 1, (line + "\n").encode())
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: every array as out_dir/<name>.npy in float32 (float64 stays float64).  Inputs are seeded, so two builds run
+    with the same arguments can be compared file by file.  Should the arrays hold more than `limit` bytes, each one is cut to its share
+    of the limit by a fixed, seeded sample of its flattened elements (same indices on every run), saved flat.  -> {name: shape saved}."""
+    import numpy as np
+    arrays = {k: (v if v.dtype == np.float64 else v.astype(np.float32)) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    os.makedirs(out_dir, exist_ok=True)
+    saved = {}
+    for name, v in sorted(arrays.items()):
+        if total > limit:
+            keep = max(1, int(v.size * limit // total))
+            if keep < v.size:
+                sel = np.sort(np.random.default_rng(0).choice(v.size, keep, replace=False))
+                v = v.reshape(-1)[sel]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(v))
+        saved[name] = list(v.shape)
+    return saved
+
+
 def load_hostpin():
     """votenet_amd/hostpin.py as a stand-alone module (no package __init__, hence no torch, no library): the pin has to precede the
     first thread torch or the HIP runtime creates."""
@@ -398,6 +425,19 @@ def main():
     pipeline = not args.no_pipeline
     counter = [0]
     pipe_on = [pipeline]
+    keep_result = [False]  # --dump-outputs: step() holds on to what the last timed step returned
+    last_result = [None]
+    # --dump-outputs, train: the parameters as seeded (and broadcast), restored with a fresh optimizer state right before the last timed
+    # step.  The default backward pass sums with fp32 atomics, and Adam's normalised update turns that rounding into whole learning-rate
+    # steps for near-zero gradients: after a few steps two runs hold visibly different models.  From the seeded state the step's outputs
+    # and gradient are the same in every run up to rounding.
+    init_flat = net.store.flat.clone() if args.dump_outputs and workload == "train" else None
+
+    def restore_initial_state():
+        net.store.flat.copy_(init_flat)
+        net._m.zero_()
+        net._v.zero_()
+        net._step = 0
 
     def step():
         i = counter[0]
@@ -406,9 +446,11 @@ def main():
         x = xs[i % nb]
         nxt = ([xs[(i + 1) % nb]] + ([xs[(i + 2) % nb]] if workload == "fwd" else [])) if pipe_on[0] else None
         if workload == "train":
-            net.train_step(x, cot, world, gt=gts[i % nb], next_x=nxt)
+            res = net.train_step(x, cot, world, gt=gts[i % nb], next_x=nxt)
         else:
-            net.forward(x, next_x=nxt)
+            res = net.forward(x, next_x=nxt)
+        if keep_result[0]:
+            last_result[0] = res
 
     if args.no_gram:
         from votenet_amd import pointnet2
@@ -464,6 +506,10 @@ def main():
         if i == prof_first + prof_steps:
             events, tf_sampling.PROFILE_EVENTS = tf_sampling.PROFILE_EVENTS, None
             bq_events, tf_grouping.PROFILE_EVENTS = tf_grouping.PROFILE_EVENTS, None
+        if args.dump_outputs and i == args.steps - 1:
+            keep_result[0] = True
+            if init_flat is not None:
+                restore_initial_state()
         if os.environ.get("VOTENET_BENCH_PROFILE_STEP") == str(i):
             import cProfile, pstats, io
             pr = cProfile.Profile(); pr.enable(); step(); pr.disable()
@@ -477,6 +523,19 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    dumped = None
+    if args.dump_outputs:  # before any further step overwrites the buffers the last timed step returned
+        keep_result[0] = False
+        arrays = {k: v.detach().cpu().numpy() for k, v in last_result[0].items() if torch.is_tensor(v)}
+        last_result[0] = None
+        if workload == "train":  # what else the step leaves its caller: the loss terms and the gradient of the flat parameter bucket
+            if gts[0] is not None:
+                arrays["losses"] = net.last_losses.detach().cpu().numpy()
+            arrays["grad"] = net.store.grad.detach().cpu().numpy()
+        if rank == 0:
+            dumped = {"dir": os.path.abspath(args.dump_outputs), "arrays": dump_outputs(args.dump_outputs, arrays),
+                      "state": "train: the last timed step starts from the seeded parameters with a fresh optimizer state" if init_flat is not None
+                      else "forward: parameters as seeded"}
     gc.enable()
     if tf_sampling.PROFILE_EVENTS is not None:  # steps <= 2
         events, tf_sampling.PROFILE_EVENTS = tf_sampling.PROFILE_EVENTS, None
@@ -926,7 +985,7 @@ def main():
             "ms_per_step_spread": spread, "without_cross_step_pipelining": in_step, "deterministic_mode": det_step,
             "fp32_mfma_gemms": fp32_step, "bf16x3_forward_operands": bf3_step, "full_row_layout": full_step, "row_layout": row_layout, "configs": cfgs,
             "communicator": comm, "per_rank": per_rank, "dp_collectives": dp_coll, "check_dp": check,
-            "gpu_busy_seconds": gpu_busy,
+            "gpu_busy_seconds": gpu_busy, "dump_outputs": dumped,
             "roofline": roof, "roofline_ball_query": bq, "roofline_mlp": mfma, "cpu_baseline": cpu,
         }
         emit(json.dumps(out))

@@ -145,3 +145,41 @@ def prob_sample_cases():
     for n in (1, 2, 3, 4, 5, 7, 8, 1000, 8191, 8192, 8193, 8195, 20000):
         out["n%d" % n] = (rs.rand(2, n).astype(np.float32) + 1e-3, rs.rand(2, 257).astype(np.float32))
     return out
+
+
+# ---- the cases test_oracle_golden.py / test_oracle_variants.py run against the reference's compiled CPU code (oracle/_ref);
+# its outputs on them are stored in ref_build.npz (make_golden.py), so that the comparison does not need the reference tree
+REF_BUILD_BALL = [(1, 2, 700, 90, 0.2, 16), (2, 1, 2048, 512, 0.2, 32), (3, 3, 513, 64, 0.4, 64), (4, 1, 100, 7, 0.05, 8),
+                  (5, 2, 64, 64, 2.0, 5)]                       # (seed, b, n, m, radius, nsample)
+REF_BUILD_NN = [(1, 2, 300, 40, 8), (2, 1, 1024, 512, 3), (3, 1, 50, 2, 4), (4, 1, 50, 1, 4)]  # (seed, b, n, m, c)
+
+
+def ref_build_ball(seed, b, n, m, k):
+    """Ball query / group_point / its gradient: (xyz1, xyz2, points, grad_out)."""
+    rng = np.random.default_rng(seed)
+    xyz1 = rng.random((b, n, 3), dtype=np.float32)
+    xyz2 = rng.random((b, m, 3), dtype=np.float32)
+    pts = rng.random((b, n, 5), dtype=np.float32)
+    go = rng.random((b, m, k, 5), dtype=np.float32)
+    return xyz1, xyz2, pts, go
+
+
+def ref_build_nn(seed, b, n, m, c):
+    """three_nn / three_interpolate / its gradient: (xyz1, xyz2, points, grad_out)."""
+    rng = np.random.default_rng(seed)
+    xyz1 = rng.random((b, n, 3), dtype=np.float32)
+    xyz2 = rng.random((b, m, 3), dtype=np.float32)
+    if seed == 2:
+        xyz2[:, 5] = xyz2[:, 9]  # duplicated known points: equal distances, lower index first
+    pts = rng.random((b, m, c), dtype=np.float32)
+    go = rng.random((b, n, c), dtype=np.float32)
+    return xyz1, xyz2, pts, go
+
+
+def ref_build_selection_sort():
+    """SelectionSort rows with plenty of ties: [(dist, k)]."""
+    rs = np.random.RandomState(0)
+    out = []
+    for b, m, n, k in ((2, 5, 40, 7), (1, 3, 9, 9), (3, 2, 100, 1), (1, 1, 1, 1)):
+        out.append((np.round(rs.random_sample((b, m, n)) * 8).astype(np.float32) / 8, k))
+    return out

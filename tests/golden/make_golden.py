@@ -118,11 +118,38 @@ def main():
         out[name] = O.prob_sample(p, r)
         out[name + "_cumsum_sha"] = sha(O.cumsum(p))
     np.savez_compressed(os.path.join(HERE, "prob_sample.npz"), source="oracle", **out)
+    ref_build()
     print("golden fixtures written to", HERE)
     for f in sorted(os.listdir(HERE)):
         if f.endswith(".npz"):
             print("  %-28s %7d bytes" % (f, os.path.getsize(os.path.join(HERE, f))))
 
 
+def ref_build():
+    """ref_build.npz: the reference's compiled CPU code (oracle/_ref) on the cases the oracle tests also run against it live
+    (cases.REF_BUILD_*), as sha256 digests -- every compared result is bit-exact."""
+    O.build()
+    assert all(O.ref(n) is not None for n in ("grouping", "interpolate", "selection_sort")), "oracle/_ref missing (no reference tree?)"
+    out = {}
+    for seed, b, n, m, r, k in cases.REF_BUILD_BALL:
+        xyz1, xyz2, pts, go = cases.ref_build_ball(seed, b, n, m, k)
+        idx = O.ref_query_ball_point(r, k, xyz1, xyz2)
+        out["ball%d_idx" % seed] = sha(idx)
+        out["ball%d_group" % seed] = sha(O.ref_group_point(pts, idx))
+        out["ball%d_group_grad" % seed] = sha(O.ref_group_point_grad(pts, idx, go))
+    for seed, b, n, m, c in cases.REF_BUILD_NN:
+        xyz1, xyz2, pts, go = cases.ref_build_nn(seed, b, n, m, c)
+        dist, idx = O.ref_three_nn(xyz1, xyz2)
+        w = O.three_nn_weights(np.where(np.isfinite(dist), dist, 1.0).astype(np.float32))
+        out["nn%d_dist" % seed], out["nn%d_idx" % seed] = sha(dist), sha(idx)
+        out["nn%d_interp" % seed] = sha(O.ref_three_interpolate(pts, idx, w))
+        out["nn%d_interp_grad" % seed] = sha(O.ref_three_interpolate_grad(pts, idx, w, go))
+    for i, (d, k) in enumerate(cases.ref_build_selection_sort()):
+        outi, val = O.ref_select_top_k(k, d)
+        out["sort%d_idx" % i], out["sort%d_val" % i] = sha(outi), sha(val)
+    np.savez_compressed(os.path.join(HERE, "ref_build.npz"), source="ref", **out)
+
+
 if __name__ == "__main__":
-    main()
+    # `make_golden.py ref_build` writes ref_build.npz alone
+    ref_build() if sys.argv[1:] == ["ref_build"] else main()

@@ -132,3 +132,36 @@ def test_the_launcher_parent_never_imports_torch():
     e = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run([sys.executable, "-c", code], env=e, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr
+
+
+def test_dump_outputs_writes_float32_and_samples_under_the_limit(tmp_path):
+    """--dump-outputs: one float32 .npy per array (float64 kept); above the byte limit a seeded sample of each array, the same on
+    every run."""
+    import numpy as np
+    rng = np.random.default_rng(3)
+    arrays = {"a": rng.random((4, 300)).astype(np.float32), "b": np.arange(50, dtype=np.int32), "c": rng.random(7)}
+    saved = bench.dump_outputs(str(tmp_path / "full"), arrays)
+    assert saved == {"a": [4, 300], "b": [50], "c": [7]}
+    a, b, c = (np.load(str(tmp_path / "full" / (n + ".npy"))) for n in "abc")
+    assert a.dtype == np.float32 and np.array_equal(a, arrays["a"])
+    assert b.dtype == np.float32 and np.array_equal(b, np.arange(50))
+    assert c.dtype == np.float64 and np.array_equal(c, arrays["c"])
+    limit = 2000
+    s1 = bench.dump_outputs(str(tmp_path / "s1"), arrays, limit=limit)
+    s2 = bench.dump_outputs(str(tmp_path / "s2"), arrays, limit=limit)
+    assert s1 == s2 and s1["a"][0] < 1200
+    total = 0
+    for n in "abc":
+        x1, x2 = np.load(str(tmp_path / "s1" / (n + ".npy"))), np.load(str(tmp_path / "s2" / (n + ".npy")))
+        assert np.array_equal(x1, x2)
+        assert np.isin(x1, arrays[n].reshape(-1)).all()
+        total += x1.nbytes
+    assert total <= limit
+
+
+def test_dump_outputs_option_is_parsed(monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "3", "--dump-outputs", "out"])
+    a = bench.parse()
+    assert a.steps == 3 and a.dump_outputs == "out"
+    monkeypatch.setattr(sys, "argv", ["bench.py"])
+    assert bench.parse().dump_outputs is None

@@ -35,14 +35,15 @@ def test_selection_sort_golden_from_the_reference_twin(O, golden):
     assert tw[0][0, 0].tolist() == [3, 2, 1, 0] and tw[1][0, 0].tolist() == [7.0, 8.0, 9.0, 10.0]
 
 
-def test_selection_sort_against_live_reference_twin(O):
-    if O.ref("selection_sort") is None:
-        pytest.skip("oracle/_ref not built (no reference tree on this machine)")
-    rs = np.random.RandomState(0)
-    for b, m, n, k in ((2, 5, 40, 7), (1, 3, 9, 9), (3, 2, 100, 1), (1, 1, 1, 1)):
-        d = np.round(rs.random_sample((b, m, n)) * 8).astype(F) / 8  # plenty of ties
-        a, r = O.select_top_k(k, d), O.ref_select_top_k(k, d)
-        assert np.array_equal(a[0], r[0]) and np.array_equal(a[1], r[1])
+def test_selection_sort_against_live_reference_twin(O, golden):
+    """The twin's outputs stored in ref_build.npz (make_golden.py ref_build); the twin itself as well when oracle/_ref exists."""
+    g = golden("ref_build")
+    for i, (d, k) in enumerate(cases.ref_build_selection_sort()):  # plenty of ties
+        a = O.select_top_k(k, d)
+        assert sha(a[0]) == str(g["sort%d_idx" % i]) and sha(a[1]) == str(g["sort%d_val" % i]), i
+        if O.ref("selection_sort") is not None:
+            r = O.ref_select_top_k(k, d)
+            assert np.array_equal(a[0], r[0]) and np.array_equal(a[1], r[1])
 
 
 def test_knn_point_is_the_k_nearest():
