@@ -261,6 +261,35 @@ int votenet_group_linear_backward(int b, int n, int m, int nsample, int cout, co
 int votenet_bn_relu_max(long groups, int k, int c, const float *z, const float *scale, const float *shift,
                         int relu, float *out, int *argmax, void *stream);
 
+/* ---- the other pooling modes of pointnet_sa_module and group_all (pool_modes.hip; utils.py:64-90, 131-146) ----
+ * mode: the reference's `pooling` argument.  Outputs per group: MAX (groups x c) + argmax; AVG = reduce_mean (groups x c);
+ * WEIGHTED_AVG = sum_k w * y (groups x c); MAX_AND_AVG = concat([avg, max], -1) (groups x 2c) + argmax (of the max half). */
+#define VOTENET_POOL_MAX 0
+#define VOTENET_POOL_AVG 1
+#define VOTENET_POOL_WEIGHTED_AVG 2
+#define VOTENET_POOL_MAX_AND_AVG 3
+/* y = act(z*scale+shift) (z: groups*k x c, contiguous), reduced over each group's k rows (utils.py:131-146).  Any k >= 1, c >= 1.
+ * When groups x ceil(c / 64) would not fill the GPU (group_all: groups = b, k = n) a group's rows are split over workgroups and
+ * the partials combined in a fixed order by a second launch: work (votenet_bn_relu_pool_workspace_floats; 0 = not needed, may
+ * then be NULL).  The mean sums in that order, then divides by k.  w (groups*k) for WEIGHTED_AVG (votenet_sa_pool_weights), else
+ * may be NULL.  argmax (groups x c, int32 row offset in the group; the first maximum in row order) may be NULL. */
+size_t votenet_bn_relu_pool_workspace_floats(long groups, int k, int c);
+int votenet_bn_relu_pool(long groups, int k, int c, const float *z, const float *scale, const float *shift, int relu, int mode,
+                         const float *w, float *out, int *argmax, float *work, void *stream);
+/* weighted_avg's weights (utils.py:135-140): w[g, j] = softmax_j(-5 |v|) over each group, v = xyz[b, idx[b,i,j]] - new_xyz[b,i]
+ * (g = b*m + i), or v = xyz[b, j] for group_all (idx = new_xyz = NULL, m = 1, k = n).  fp32, the maximum subtracted before exp. */
+int votenet_sa_pool_weights(int b, int n, int m, int k, const float *xyz, const float *new_xyz, const int *idx, float *w,
+                            void *stream);
+/* The gradient reaching the pooled layer's activation y (rows = groups*k x c) from gout (groups x c, or x 2c for MAX_AND_AVG):
+ * gout / k (AVG), w * gout (WEIGHTED_AVG), gout at the arg-max row (MAX), the sum of both (MAX_AND_AVG).  Written in full. */
+int votenet_sa_pool_grad(long groups, int k, int c, int mode, const float *gout, const float *w, const int *argmax, float *da,
+                         void *stream);
+/* The coordinate gradient through weighted_avg's weights (utils.py:135-140): gw[row] = sum_c gout[g,c] y[row,c] (scratch, rows),
+ * then the softmax backward, d|v| = -5 ds, dv (rows x 3) = d|v| v / |v| -- 0 where |v| = 0 (tf.norm's gradient there is 0 * inf). */
+int votenet_sa_pool_weights_grad(int b, int n, int m, int k, int c, const float *xyz, const float *new_xyz, const int *idx,
+                                 const float *z, const float *scale, const float *shift, int relu, const float *gout,
+                                 const float *w, float *gw, float *dv, void *stream);
+
 /* votenet_mlp_linear with the max-pool of utils.py:132 started in its epilogue: besides z and stats it writes, per group
  * of pool_k consecutive rows and channel, the RAW maximum and minimum of z and the row offsets where they are attained
  * (zmax / zmin / amax / amin, each rows/pool_k x cout).  The layer's BatchNorm scale needs the statistics of the whole

@@ -120,6 +120,10 @@ _SIGS.update({
     "votenet_register_split_weights": [_c_f, ctypes.c_int, ctypes.c_int, ctypes.c_void_p],
     "votenet_bn_finalize": [ctypes.c_long, ctypes.c_int] + [_c_f] * 3 + [ctypes.c_float] + [_c_f] * 4 + [ctypes.c_void_p],
     "votenet_bn_relu_max": [ctypes.c_long, ctypes.c_int, ctypes.c_int] + [_c_f] * 3 + [ctypes.c_int] + [_c_f] * 2 + [ctypes.c_void_p],
+    "votenet_bn_relu_pool": [ctypes.c_long, ctypes.c_int, ctypes.c_int] + [_c_f] * 3 + [ctypes.c_int] * 2 + [_c_f] * 4 + [ctypes.c_void_p],
+    "votenet_sa_pool_weights": [ctypes.c_int] * 4 + [_c_f] * 4 + [ctypes.c_void_p],
+    "votenet_sa_pool_grad": [ctypes.c_long] + [ctypes.c_int] * 3 + [_c_f] * 4 + [ctypes.c_void_p],
+    "votenet_sa_pool_weights_grad": [ctypes.c_int] * 5 + [_c_f] * 6 + [ctypes.c_int] + [_c_f] * 4 + [ctypes.c_void_p],
     "votenet_bn_relu": [ctypes.c_long, ctypes.c_int] + [_c_f] * 3 + [ctypes.POINTER(BnRaw), ctypes.c_int, _c_f, ctypes.c_void_p],
     "votenet_bn_backward_reduce": [ctypes.c_long, ctypes.c_int, ctypes.c_int] + [_c_f] * 7 + [ctypes.c_float, ctypes.c_int, _c_f,
                                                                                              ctypes.POINTER(CoefTail), ctypes.c_void_p],
@@ -258,6 +262,8 @@ def lib():
         L.votenet_nms3d_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int]
         L.votenet_mlp_split_k_floats.restype = ctypes.c_long
         L.votenet_mlp_split_k_floats.argtypes = [ctypes.c_long, ctypes.c_int, ctypes.c_int]
+        L.votenet_bn_relu_pool_workspace_floats.restype = ctypes.c_size_t
+        L.votenet_bn_relu_pool_workspace_floats.argtypes = [ctypes.c_long, ctypes.c_int, ctypes.c_int]
         L.votenet_ball_threshold.restype = ctypes.c_float
         L.votenet_ball_threshold.argtypes = [ctypes.c_float]
         for name, sig in _SIGS.items():

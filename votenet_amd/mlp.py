@@ -1313,6 +1313,62 @@ def bn_relu_max(z, k, scale, shift, relu=True, want_argmax=False):
     return out, arg
 
 
+POOL_MODES = {"max": 0, "avg": 1, "weighted_avg": 2, "max_and_avg": 3}  # VOTENET_POOL_* (include/votenet_hip.h), utils.py:131-146
+
+
+def bn_relu_pool(z, k, scale, shift, relu=True, mode="max", w=None, want_argmax=False):
+    """(groups*k, c) raw z -> (groups, c) pool over each group's k rows of act(z*scale+shift) (votenet_bn_relu_pool, any k and c;
+    a group of many rows is split over workgroups).  mode: a key of POOL_MODES; 'max_and_avg' gives (groups, 2c) = [mean | max].
+    w (groups*k,): the weights of 'weighted_avg' (sa_pool_weights).  -> out, argmax (groups, c) int32 or None."""
+    rows, c = z.shape
+    groups = rows // k
+    m = POOL_MODES[mode]
+    out = torch.empty((groups, 2 * c if mode == "max_and_avg" else c), dtype=torch.float32, device=z.device)
+    arg = torch.empty((groups, c), dtype=torch.int32, device=z.device) if want_argmax and mode in ("max", "max_and_avg") else None
+    nwork = L.lib().votenet_bn_relu_pool_workspace_floats(groups, k, c)
+    work = torch.empty(nwork, dtype=torch.float32, device=z.device) if nwork else None
+    with L.device_guard(z.device):
+        L.check(L.lib().votenet_bn_relu_pool(groups, k, c, L.ptr(z), L.ptr(scale), L.ptr(shift), 1 if relu else 0, m, L.ptr(w),
+                                             L.ptr(out), L.ptr(arg), L.ptr(work), L.stream_ptr()))
+    return out, arg
+
+
+def sa_pool_weights(xyz, new_xyz=None, idx=None):
+    """weighted_avg's weights softmax(-5 |v|) per group (utils.py:135-140): v = xyz[idx] - new_xyz, or xyz itself (group_all: new_xyz
+    and idx None, one group of all n points per scene).  -> (b*m*k,) f32."""
+    b, n = xyz.shape[:2]
+    m, k = (idx.shape[1], idx.shape[2]) if idx is not None else (1, n)
+    w = torch.empty(b * m * k, dtype=torch.float32, device=xyz.device)
+    with L.device_guard(xyz.device):
+        L.check(L.lib().votenet_sa_pool_weights(b, n, m, k, L.ptr(xyz), L.ptr(new_xyz), L.ptr(idx), L.ptr(w), L.stream_ptr()))
+    return w
+
+
+def sa_pool_grad(gout, k, c, mode, w=None, argmax=None):
+    """gout (groups, c | 2c) of bn_relu_pool -> the gradient reaching its activation, (groups*k, c) (votenet_sa_pool_grad)."""
+    groups = gout.shape[0]
+    da = torch.empty((groups * k, c), dtype=torch.float32, device=gout.device)
+    with L.device_guard(gout.device):
+        L.check(L.lib().votenet_sa_pool_grad(groups, k, c, POOL_MODES[mode], L.ptr(gout), L.ptr(w), L.ptr(argmax), L.ptr(da),
+                                             L.stream_ptr()))
+    return da
+
+
+def sa_pool_weights_grad(xyz, new_xyz, idx, z, scale, shift, relu, gout, w):
+    """The gradient through weighted_avg's weights with respect to v = xyz[idx] - new_xyz (or xyz, group_all: new_xyz / idx None):
+    -> dv (b*m*k, 3); rows with |v| = 0 get 0 (votenet_sa_pool_weights_grad)."""
+    b, n = xyz.shape[:2]
+    m, k = (idx.shape[1], idx.shape[2]) if idx is not None else (1, n)
+    c = z.shape[1]
+    gw = torch.empty(b * m * k, dtype=torch.float32, device=z.device)
+    dv = torch.empty((b * m * k, 3), dtype=torch.float32, device=z.device)
+    with L.device_guard(z.device):
+        L.check(L.lib().votenet_sa_pool_weights_grad(b, n, m, k, c, L.ptr(xyz), L.ptr(new_xyz), L.ptr(idx), L.ptr(z), L.ptr(scale),
+                                                     L.ptr(shift), 1 if relu else 0, L.ptr(gout), L.ptr(w), L.ptr(gw), L.ptr(dv),
+                                                     L.stream_ptr()))
+    return dv
+
+
 def bn_relu(z, scale, shift, relu=True, bn=None):
     """bn: a PendingBN instead of scale / shift (the kernel finalizes it)."""
     rows, c = z.shape

@@ -1,8 +1,9 @@
 """PointNet++ SA / FP layers of VoteNet on the HIP hot path -- mirror of the reference's utils.py.
 
     sample_and_group     utils.py:25-61
-    pointnet_sa_module   utils.py:93-158   (group_all=False, pooling='max'; knn=False is the only
-                                            configuration model.py uses, knn=True is served too)
+    pointnet_sa_module   utils.py:93-158   (group_all=False, pooling='max', knn=False is the
+                                            configuration model.py uses; knn=True, group_all=True and
+                                            pooling='avg' / 'weighted_avg' / 'max_and_avg' are served too)
     pointnet_sa_module_msg utils.py:161-201 (multi-scale grouping; never reached by model.py)
     pointnet_fp_module   utils.py:266-294
 
@@ -809,29 +810,50 @@ def sample_and_group(npoint, radius, nsample, xyz, sample_xyz=None, knn=False):
     return fps_idx, new_xyz, idx, pts_cnt
 
 
-class SAModule:
-    """pointnet_sa_module (utils.py:93-158) with group_all=False, pooling='max', use_xyz=True."""
+POOLINGS = ("max", "avg", "weighted_avg", "max_and_avg")  # utils.py:131-146
 
-    def __init__(self, store, scope, npoint, radius, nsample, cin, mlp, mlp2=None, knn=False, prefix="conv", leaf=False):
+
+class SAModule:
+    """pointnet_sa_module (utils.py:93-158) with use_xyz=True, bn=True.
+
+    The default configuration (group_all=False, pooling='max') runs the fused forms below (narrow / assembled first layer, piece
+    layout, max-pool in the GEMM epilogue, Gram-form backward).  group_all=True or another pooling mode runs the plain chain (every
+    z stored) and the pool as its own launch (votenet_bn_relu_pool, csrc/pool_modes.hip): the fused forms are max-specific -- the
+    piece layout drops the rows that repeat a ball's first hit, which a mean or a softmax counts."""
+
+    def __init__(self, store, scope, npoint, radius, nsample, cin, mlp, mlp2=None, knn=False, prefix="conv", leaf=False, pooling="max",
+                 group_all=False):
         """leaf: the input points carry no gradient (the first module of a network): backward() then returns (None, None), which
-        lets a narrow first layer (3 + cin <= 8) run without ever storing its output (NARROW_FIRST, csrc/narrow.hip)."""
+        lets a narrow first layer (3 + cin <= 8) run without ever storing its output (NARROW_FIRST, csrc/narrow.hip).
+        pooling: 'max' | 'avg' | 'weighted_avg' | 'max_and_avg' (utils.py:131-146; the last pools to 2 mlp[-1] channels, [avg | max]).
+        group_all: one group of all n points per scene, centre 0, uncentred coordinates (utils.py:64-90); npoint, radius, nsample
+        and knn are ignored."""
+        if pooling not in POOLINGS:
+            raise ValueError("SAModule: pooling must be one of %s, got %r" % (", ".join(POOLINGS), pooling))
+        self.pooling, self.group_all = pooling, bool(group_all)
+        self.plain_pool = self.group_all or pooling != "max"  # the pool as its own launch behind the plain chain
+        if self.group_all:
+            npoint, radius, nsample, knn = 1, None, None, False
         self.npoint, self.radius, self.nsample, self.knn = npoint, radius, nsample, knn
         self.leaf, self.cin = leaf, cin
         self.mlp = make_mlp(store, scope, 3 + cin, mlp, prefix)
         store.want_transpose(self.mlp[0].name + "/W", 3, None)  # W[3:]^T: the per-point feature gradient
         store._split_rows.append((self.mlp[0].name + "/W", 3, None))  # W[3:]: the per-point GEMM of the forward pass gets its image too
         store.want_transpose(self.mlp[0].name + "/W", 0, 3)     # W[:3]^T: the xyz gradient (proposal layer)
-        self.mlp2 = make_mlp(store, scope, mlp[-1], mlp2, "conv_post_", last_plain=True) if mlp2 else None
+        pooled = 2 * mlp[-1] if pooling == "max_and_avg" else mlp[-1]
+        self.mlp2 = make_mlp(store, scope, pooled, mlp2, "conv_post_", last_plain=True) if mlp2 else None
 
     def narrow(self, rows):
         """True when this module runs its first layer in the narrow form for `rows` grouped rows."""
         m = self.mlp
-        return bool(NARROW_FIRST and self.leaf and len(m) >= 3 and m[0].bn and m[1].bn and m[0].relu and
+        return bool(NARROW_FIRST and not self.plain_pool and self.leaf and len(m) >= 3 and m[0].bn and m[1].bn and m[0].relu and
                     M.narrow_supported(rows, 3 + self.cin, m[0].cout, m[1].cout))
 
     def assembled(self, b, n):
         """True when this module's first layer is assembled inside its consumers (csrc/assemble.hip) for b scenes of n points."""
         m = self.mlp
+        if self.plain_pool:
+            return False
         rows = b * self.npoint * self.nsample
         return bool(ASSEMBLE_FIRST and PRE_LINEAR and not M.DETERMINISTIC and self.cin > 0 and not self.narrow(rows) and len(m) >= 3
                     and m[0].bn and m[1].bn and m[0].relu and M.assembled_supported(rows, m[0].cout, m[1].cout)
@@ -841,7 +863,7 @@ class SAModule:
         """True when this module's grouped MLP runs on the piece layout (csrc/half.hip: the rows that repeat slot 0 dropped by
         halves of a ball) for b scenes of n points: an assembled first layer, three BatchNorm'ed layers, the pooled one in Gram form."""
         m = self.mlp
-        if not (HALF_GROUPS and not M.DETERMINISTIC and not self.knn and self.nsample == 64 and len(m) == 3 and m[2].bn and POOL_IN_EPILOGUE
+        if not (HALF_GROUPS and not self.plain_pool and not M.DETERMINISTIC and not self.knn and self.nsample == 64 and len(m) == 3 and m[2].bn and POOL_IN_EPILOGUE
                 and POOL_GRAM_BACKWARD and (b * self.npoint) % 8 == 0 and M.pool_backward_supported(m[1].cout, m[2].cout, 64)):
             return False
         return bool(self.narrow(b * self.npoint * 64) or (m[1].cout == 128 and self.assembled(b, n)))
@@ -876,6 +898,8 @@ class SAModule:
     def forward(self, xyz, points, sample_xyz=None, tape=None, geom=None):
         """xyz (B,n,3), points (B,n,C) or None -> new_xyz (B,m,3), new_points (B,m,C'), idx (B,m,K).
         geom: the tuple returned by geometry() when it was computed ahead of time."""
+        if self.plain_pool:
+            return self._forward_plain_pool(xyz, points, sample_xyz, tape, geom)
         b = xyz.shape[0]
         geom = geom if geom is not None else self.geometry(xyz, sample_xyz, points=points)
         fps_idx, new_xyz, idx, pts_cnt = geom[:4]
@@ -916,6 +940,8 @@ class SAModule:
 
     def backward(self, rec, g_out, need_feat_grad=True, need_xyz_grad=False):
         """g_out (B,m,C') -> d_points (B,n,C) or None, d_xyz (B,n,3) or None."""
+        if self.plain_pool:
+            return self._backward_plain_pool(rec, g_out, need_feat_grad, need_xyz_grad)
         b = rec["b"]
         g = g_out.reshape(b * self.npoint, -1).contiguous()
         if self.mlp2:
@@ -929,7 +955,81 @@ class SAModule:
             return None, None
         return self._first_layer_backward(rec, h, need_feat, need_xyz_grad)
 
-    def _first_layer_backward(self, rec, h, need_feat, need_xyz_grad):
+    def _forward_plain_pool(self, xyz, points, sample_xyz, tape, geom):
+        """forward() of a group_all module or of a pooling mode other than max: the plain chain with every z stored, then
+        votenet_bn_relu_pool over the last layer's raw z (its BatchNorm finalized first)."""
+        b, n = xyz.shape[:2]
+        if self.group_all:
+            # sample_and_group_all (utils.py:64-90): centre 0, idx = arange(n), the grouped rows [xyz | points] of every point
+            # uncentred -- a dense (b n, 3 + c) input built in one launch, no gather
+            fps_idx = pts_cnt = None
+            new_xyz = torch.zeros((b, 1, 3), dtype=torch.float32, device=xyz.device)
+            idx = torch.arange(n, dtype=torch.int32, device=xyz.device).view(1, 1, n).expand(b, 1, n).contiguous()
+            m, k = 1, n
+            x = xyz.reshape(b * n, 3)
+            if points is not None:
+                c = points.shape[2]
+                x = torch.empty((b * n, 3 + c), dtype=torch.float32, device=xyz.device)
+                M.row_segments(b * n, [(x[:, :3], xyz.reshape(b * n, 3), None), (x[:, 3:], points.reshape(b * n, c), None)])
+            first = ("dense", x)
+        else:
+            geom = geom if geom is not None else self.geometry(xyz, sample_xyz)
+            fps_idx, new_xyz, idx, pts_cnt = geom[:4]
+            m, k = self.npoint, self.nsample
+            first = ("gather", xyz, new_xyz, points, idx)
+        rows = b * m * k
+        recs = []
+        z, pend = mlp_chain_forward(self.mlp, rows, first, recs)
+        sc, sh = pend.finalize()
+        w = None
+        if self.pooling == "weighted_avg":
+            w = M.sa_pool_weights(xyz, None, None) if self.group_all else M.sa_pool_weights(xyz, new_xyz, idx)
+        pooled, argmax = M.bn_relu_pool(z, k, sc, sh, self.mlp[-1].relu, self.pooling, w=w, want_argmax=tape is not None)
+        recs2 = []
+        out = pooled
+        if self.mlp2:
+            out, _ = mlp_chain_forward(self.mlp2, b * m, ("dense", pooled), recs2)
+        if tape is not None:
+            tape.append(dict(op="sa", module=self, recs=recs, recs2=recs2, argmax=argmax, zsel=None, fps_idx=fps_idx, idx=idx,
+                             pts_cnt=pts_cnt, xyz=xyz, points=points, new_xyz=new_xyz, b=b, m=m, k=k, weights=w))
+        return new_xyz, out.reshape(b, m, -1), idx
+
+    def _backward_plain_pool(self, rec, g_out, need_feat_grad, need_xyz_grad):
+        """backward() of _forward_plain_pool: the gradient reaching the last activation is written out (votenet_sa_pool_grad) and the
+        chain runs its 'act' backward; weighted_avg adds the coordinate gradient through its softmax weights."""
+        b, m, k = rec["b"], rec["m"], rec["k"]
+        g = g_out.reshape(b * m, -1).contiguous()
+        if self.mlp2:
+            g = mlp_chain_backward(rec["recs2"], g, "plain", need_input_grad=True)
+        last = rec["recs"][-1]
+        c = last["layer"].cout
+        need_feat = need_feat_grad and rec["points"] is not None
+        dy = M.sa_pool_grad(g, k, c, self.pooling, w=rec["weights"], argmax=rec["argmax"])
+        dv = None
+        if need_xyz_grad and self.pooling == "weighted_avg":
+            new_xyz, idx = (None, None) if self.group_all else (rec["new_xyz"], rec["idx"])
+            dv = M.sa_pool_weights_grad(rec["xyz"], new_xyz, idx, last["z"], last["scale"], last["shift"], last["layer"].relu, g,
+                                        rec["weights"])
+        xyz = rec["xyz"]
+        n = xyz.shape[1]
+        if not self.group_all:
+            h = mlp_chain_backward(rec["recs"], dy, "act", need_input_grad=need_feat)
+            return self._first_layer_backward(rec, h, need_feat, need_xyz_grad, d_rows_xyz_extra=dv)
+        # group_all: the chain's input is the dense [xyz | points]; its gradient splits into the two blocks
+        dx = mlp_chain_backward(rec["recs"], dy, "act", need_input_grad=need_feat or need_xyz_grad)
+        d_feat = d_xyz = None
+        if need_feat:
+            c_in = rec["points"].shape[2]
+            d_feat = torch.empty((b * n, c_in), dtype=torch.float32, device=xyz.device)
+            M.row_segments(b * n, [(d_feat, dx[:, 3:3 + c_in], None)])
+            d_feat = d_feat.view(b, n, c_in)
+        if need_xyz_grad:
+            d_xyz = torch.empty((b * n, 3), dtype=torch.float32, device=xyz.device)
+            M.row_segments(b * n, [(d_xyz, dx[:, :3], dv)])
+            d_xyz = d_xyz.view(b, n, 3)
+        return d_feat, d_xyz
+
+    def _first_layer_backward(self, rec, h, need_feat, need_xyz_grad, d_rows_xyz_extra=None):
         """Backward of z = P[idx] + dxyz W[0:3] (P = feat W[3:]) given dz (rows, cout):
              dW[0:3] += dxyz^T dz                     (over the grouped rows)
              S = scatter-add of dz rows by idx        (b, n, cout)  -- GroupPointGrad on the layer OUTPUT width
@@ -987,6 +1087,8 @@ class SAModule:
                     d_feat, _, _ = M.group_concat_grad(d_rows_feat, None, idx, pts_cnt, n, c)
         if need_xyz_grad:
             d_rows_xyz = M.rows_dot3(dz, W[:3])  # dz W[0:3]^T, three columns: a streaming kernel, not a 128-wide GEMM tile
+            if d_rows_xyz_extra is not None:  # weighted_avg: the gradient through the pooling weights, also per grouped row
+                d_rows_xyz = add_rows(d_rows_xyz, d_rows_xyz_extra)
             _, d_xyz, d_new = M.group_concat_grad(None, d_rows_xyz, idx, pts_cnt, n, 0)
             d_xyz = tf_sampling.gather_point_grad_raw(n, rec["fps_idx"], d_new, into=d_xyz)  # new_xyz = gather(xyz, fps_idx): accumulated in place
         return d_feat, d_xyz
