@@ -12,6 +12,8 @@ Workloads:
     train : forward + the reference's loss graph + backward + (N>1: one RCCL all-reduce of the flat gradient bucket) + Adam
     fwd   : forward only (BASELINE.json configs[1] plus voting + proposal)
 Inputs are resident in HBM before the timed region.  One JSON line on rank 0.
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, --dump-outputs, the line.  --full adds every other
+leg after the timed region (variant steps, GEMM roofline, kernels alone, BASELINE configs, CPU baseline, N > 1 self-check).
 --dump-outputs DIR: what the last timed step returned (train: also the loss terms and the gradient) as DIR/<name>.npy; for train,
 that step starts from the seeded parameters (see init_flat in main), so two runs with the same arguments agree up to rounding.
 """
@@ -41,9 +43,13 @@ def parse():
     ap.add_argument("--points", type=int, default=20480, help="points per scene (config.py:1)")
     ap.add_argument("--workload", default=None, choices=["train", "fwd"])
     ap.add_argument("--scene", default="room", choices=["room", "uniform"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, every other leg of the line: variant steps, GEMM roofline, kernels alone on the GPU, "
+                         "BASELINE configs, CPU baseline, dp collectives, and with N > 1 the data-parallel self-check")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline (and no CPU timing in the configs)")
     ap.add_argument("--dry-run", action="store_true", help="launcher self-test on CPU (gloo rendezvous, no kernels, nothing measured)")
-    ap.add_argument("--headline-only", action="store_true", help="skip the extra unpipelined / alone-on-the-GPU measurements (profiling)")
+    ap.add_argument("--headline-only", action="store_true",
+                    help="with --full: skip the extra unpipelined / alone-on-the-GPU measurements (profiling); without --full nothing else runs anyway")
     ap.add_argument("--no-gram", action="store_true", help="pooled layers: direct backward GEMMs on the stored z instead of the Gram form")
     ap.add_argument("--check-dp", action="store_true",
                     help="data-parallel self-check instead of a measurement: in deterministic mode, train steps with the overlapped "
@@ -403,6 +409,10 @@ def main():
     from votenet_amd import synth, tf_grouping, tf_sampling
     have_train = hasattr(VM.VoteNetHotPath, "train_step")
     workload = args.workload or ("train" if have_train else "fwd")
+    # what runs after the timed region besides the line itself: nothing in a plain run (its wall time outside the steps is what a
+    # caller of the headline waits for); --full: the legs below, narrowed by --headline-only / --no-cpu-baseline as before
+    legs = args.full and not args.headline_only
+    cpu_legs = args.full and not args.no_cpu_baseline
 
     B, n = args.batch, args.points
     gen = synth.room_batch if args.scene == "room" else synth.uniform_batch
@@ -540,7 +550,7 @@ def main():
     if tf_sampling.PROFILE_EVENTS is not None:  # steps <= 2
         events, tf_sampling.PROFILE_EVENTS = tf_sampling.PROFILE_EVENTS, None
         bq_events, tf_grouping.PROFILE_EVENTS = tf_grouping.PROFILE_EVENTS, None
-    if not args.headline_only:  # the GEMM launches of two more steps, outside the timed region (see above); every rank steps (collectives)
+    if legs:  # the GEMM launches of two more steps, outside the timed region (see above); every rank steps (collectives)
         vmlp.PROFILE_EVENTS = []
         vmlp.PROFILE_SHAPES = True  # entries carry (rows, cin, cout, note): the per-family table of roofline_mlp
         for _ in range(gemm_steps):
@@ -568,7 +578,7 @@ def main():
     # the same step with every batch's geometry computed inside its own step (nothing carried across steps): reported beside
     # the headline value, not instead of it
     in_step = None
-    if pipeline and not args.headline_only:
+    if pipeline and legs:
         pipe_on[0] = False
         k2 = max(2, min(args.steps, 20))
         for _ in range(2):
@@ -595,7 +605,7 @@ def main():
 
     # the same step in bit-reproducible mode (votenet_amd.set_deterministic: no fp32 atomics anywhere in the backward pass)
     det_step = None
-    if workload == "train" and world == 1 and not args.headline_only:
+    if workload == "train" and world == 1 and legs:
         import votenet_amd
         prev = votenet_amd.set_deterministic(True)
         try:
@@ -619,7 +629,7 @@ def main():
 
     # the same step with every GEMM on the fp32 MFMA kernels (v_mfma_f32_32x32x2_f32) instead of bf16 x 3 split operands
     fp32_step = None
-    if world == 1 and not args.headline_only:
+    if world == 1 and legs:
         from votenet_amd import _lib as vlib
         vmlp.debug_switch("fast_bf3", 0)
         vmlp.debug_switch("gram_bf3", 0)
@@ -646,7 +656,7 @@ def main():
 
     # the same step with the FORWARD operands on bf16 x 3 again (the round-3..5 form: six MFMAs per product instead of three fp16 ones)
     bf3_step = None
-    if world == 1 and not args.headline_only and workload == "train" and vmlp.FORWARD_H2:
+    if world == 1 and legs and workload == "train" and vmlp.FORWARD_H2:
         vmlp.FORWARD_H2 = False
         net.store.rebuild_split()
         try:
@@ -671,7 +681,7 @@ def main():
     # the same step on the FULL row layout (64 rows per ball, copies of slot 0 included: the reference's tensor shape), and what the
     # piece layout keeps of each level's grouped rows on these scenes
     full_step = row_layout = None
-    if world == 1 and not args.headline_only and workload == "train":
+    if world == 1 and legs and workload == "train":
         from votenet_amd import pointnet2 as vp2
         if vp2.HALF_GROUPS:
             tape = []
@@ -706,7 +716,7 @@ def main():
 
     # the same two kernels alone on the GPU (in the timed region they share it with the GEMMs of the previous batch)
     iso_fps = iso_bq = None
-    if rank == 0 and not args.headline_only:
+    if rank == 0 and legs:
         tf_sampling.PROFILE_EVENTS, tf_grouping.PROFILE_EVENTS = [], []
         for _ in range(5):
             net.sa1.geometry(xs[0])
@@ -721,7 +731,7 @@ def main():
     # collectives run through RCCL and the three-stream ordering on this GPU (labelled: it measures the path, not xGMI)
     comm = dp.comm_info(dev)
     dp_coll = None
-    if workload == "train" and not args.headline_only and not os.environ.get("VOTENET_BENCH_NO_DP_LEG"):
+    if workload == "train" and legs and not os.environ.get("VOTENET_BENCH_NO_DP_LEG"):
         try:
             one_rank = False
             if world == 1:
@@ -759,9 +769,9 @@ def main():
                 raise
             dp_coll = {"error": repr(e)[:300]}
     # N > 1: the line validates its own data-parallel path -- overlapped exchange == blocking exchange on every rank, replicas identical
-    # across ranks, N distinct devices in the communicator (check_dp; the same comparison as `--check-dp`, two steps)
+    # across ranks, N distinct devices in the communicator (check_dp; the same comparison as `--check-dp`, two steps; --full only)
     check = None
-    if workload == "train" and world > 1 and args.scene == "room" and not os.environ.get("VOTENET_BENCH_NO_DP_LEG"):
+    if args.full and workload == "train" and world > 1 and args.scene == "room" and not os.environ.get("VOTENET_BENCH_NO_DP_LEG"):
         import votenet_amd
         prev_det = votenet_amd.set_deterministic(True)
         try:
@@ -926,10 +936,10 @@ def main():
         # every BASELINE.json configuration in this line (1: single SA layer, 2: backbone forward, 3b: predict tower + NMS,
         # 5: dense 80000-pt scan; 3a = the headline value, 4 = this command with --gpus 8) + what the ball query really scans
         cfgs = bq_detail = None
-        if world == 1 and not args.headline_only:
+        if world == 1 and legs:
             sys.path.insert(0, os.path.join(ROOT, "tools"))
             import bench_legs
-            cfgs = bench_legs.config_legs(net, xs, gts, dev, B, n, cpu=not args.no_cpu_baseline)
+            cfgs = bench_legs.config_legs(net, xs, gts, dev, B, n, cpu=cpu_legs)
             cfgs["config3_train_step"] = "= the headline value of this line (forward + loss graph + backward + clip/Adam)"
             cfgs["config4_dp8"] = "python bench.py --gpus 8 (one rank per GPU, RCCL all-reduce of the flat gradient bucket, tail overlapped with backward)"
             bq_detail = bench_legs.ball_query_detail(net.sa1, xs[0], torch.from_numpy(synth.uniform_batch(B, n, 1000)).to(dev))
@@ -951,11 +961,11 @@ def main():
                     "after_the_timed_region_s": round(t_end_gpu - t_phase0 - t_setup - dt, 3),
                     "total_s": round(t_end_gpu - t_phase0, 3), "run_wall_s_so_far": round(t_end_gpu - T_PROCESS_START, 3),
                     "what": "wall seconds (host clock between device synchronisations) of the phases in which this process kept the GPU's queues "
-                            "fed: set-up + warm-up steps, the timed region, and everything after it (roofline / variant steps, the kernels alone, "
-                            "the config legs: %.1f s, of which a few seconds are the CPU oracle's config-1 layer with an idle GPU); an UPPER bound of "
-                            "GPU-busy time -- a 5 s utilisation sampler sees 0 %% because the timed region is %.2f s long and the rest of the run is "
-                            "the CPU baseline and the interpreter's start" % (t_end_gpu - t_legs0, dt)}
-        if world == 1 and not args.no_cpu_baseline:  # last: its OpenMP threads keep the host busy for a while after they finish
+                            "fed: set-up + warm-up steps, the timed region, and everything after it (with --full: roofline / variant steps, the kernels "
+                            "alone, the config legs: %.1f s, of which a few seconds are the CPU oracle's config-1 layer with an idle GPU); an UPPER bound "
+                            "of GPU-busy time -- a 5 s utilisation sampler sees 0 %% because the timed region is %.2f s long and the rest of the run is "
+                            "the interpreter's start (and with --full the CPU baseline)" % (t_end_gpu - t_legs0, dt)}
+        if world == 1 and cpu_legs:  # last: its OpenMP threads keep the host busy for a while after they finish
             if pinned and full_mask:
                 hostpin.unpin(full_mask)  # the CPU oracle runs on ALL cores: every thread of the process gets the full mask back
             cpu = cpu_baseline(n, args.scene)

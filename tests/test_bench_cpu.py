@@ -35,6 +35,10 @@ def test_default_arguments_are_one_gpu_and_a_short_run(monkeypatch):
     monkeypatch.setattr(sys, "argv", ["bench.py"])
     a = bench.parse()
     assert a.gpus == 1 and a.steps <= 50 and a.batch == 8 and a.points == 20480 and not a.no_pipeline
+    assert not a.full  # a plain run: only what the headline needs
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-cpu-baseline"])
+    a = bench.parse()
+    assert a.full and a.no_cpu_baseline and not a.headline_only
 
 
 def _run_bench(*argv, env=None):

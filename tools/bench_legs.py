@@ -1,4 +1,4 @@
-"""The measurement legs bench.py adds to its JSON line besides the headline value:
+"""The measurement legs bench.py --full adds to its JSON line besides the headline value:
 
   cpu_baseline   the CPU oracle (oracle/, the restatement of the reference's CPU path) timed on the GPU box's host:
                  single thread (the reference's loop structure) AND all cores (the same sources with OpenMP), CPU model and

@@ -17,7 +17,7 @@ bash tools/pmc_pieces.sh > $O/pmc_pieces.log 2>&1
 python3 tools/probe/fps_time.py > $O/fps_time.txt 2>&1
 python3 tools/cpu_issue_time.py > $O/issue_pinned.txt 2>&1
 NO_PIN=1 python3 tools/cpu_issue_time.py > $O/issue_unpinned.txt 2>&1
-python3 bench.py > $O/train_bench_line.json 2> $O/train_bench.err
+python3 bench.py --full > $O/train_bench_line.json 2> $O/train_bench.err
 VOTENET_NO_PIN=1 python3 bench.py --headline-only --no-cpu-baseline > $O/train_bench_line_unpinned.json 2> $O/train_bench_unpinned.err
-python3 bench.py --workload fwd > $O/fwd_bench_line.json 2> $O/fwd_bench.err
+python3 bench.py --full --workload fwd > $O/fwd_bench_line.json 2> $O/fwd_bench.err
 tail -c 300 $O/train_bench_line.json; cat $O/fps_time.txt | tail -1; tail -3 $O/issue_pinned.txt; tail -3 $O/issue_unpinned.txt

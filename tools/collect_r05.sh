@@ -17,6 +17,6 @@ bash tools/pmc_pieces.sh > $O/pmc_pieces.log 2>&1
 bash tools/pmc_fps.sh $(basename $O)_pmcfps > $O/pmc_fps.log 2>&1
 python3 tools/probe/stretch_time.py > $O/stretch_time.txt 2>&1
 python3 tools/cpu_issue_time.py > $O/issue_pinned.txt 2>&1
-python3 bench.py > $O/train_bench_line.json 2> $O/train_bench.err
-python3 bench.py --workload fwd > $O/fwd_bench_line.json 2> $O/fwd_bench.err
+python3 bench.py --full > $O/train_bench_line.json 2> $O/train_bench.err
+python3 bench.py --full --workload fwd > $O/fwd_bench_line.json 2> $O/fwd_bench.err
 tail -c 300 $O/train_bench_line.json; head -3 $O/stretch_time.txt; tail -3 $O/issue_pinned.txt
