@@ -1,7 +1,9 @@
 """End-to-end check on synthetic rooms (GPU box only): train the hot path with the reference's loss, then run the predict
 tower (decode -> 3D NMS) on held-out scenes and report mAP@0.25 / @0.5 with the reference's evaluator logic.
-    python tools/train_eval.py [steps] [train_batches]"""
-import os, sys, time
+    python tools/train_eval.py [steps] [train_batches] [--save PATH] [--resume PATH]
+--save PATH: a checkpoint (VoteNetHotPath.save) at every evaluation and at the end.  --resume PATH: continue the run a checkpoint
+holds -- parameters, moving averages, Adam state and step count -- up to `steps` steps in all, on the batches it would have seen."""
+import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import importlib.util
 _spec = importlib.util.spec_from_file_location("votenet_hostpin", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "votenet_amd", "hostpin.py"))
@@ -11,12 +13,20 @@ import numpy as np, torch
 from votenet_amd import evaluator as E, loss as VL, synth
 from votenet_amd.model import VoteNetHotPath
 
-steps = int(sys.argv[1]) if len(sys.argv) > 1 else 600
-nb = int(sys.argv[2]) if len(sys.argv) > 2 else 16
+ap = argparse.ArgumentParser()
+ap.add_argument("steps", nargs="?", type=int, default=600)
+ap.add_argument("train_batches", nargs="?", type=int, default=16)
+ap.add_argument("--save", metavar="PATH", help="write a checkpoint at every evaluation and at the end")
+ap.add_argument("--resume", metavar="PATH", help="continue from this checkpoint")
+args = ap.parse_args()
+steps, nb = args.steps, args.train_batches
 dev = torch.device("cuda:0")
 B, n = 8, 20480
 net = VoteNetHotPath(dev, seed=0)
 net.init_optimizer(1e-3)
+if args.resume:
+    net.load(args.resume)
+start = net._step
 xs = [torch.from_numpy(synth.room_batch(B, n, 5000 + B * i)).to(dev) for i in range(nb)]
 gts = [VL.gt_to_device(synth.room_gt(B, n, 5000 + B * i), dev) for i in range(nb)]
 val_x = [torch.from_numpy(synth.room_batch(B, n, 90000 + B * i)).to(dev) for i in range(4)]
@@ -34,9 +44,15 @@ def evaluate():
     return res
 
 
+def save():
+    if args.save:
+        net.save(args.save)
+        print("step %d: saved %s" % (net._step, args.save))
+
+
 t0 = time.time()
-print("step 0: mAP", evaluate())
-for i in range(steps):
+print("step %d: mAP" % start, evaluate())
+for i in range(start, steps):
     net.train_step(xs[i % nb], gt=gts[i % nb], next_x=xs[(i + 1) % nb])  # geometry of the next batch under this step
     if (i + 1) % 100 == 0:
         l = net.last_losses.cpu().numpy()
@@ -44,3 +60,6 @@ for i in range(steps):
                                                                                               time.time() - t0))
     if (i + 1) % 300 == 0:
         print("step %d: mAP" % (i + 1), evaluate())
+        save()
+if steps % 300 or steps <= start:  # (a run that ends on an evaluation has just saved)
+    save()

@@ -12,8 +12,11 @@ the hot path can be driven, checked and timed end to end:
     proposal SA on votes, FPS on seeds (utils.py:42-43), 256 x r0.3 K64 [128,128,128] + [128,128,79]
 """
 
+import math
+
 import torch
 
+from . import checkpoint
 from . import dp
 from . import mlp as M
 from . import pointnet2 as P
@@ -24,6 +27,7 @@ SIDE_PRIORITY = 0   # HIP stream priorities of the geometry (prefetch) streams a
 WGRAD_PRIORITY = 0
 PROPOSAL_NUM = 256       # config.py:6
 PROPOSAL_OUT = 5 + 2 * NH + 4 * NS + NC  # model.py:91 -> 79
+LEARNING_RATE = 1e-3     # the initial value of the reference's learning_rate variable (model.py:241)
 
 
 GEOMETRY_GRAPHS = True  # prefetch_geometry replays the coordinate-only chain of a batch as ONE HIP graph (GeometryGraph) instead of enqueuing its ~50 launches
@@ -917,9 +921,8 @@ class VoteNetHotPath:
         self.__dict__.setdefault("_prefetched", {}).clear()
         self._geometry_current = None
 
-    def init_optimizer(self, lr=1e-3):
+    def init_optimizer(self, lr=LEARNING_RATE):
         s = self.store
-        import math
         base = s.flat.data_ptr()
         seg = []
         for name, shape, _ in s._specs:  # [start, end) of every tensor inside the flat bucket
@@ -931,6 +934,34 @@ class VoteNetHotPath:
         self._v = torch.zeros_like(s.flat)
         self._step = 0
         self._lr = lr
+
+    def set_lr(self, lr):
+        """The rate of the following Adam steps (the reference's ScheduledHyperParamSetter('learning_rate', ...), run.py:113); it is
+        part of the optimizer state a checkpoint keeps, so a resumed run continues the schedule."""
+        lr = float(lr)
+        if not (math.isfinite(lr) and lr >= 0.0):
+            raise ValueError("set_lr: the learning rate must be finite and >= 0, got %r" % lr)
+        if not hasattr(self, "_seg"):
+            self.init_optimizer(lr)
+        self._lr = lr
+
+    # ---- checkpoints (checkpoint.py: the reference's variable names, restored in place) ---------------------------------------
+    def state_dict(self, optimizer=True):
+        """Reference variable name -> numpy array: parameters, BatchNorm moving averages and (optimizer=True) the Adam moments,
+        global_step and learning_rate."""
+        return checkpoint.state_dict(self, optimizer)
+
+    def load_state_dict(self, sd, strict=True):
+        """Copy a state_dict() into this model's live buffers in place; ValueError (model untouched) when it does not fit."""
+        checkpoint.load_state_dict(self, sd, strict)
+
+    def save(self, path, optimizer=True):
+        """Write the state to an .npz file at `path` (numeric arrays + a JSON header)."""
+        checkpoint.save(self, path, optimizer)
+
+    def load(self, path, strict=True):
+        """Restore a file written by save(): in place, between two train_step calls or before predict."""
+        checkpoint.load(self, path, strict)
 
     def train_step(self, x, cot=None, world=1, gt=None, next_x=None):
         """forward + loss + backward + (world>1: the RCCL all-reduce of the flat gradient bucket, its tail overlapped with the
