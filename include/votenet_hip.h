@@ -709,6 +709,30 @@ int votenet_augment_boxes(int b, int n_box_out, const long *box_offset, const do
                           int *heading_labels, float *heading_residuals, int *size_labels, float *size_residuals,
                           void *stream);
 
+/* Which labelled objects of a scene become ground truth (dataset.py:237-283,300), before any augmentation.  The points
+ * tested are the rows votenet_subsample_augment picks for the same (raw, raw_f64, raw_stride, raw_offset, n_out, choice |
+ * seed, scene0), un-augmented, in upright-depth coordinates.  rtilt, kmat: HOST (b,9) doubles, the row-major Rtilt and K of
+ * SUNRGBD_Calibration (sunutils.py:59-64).  Scene s owns objects [obj_offset[s], obj_offset[s+1]) (HOST, b+1, from 0) of the
+ * device arrays cls (int; < 0: not whitelisted), box2d (xmin, ymin, xmax, ymax), centroid (3), half_extent (l, w, h as
+ * sunutils.py:21-24 names them) and heading (-atan2(orientation[1], orientation[0])), doubles.
+ * A point is in an object's frustum iff its pixel (sunutils.py:85-99) has xmin <= u < xmax and ymin <= v < ymax
+ * (dataset.py:243-244), and inside its box iff |rotz(-heading)^T (p - centroid)| <= (l, w, h) component-wise (the closed
+ * form of the hull test of sunutils.py:199-209).  The box is degenerate iff the eight corners of compute_box_3d
+ * (sunutils.py:212-241), turned to the upright-camera frame, span less than 1e-7 in y.  status (one per object): 0 kept,
+ * 1 not whitelisted, 2 degenerate, 3 fewer than 5 points in frustum and box; n_inside: that count (0 for status 1, 2).
+ * Kept objects are written in label order, compacted over the whole batch: center ((corner0 + corner6) / 2, upright-camera
+ * frame), size (2l, 2w, 2h), heading_out, cls_out -- the inputs of votenet_augment_boxes -- and kept_count[s] of them
+ * belong to scene s.  inside: NULL, or (objects, n_out) bytes: 1 where the point is in frustum and box (0 for status 1, 2).
+ * All outputs are device memory; integer counts make them independent of scheduling.  workspace:
+ * votenet_select_boxes_workspace_bytes(b, obj_offset[b]) bytes of device scratch. */
+size_t votenet_select_boxes_workspace_bytes(int b, long n_obj);
+int votenet_select_boxes(int b, int n_out, const void *raw, int raw_f64, int raw_stride, const long *raw_offset,
+                         const int *choice, unsigned long long seed, long scene0, const double *rtilt, const double *kmat,
+                         const long *obj_offset, const int *cls, const double *box2d, const double *centroid,
+                         const double *half_extent, const double *heading, double *center, double *size,
+                         double *heading_out, int *cls_out, int *kept_count, int *n_inside, int *status,
+                         unsigned char *inside, void *workspace, size_t workspace_bytes, void *stream);
+
 /* 3D IoU (the arithmetic of tf_nms3d.cpp:178-192) of every box of set A (b,n,8,3) against every box of set B
  * (b,m,8,3) of the same scene -> iou (b,n,m): the detections-vs-ground-truth overlaps of evaluator.py:26-39,122-132. */
 int votenet_iou3d_cross(int b, int n, int m, const float *boxes_a, const float *boxes_b, float *iou, void *stream);

@@ -30,3 +30,32 @@ pk = lambda a: IP.pack_ragged(a, dev)
 dc, boff = pk([rng.normal(size=(c, 3)) for c in cnt]); ds, _ = pk([np.abs(rng.normal(size=(c, 3))) + .3 for c in cnt])
 dh, _ = pk([rng.uniform(-3, 3, c) for c in cnt]); dk, _ = pk([rng.integers(0, 10, c).astype(np.int32) for c in cnt])
 print("boxes: %.4f ms / batch" % timeit(lambda: IP.augment_boxes(dc, ds, dh, dk, boff, aug), it=50))
+
+# ---- ground-truth selection (votenet_select_boxes) and the whole path parsed scene -> model inputs (build_batch):
+# 8 scenes x 50 000 - 200 000 raw rows -> 20 480, 4 / 16 / 32 objects per scene.  Median and spread of repeated timed launches.
+from votenet_amd import sunrgbd
+def med(fn, rep=9, it=20):
+    t = sorted(timeit(fn, it=it) for _ in range(rep))
+    return t[len(t) // 2], t[0], t[-1]
+n_raws = rng.integers(50000, 200001, b)
+clouds = [np.column_stack([rng.uniform(-3, 3, n), rng.uniform(0.5, 7, n), rng.uniform(-1.5, 1.5, n)]).astype(np.float32) for n in n_raws]
+raw, off = IP.pack_ragged(clouds, dev)
+calib = (np.tile(np.eye(3), (b, 1, 1)), np.tile(np.array([[529.5, 0, 365.0], [0, 529.5, 265.0], [0, 0, 1.0]]), (b, 1, 1)))
+print("selection: %d scenes, raw rows %s -> %d" % (b, [int(n) for n in n_raws], n_out))
+print("  subsample_augment + augment_boxes (what the pipeline cost before the selection): %.4f ms (min %.4f, max %.4f)"
+      % med(lambda: (IP.subsample_augment(raw, off, n_out, aug, None, seed=3), IP.augment_boxes(dc, ds, dh, dk, boff, aug))))
+for nobj in (4, 16, 32):
+    scenes = []
+    for s in range(b):
+        cen = np.column_stack([rng.uniform(-2, 2, nobj), rng.uniform(2, 6, nobj), rng.uniform(-1, 1, nobj)])
+        scenes.append({"cls": rng.integers(0, 10, nobj).astype(np.int32), "box2d": np.tile([-1e4, -1e4, 1e4, 1e4], (nobj, 1)),
+                       "centroid": cen, "half_extent": rng.uniform(0.3, 0.9, (nobj, 3)), "heading": rng.uniform(-3, 3, nobj)})
+    objects = sunrgbd.pack_objects(scenes)
+    dobj = {k: (torch.from_numpy(v).to(dev) if k != "obj_offset" else v) for k, v in objects.items()}  # labels staged once
+    pairs = b * n_out * nobj
+    ms, lo, hi = med(lambda: IP.select_boxes(raw, off, calib, dobj, n_out, None, seed=3))
+    print("  %2d objects: select_boxes %.4f ms (min %.4f, max %.4f; incl. the read-back of %d counts)  %.1f G pair/s"
+          % (nobj, ms, lo, hi, b, pairs / ms / 1e6))
+    ms, lo, hi = med(lambda: IP.build_batch(raw, off, calib, dobj, aug, None, seed=3))
+    kept = len(IP.build_batch(raw, off, calib, dobj, aug, None, seed=3)[2])
+    print("  %2d objects: build_batch  %.4f ms (min %.4f, max %.4f; %d of %d scenes kept)" % (nobj, ms, lo, hi, kept, b))

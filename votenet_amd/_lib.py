@@ -108,6 +108,8 @@ _SIGS.update({
     "votenet_subsample_augment": [ctypes.c_int, ctypes.c_int, _c_f, ctypes.c_int, ctypes.c_int, _c_f, _c_f, ctypes.c_ulonglong,
                                   ctypes.c_long, ctypes.c_int] + [_c_f] * 5 + [ctypes.c_void_p],
     "votenet_augment_boxes": [ctypes.c_int, ctypes.c_int] + [_c_f] * 11 + [ctypes.c_int, ctypes.c_int] + [_c_f] * 8 + [ctypes.c_void_p],
+    "votenet_select_boxes": [ctypes.c_int, ctypes.c_int, _c_f, ctypes.c_int, ctypes.c_int, _c_f, _c_f, ctypes.c_ulonglong,
+                             ctypes.c_long] + [_c_f] * 17 + [ctypes.c_size_t, ctypes.c_void_p],
     "votenet_transpose_segments": [ctypes.c_int] + [_c_f] * 3 + [ctypes.c_void_p],
     "votenet_split_weights": [ctypes.c_int, _c_f, ctypes.c_void_p],
     "votenet_split_weights_h2": [ctypes.c_int, _c_f, ctypes.c_void_p],
@@ -258,6 +260,8 @@ def lib():
         L.votenet_loss_workspace_floats.argtypes = [ctypes.c_int]
         L.votenet_knn_workspace_bytes.restype = ctypes.c_size_t
         L.votenet_knn_workspace_bytes.argtypes = [ctypes.c_int] * 3
+        L.votenet_select_boxes_workspace_bytes.restype = ctypes.c_size_t
+        L.votenet_select_boxes_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_long]
         L.votenet_nms3d_workspace_bytes.restype = ctypes.c_size_t
         L.votenet_nms3d_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int]
         L.votenet_mlp_split_k_floats.restype = ctypes.c_long

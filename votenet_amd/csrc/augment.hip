@@ -17,35 +17,6 @@ struct AugScenes {
     unsigned key[AUG_CHUNK];
 };
 
-__host__ __device__ inline unsigned lowbias32(unsigned x)
-{
-    x ^= x >> 16;
-    x *= 0x7feb352du;
-    x ^= x >> 15;
-    x *= 0x846ca68bu;
-    x ^= x >> 16;
-    return x;
-}
-
-// keyed permutation of [0, n): balanced Feistel network over the next even number of bits, cycle walking back into range
-__device__ __forceinline__ long feistel_perm(long j, long n, unsigned key, int half)
-{
-    const unsigned mask = (1u << half) - 1u;
-    unsigned long long x = (unsigned long long)j;
-    do {
-        unsigned l = (unsigned)(x >> half) & mask, r = (unsigned)x & mask;
-#pragma unroll
-        for (int round = 0; round < 6; round++) {
-            const unsigned f = lowbias32(r + key + 0x9E3779B9u * (unsigned)(round + 1)) & mask;
-            const unsigned nl = r;
-            r = l ^ f;
-            l = nl;
-        }
-        x = ((unsigned long long)l << half) | r;
-    } while (x >= (unsigned long long)n);
-    return (long)x;
-}
-
 template <typename T>
 __global__ __launch_bounds__(256) void subsample_augment_kernel(AugScenes P, int n_out, const T *__restrict__ raw, int stride,
                                                                 const int *__restrict__ choice, int to_camera, int train,
@@ -162,12 +133,6 @@ __global__ void augment_boxes_kernel(AugScenes P, int bb, const double *__restri
         O.sres[o * 3 + 1] = (float)((w - M.v[km][1]) / M.v[km][1]);
         O.sres[o * 3 + 2] = (float)((h - M.v[km][2]) / M.v[km][2]);
     }
-}
-
-static unsigned scene_key(unsigned long long seed, long scene)
-{
-    const unsigned hi = lowbias32((unsigned)(seed >> 32) + 0x632BE5ABu * (unsigned)(scene + 1));
-    return lowbias32((unsigned)seed ^ hi ^ (0x85EBCA6Bu * (unsigned)(scene + 1)));
 }
 
 } // namespace votenet

@@ -145,6 +145,43 @@ inline SpatialIndex spatial_index_view(float *base, int b, int n)
 }
 int build_spatial_index(int b, int n, const float *xyz, float *index, hipStream_t st); // fps.hip
 
+// ---- the device-side row draw of the input pipeline (augment.hip, select_boxes.hip): scene s of a call takes rows
+// feistel_perm(0 .. n_out-1) of its raw cloud under scene_key(seed, scene0 + s) ----
+__host__ __device__ inline unsigned lowbias32(unsigned x)
+{
+    x ^= x >> 16;
+    x *= 0x7feb352du;
+    x ^= x >> 15;
+    x *= 0x846ca68bu;
+    x ^= x >> 16;
+    return x;
+}
+
+// keyed permutation of [0, n): balanced Feistel network over the next even number of bits, cycle walking back into range
+__device__ __forceinline__ long feistel_perm(long j, long n, unsigned key, int half)
+{
+    const unsigned mask = (1u << half) - 1u;
+    unsigned long long x = (unsigned long long)j;
+    do {
+        unsigned l = (unsigned)(x >> half) & mask, r = (unsigned)x & mask;
+#pragma unroll
+        for (int round = 0; round < 6; round++) {
+            const unsigned f = lowbias32(r + key + 0x9E3779B9u * (unsigned)(round + 1)) & mask;
+            const unsigned nl = r;
+            r = l ^ f;
+            l = nl;
+        }
+        x = ((unsigned long long)l << half) | r;
+    } while (x >= (unsigned long long)n);
+    return (long)x;
+}
+
+inline unsigned scene_key(unsigned long long seed, long scene)
+{
+    const unsigned hi = lowbias32((unsigned)(seed >> 32) + 0x632BE5ABu * (unsigned)(scene + 1));
+    return lowbias32((unsigned)seed ^ hi ^ (0x85EBCA6Bu * (unsigned)(scene + 1)));
+}
+
 // ---- wave64 cross-lane helpers (DPP; no LDS traffic) ----
 // dpp_ctrl encodings (gfx9): quad_perm 0x00-0xFF, row_shr:n 0x110+n, row_mirror 0x140,
 // row_half_mirror 0x141, row_bcast:15 0x142, row_bcast:31 0x143.

@@ -4,6 +4,8 @@ The reference builds every training sample in numpy inside MyDataFlow.__iter__ (
 config.POINT_NUM points + depth->camera axes, :219-231 the augmentation draws, :262-276 the box side, :302-308 the point
 side) and pads the ragged ground truth in BatchData2Biggest (run.py:14-24,60-64).  Here the DRAWS stay on the host, in the
 reference's order, and the work is two kernels over the whole batch (votenet_subsample_augment, votenet_augment_boxes).
+Which labelled objects a scene trains on (dataset.py:237-283,300: image frustum, 3D box, at least 5 points) is decided on
+the device too (votenet_select_boxes); build_batch chains the three from parsed scene files (sunrgbd.py) to the model's inputs.
 There is no CPU path: without libvotenet_hip.so these functions raise.
 """
 import ctypes
@@ -130,3 +132,119 @@ def augment_boxes(center, size, heading, cls, box_offset, aug=None, mean_size=ME
                                               _hp(ang), _hp(c), _hp(s), _hp(sc), _hp(ms), ms.shape[0], nh,
                                               *[L.ptr(out[k]) for k, _, _ in GT_FIELDS], L.stream_ptr()))
     return out
+
+
+def _calib_arrays(calib, b, what):
+    """calib: (Rtilt (b,3,3), K (b,3,3)) or a list of b (Rtilt, K) pairs (sunrgbd.parse_calib) -> two host (b,9) float64."""
+    if isinstance(calib, (list,)) or (isinstance(calib, tuple) and len(calib) and isinstance(calib[0], (tuple, list))):
+        if len(calib) != b:
+            raise L.InvalidArgumentError("%s: %d scenes but %d calibrations" % (what, b, len(calib)))
+        calib = (np.stack([np.asarray(c[0], np.float64) for c in calib]), np.stack([np.asarray(c[1], np.float64) for c in calib]))
+    rt, km = (np.ascontiguousarray(np.asarray(a, dtype=np.float64)).reshape(-1, 9) for a in calib)
+    if rt.shape[0] != b or km.shape[0] != b:
+        raise L.InvalidArgumentError("%s: %d scenes but %d / %d calibrations" % (what, b, rt.shape[0], km.shape[0]))
+    return rt, km
+
+
+def _check_raw(raw, raw_offset, n_out, choice, what):
+    """The argument checks subsample_augment makes, for the entries that pick the same rows.  -> (raw, off, b, choice tensor)."""
+    if not torch.is_tensor(raw) or raw.dim() != 2 or raw.dtype not in (torch.float32, torch.float64) or not raw.is_cuda:
+        raise L.InvalidArgumentError("%s: raw must be a 2-D float32 / float64 device tensor" % what)
+    raw = raw.contiguous()
+    off = np.ascontiguousarray(raw_offset, dtype=np.int64)
+    b = len(off) - 1
+    if b < 1 or off[0] < 0 or off[-1] > raw.shape[0] or np.any(np.diff(off) < 0):
+        raise L.InvalidArgumentError("%s: raw_offset does not describe rows of raw" % what)
+    ch = None
+    if choice is not None:
+        if tuple(choice.shape) != (b, n_out):
+            raise L.InvalidArgumentError("%s: choice must be (b, n_out)" % what)
+        if torch.is_tensor(choice) and choice.is_cuda:  # already on the device: not read back (the kernel clamps the index)
+            ch = choice.to(torch.int32).contiguous()
+        else:
+            chn = np.asarray(choice)
+            if np.any(chn < 0) or np.any(chn >= np.diff(off)[:, None]):
+                raise L.InvalidArgumentError("%s: choice index out of range" % what)
+            ch = torch.from_numpy(np.ascontiguousarray(chn, dtype=np.int32)).to(raw.device)
+    return raw, off, b, ch
+
+
+_OBJECT_KEYS = (("cls", 0, torch.int32), ("box2d", 4, torch.float64), ("centroid", 3, torch.float64),
+                ("half_extent", 3, torch.float64), ("heading", 0, torch.float64))
+
+
+def select_boxes(raw, raw_offset, calib, objects, n_out=POINT_NUM, choice=None, seed=0, scene0=0, want_inside=False):
+    """Which labelled objects become ground truth (dataset.py:237-283): whitelisted, not degenerate, at least 5 of the
+    subsampled points inside both the 2D box's frustum and the 3D box.  raw, raw_offset, n_out, choice, seed, scene0 as for
+    subsample_augment: the points tested are the rows it picks, un-augmented, upright-depth.  calib: (Rtilt (b,3,3),
+    K (b,3,3)) or a list of (Rtilt, K) pairs.  objects: sunrgbd.pack_objects' dict (host arrays or device tensors: cls,
+    box2d, centroid, half_extent, heading; host obj_offset (b+1)).
+    -> dict: center (nkept,3), size (nkept,3), heading (nkept) float64 and cls (nkept) int32 device tensors, in label order
+    -- what augment_boxes takes; box_offset host int64 (b+1), the one read-back; n_inside, status (one per input object,
+    device int32; 0 kept, 1 not whitelisted, 2 degenerate, 3 fewer than 5 points); inside (objects, n_out) uint8 if asked."""
+    raw, off, b, ch = _check_raw(raw, raw_offset, n_out, choice, "select_boxes")
+    if np.any(np.diff(off) < n_out):
+        raise L.InvalidArgumentError("select_boxes: a scene has fewer than n_out = %d points" % n_out)
+    rt, km = _calib_arrays(calib, b, "select_boxes")
+    ooff = np.ascontiguousarray(objects["obj_offset"], dtype=np.int64)
+    if len(ooff) != b + 1 or ooff[0] != 0 or np.any(np.diff(ooff) < 0):
+        raise L.InvalidArgumentError("select_boxes: obj_offset must have b + 1 = %d non-decreasing entries from 0" % (b + 1))
+    n_obj = int(ooff[-1])
+    dev = raw.device
+    obj = {}
+    for k, w, dt in _OBJECT_KEYS:
+        t = objects[k]
+        t = (t if torch.is_tensor(t) else torch.from_numpy(np.ascontiguousarray(t))).to(device=dev, dtype=dt).contiguous()
+        if tuple(t.shape) != ((n_obj, w) if w else (n_obj,)):
+            raise L.InvalidArgumentError("select_boxes: objects[%r] has shape %s, obj_offset describes %d objects"
+                                         % (k, tuple(t.shape), n_obj))
+        obj[k] = t
+    center = torch.empty((n_obj, 3), dtype=torch.float64, device=dev)
+    size = torch.empty((n_obj, 3), dtype=torch.float64, device=dev)
+    heading = torch.empty((n_obj,), dtype=torch.float64, device=dev)
+    cls = torch.empty((n_obj,), dtype=torch.int32, device=dev)
+    kept = torch.empty((b,), dtype=torch.int32, device=dev)
+    n_inside = torch.empty((n_obj,), dtype=torch.int32, device=dev)
+    status = torch.empty((n_obj,), dtype=torch.int32, device=dev)
+    inside = torch.empty((n_obj, n_out), dtype=torch.uint8, device=dev) if want_inside else None
+    wsb = int(L.lib().votenet_select_boxes_workspace_bytes(b, n_obj))
+    ws = torch.empty((wsb,), dtype=torch.uint8, device=dev)
+    with L.device_guard(dev):
+        L.check(L.lib().votenet_select_boxes(b, n_out, L.ptr(raw), 1 if raw.dtype == torch.float64 else 0, raw.shape[1], _hp(off),
+                                             L.ptr(ch), int(seed) & (2 ** 64 - 1), int(scene0), _hp(rt), _hp(km), _hp(ooff),
+                                             *[L.ptr(obj[k]) for k, _, _ in _OBJECT_KEYS], L.ptr(center), L.ptr(size),
+                                             L.ptr(heading), L.ptr(cls), L.ptr(kept), L.ptr(n_inside), L.ptr(status),
+                                             L.ptr(inside), L.ptr(ws), wsb, L.stream_ptr()))
+    box_offset = np.zeros(b + 1, np.int64)
+    box_offset[1:] = np.cumsum(kept.cpu().numpy())
+    nk = int(box_offset[-1])
+    res = {"center": center[:nk], "size": size[:nk], "heading": heading[:nk], "cls": cls[:nk], "box_offset": box_offset,
+           "n_inside": n_inside, "status": status}
+    if want_inside:
+        res["inside"] = inside
+    return res
+
+
+def build_batch(raw, raw_offset, calib, objects, aug=None, choice=None, seed=0, scene0=0, n_out=POINT_NUM):
+    """Parsed scenes -> model inputs: select_boxes, then subsample_augment and augment_boxes with the same choice / seed for
+    the scenes that kept at least one box (the reference skips the others, dataset.py:300).  aug holds one draw per INPUT
+    scene: the reference draws before it looks at the objects (dataset.py:219-231), so a dropped scene consumes its draw.
+    -> (points (k, n_out, 3) float32, gt dict of augment_boxes, scene_index host int64 (k)); (None, None, empty) when every
+    scene is dropped."""
+    b = len(raw_offset) - 1
+    if aug is not None and aug.b != b:
+        raise L.InvalidArgumentError("build_batch: %d scenes but %d augmentation draws" % (b, aug.b))
+    sel = select_boxes(raw, raw_offset, calib, objects, n_out, choice, seed, scene0)
+    cnt = np.diff(sel["box_offset"])
+    scene_index = np.nonzero(cnt > 0)[0].astype(np.int64)
+    if len(scene_index) == 0:
+        return None, None, scene_index
+    # every input scene goes through the point kernel with its own rows and its own draw; the dropped ones are left out after
+    points = subsample_augment(raw, raw_offset, n_out, aug, choice, seed, scene0)
+    if len(scene_index) < b:
+        points = points[torch.from_numpy(scene_index).to(points.device)]
+        if aug is not None:
+            aug = Augmentation(aug.flip_x[scene_index], aug.flip_z[scene_index], aug.angle[scene_index], aug.scale[scene_index])
+    box_offset = np.concatenate([[0], np.cumsum(cnt[scene_index])]).astype(np.int64)
+    gt = augment_boxes(sel["center"], sel["size"], sel["heading"], sel["cls"], box_offset, aug)
+    return points, gt, scene_index
