@@ -737,6 +737,29 @@ int votenet_select_boxes(int b, int n_out, const void *raw, int raw_f64, int raw
  * (b,m,8,3) of the same scene -> iou (b,n,m): the detections-vs-ground-truth overlaps of evaluator.py:26-39,122-132. */
 int votenet_iou3d_cross(int b, int n, int m, const float *boxes_a, const float *boxes_b, float *iou, void *stream);
 
+/* One batch's share of the detection evaluation, evaluator.py:76-161,224-226: every kept row becomes one record that already
+ * holds whether it is a true positive at each IoU threshold.  One launch on `stream`, nothing is read back.
+ *   bboxes (b,n,8,3), class_scores (b,n,nc): the predict tower's boxes and class logits; rows (nrows,2) int32 [scene, box]: the
+ *   kept rows, in any order; nrows_dev: NULL, or a device int holding how many of the nrows rows are valid (what votenet_nms3d
+ *   leaves in *out_count).  gt_boxes (b,g,8,3), gt_labels (b,g), gt_count (b): ground truth, rows beyond gt_count[s] are padding.
+ *   thresholds: nthr <= 8 floats on the HOST.  scene0: the running number of the batch's first scene; arrival0: the running
+ *   number of its first row (the caller adds nrows after every call).
+ * A kept row is one detection of its first arg-max class c with that maximum as score (:224-226).  Its overlap with every
+ * valid ground-truth box of class c in its scene is the IoU of votenet_iou3d_cross, bit for bit; ovmax / jmax by the
+ * reference's strict '>' scan (first maximum); no ground truth of the class, or a NaN overlap -> false positive.  It is a true
+ * positive at threshold t iff ovmax > t and no detection of its scene with the same jmax and ovmax > t comes before it, by score
+ * descending, then row index ascending: the greedy matching of :128-147 in closed form (a NaN score ranks as -inf).
+ *   records: capacity records of 16 bytes {f32 score, u32 class | tp_mask << 8, i32 scene0 + scene, u32 arrival0 + row}, bit t of
+ *   tp_mask = true positive at thresholds[t].  The rows of a scene are appended at *rec_count (device int, which counts every
+ *   record offered); a record that does not fit is dropped and bit 0 of *flags is set -- nothing is written beyond capacity.
+ *   Bit 1 of *flags: a row naming a scene or box outside the batch was skipped; bit 2: a scene had more than 1024 kept rows.
+ *   npos (nc) device ints: += the valid ground-truth boxes per class.  The caller zeroes rec_count, npos and flags once.
+ * n >= 1, g <= 4096, nc <= 256. */
+int votenet_eval_match(int b, int n, int g, int nc, const float *bboxes, const int *rows, int nrows, const int *nrows_dev,
+                       const float *class_scores, const float *gt_boxes, const int *gt_labels, const int *gt_count, int nthr,
+                       const float *thresholds, long scene0, unsigned arrival0, void *records, int capacity, int *rec_count,
+                       int *npos, int *flags, void *stream);
+
 /* Plumbing between the path's kernels in one launch: concat (utils.py:286, model.py:53), slices of an input gradient, zero
  * padding of a ragged layer, residual sums (votes = x + offset, model.py:57-61; gradients from two consumers) of row-major
  * (rows x width) tensors.  For every segment s < nseg <= 8:

@@ -1,5 +1,7 @@
 """End-to-end check on synthetic rooms (GPU box only): train the hot path with the reference's loss, then run the predict
-tower (decode -> 3D NMS) on held-out scenes and report mAP@0.25 / @0.5 with the reference's evaluator logic.
+tower (decode -> 3D NMS) on held-out scenes and report mAP@0.25 / @0.5 with the reference's evaluator logic: "mAP" is the mean
+of the per-batch mAPs (the figure of every earlier log), "set mAP" the reference's own metric, detections ranked over the whole
+validation set (evaluator.evaluate).
     python tools/train_eval.py [steps] [train_batches] [--save PATH] [--resume PATH]
 --save PATH: a checkpoint (VoteNetHotPath.save) at every evaluation and at the end.  --resume PATH: continue the run a checkpoint
 holds -- parameters, moving averages, Adam state and step count -- up to `steps` steps in all, on the batches it would have seen."""
@@ -50,8 +52,14 @@ def save():
         print("step %d: saved %s" % (net._step, args.save))
 
 
+def report(step):
+    """The line of every earlier log (mean of the per-batch mAPs), and beside it the reference's metric: mAP over the whole set."""
+    res = E.evaluate(net, val_x, val_gt, (0.25, 0.5))
+    print("step %d: mAP" % step, evaluate(), " set mAP", {thr: res[thr]["mAP"] for thr in (0.25, 0.5)})
+
+
 t0 = time.time()
-print("step %d: mAP" % start, evaluate())
+report(start)
 for i in range(start, steps):
     net.train_step(xs[i % nb], gt=gts[i % nb], next_x=xs[(i + 1) % nb])  # geometry of the next batch under this step
     if (i + 1) % 100 == 0:
@@ -59,7 +67,7 @@ for i in range(start, steps):
         print("step %d  cost %.3f  vote %.3f obj %.3f box %.3f sem %.3f  pos %d  (%.1f s)" % (i + 1, l[0], l[1], l[2], l[9], l[8], int(l[10]),
                                                                                               time.time() - t0))
     if (i + 1) % 300 == 0:
-        print("step %d: mAP" % (i + 1), evaluate())
+        report(i + 1)
         save()
 if steps % 300 or steps <= start:  # (a run that ends on an evaluation has just saved)
     save()

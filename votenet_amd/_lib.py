@@ -102,6 +102,8 @@ _SIGS.update({
     "votenet_loss_pitched": [ctypes.c_int] * 7 + [_c_f] * 4 + [ctypes.c_long] + [_c_f] * 8 + [ctypes.c_float] * 2 + [_c_f] * 5 + [ctypes.c_void_p],
     "votenet_decode_boxes": [ctypes.c_int] * 5 + [_c_f] * 5 + [ctypes.c_void_p],
     "votenet_iou3d_cross": [ctypes.c_int] * 3 + [_c_f] * 3 + [ctypes.c_void_p],
+    "votenet_eval_match": [ctypes.c_int] * 4 + [_c_f] * 2 + [ctypes.c_int] + [_c_f] * 5 + [ctypes.c_int, ctypes.POINTER(ctypes.c_float),
+                           ctypes.c_long, ctypes.c_uint, _c_f, ctypes.c_int] + [_c_f] * 3 + [ctypes.c_void_p],
     "votenet_selection_sort": [ctypes.c_int] * 4 + [_c_f] * 3 + [ctypes.c_void_p],
     "votenet_knn_point": [ctypes.c_int] * 5 + [_c_f] * 5 + [ctypes.c_void_p],
     "votenet_prob_sample": [ctypes.c_int] * 3 + [_c_f] * 4 + [ctypes.c_void_p],

@@ -12,7 +12,7 @@ pids=()
 for src in "$HERE"/*.hip; do
   obj="$HERE/obj/$(basename "${src%.hip}").o"
   # (this script carries the flags: an object older than it is stale too)
-  if [ ! -f "$obj" ] || [ "$src" -nt "$obj" ] || [ "$HERE/common.h" -nt "$obj" ] || [ "$HERE/mlp_types.h" -nt "$obj" ] \
+  if [ ! -f "$obj" ] || [ "$src" -nt "$obj" ] || [ "$HERE/common.h" -nt "$obj" ] || [ "$HERE/mlp_types.h" -nt "$obj" ] || [ "$HERE/iou3d.h" -nt "$obj" ] \
      || [ "$HERE/../../include/votenet_hip.h" -nt "$obj" ] || [ "$HERE/../../include/votenet_hip_debug.h" -nt "$obj" ] \
      || [ "${BASH_SOURCE[0]}" -nt "$obj" ]; then
     extra=""

@@ -1,10 +1,17 @@
 """Detection evaluation (evaluator.py:26-200 of the reference): VOC average precision per class at a 3D-IoU threshold.
 The box overlaps -- the reference's shapely polygon loop over every (detection, ground-truth) pair -- come from the device
 (votenet_iou3d_cross, the IoU kernel of the NMS); matching and the precision / recall curve are the reference's host logic
-restated with numpy (they are O(detections))."""
+restated with numpy (they are O(detections)).
+
+eval_det scores ONE batch.  DetectionAccumulator / evaluate score a whole validation set, as evaluator.py:217-233 collects every
+scene before eval_det_cls ranks by confidence: each batch is matched on the device (votenet_eval_match, csrc/eval_match.hip) into
+one 16-byte record per kept box, nothing is read back until result()."""
+import ctypes
+
 import numpy as np
 import torch
 
+from . import _lib as L
 from . import tf_nms3d
 from .synth import MEAN_SIZES, NC
 
@@ -108,3 +115,135 @@ def gt_for_eval(gt_np, counts=None):
             counts.append(n)
     return dict(boxes=box_corners(gt_np["bboxes_xyz"], gt_np["bboxes_lwh"], gt_np["bboxes_roty"]), labels=gt_np["semantic_labels"],
                 count=np.asarray(counts))
+
+
+def gt_to_device(gt, device):
+    """gt_for_eval's dict (numpy or device tensors) -> the same dict as contiguous device tensors (boxes f32, labels / count int32):
+    what DetectionAccumulator.add uses in place, so a validation set is uploaded once."""
+    def conv(v, dtype):
+        if not isinstance(v, torch.Tensor):
+            v = torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32 if dtype == torch.float32 else np.int32))
+        return v.to(device=device, dtype=dtype).contiguous()
+    return dict(boxes=conv(gt["boxes"], torch.float32), labels=conv(gt["labels"], torch.int32), count=conv(gt["count"], torch.int32))
+
+
+def finalize_records(records, npos, thresholds, use_07_metric=False):
+    """The host half of the streaming evaluation: records (K,4) int32 as votenet_eval_match writes them {score bits, class |
+    tp_mask << 8, scene, arrival}, npos (NC,) ground-truth boxes per class over the whole set -> {threshold: dict(ap, mAP, rec,
+    prec, npos)}.  Per class: sort by (-score, arrival) -- eval_det_cls's stable argsort of detections listed in arrival order --
+    cumulative sums, voc_ap.  Classes without ground truth are left out, as eval_det leaves them out for a batch."""
+    records = np.ascontiguousarray(records, dtype=np.int32).reshape(-1, 4)
+    score = records[:, 0].copy().view(np.float32).astype(np.float64)
+    cls, mask = records[:, 1] & 0xff, (records[:, 1] >> 8) & 0xff
+    arrival = records[:, 3].copy().view(np.uint32)
+    order = np.lexsort((arrival, -score))
+    cls_sorted, mask_sorted = cls[order], mask[order]
+    out = {}
+    for t, thr in enumerate(thresholds):
+        res = dict(ap={}, rec={}, prec={}, npos={})
+        for c in range(len(npos)):
+            if npos[c] <= 0:
+                continue
+            tp = ((mask_sorted[cls_sorted == c] >> t) & 1).astype(np.float64)
+            fp = 1.0 - tp
+            fp, tp = np.cumsum(fp), np.cumsum(tp)
+            rec = tp / float(npos[c])
+            prec = tp / np.maximum(tp + fp, np.finfo(np.float64).eps)
+            res["rec"][c], res["prec"][c], res["npos"][c] = rec, prec, int(npos[c])
+            res["ap"][c] = voc_ap(rec, prec, use_07_metric)
+        res["mAP"] = float(np.mean(list(res["ap"].values()))) if res["ap"] else float("nan")
+        out[thr] = res
+    return out
+
+
+class DetectionAccumulator:
+    """Detection evaluation over any number of batches (evaluator.py:164-233).
+        acc = DetectionAccumulator(device, thresholds=(0.25, 0.5), capacity=...)
+        acc.add(pred, gt)      # enqueues one kernel; no host synchronisation
+        res = acc.result()     # the one synchronisation: res[0.25] -> dict(ap, mAP, rec, prec, npos)
+    capacity: the most detections (kept boxes) the whole set can offer; result() raises if more arrived.  records: an int32
+    (rows >= capacity, 4) device tensor to use as the record buffer instead of allocating one.  Thresholds are compared in
+    float32, as numpy compares a float32 overlap with a Python float.  Equal scores rank in arrival order (add call, then row)."""
+    FLAG_OVERFLOW, FLAG_BAD_ROW, FLAG_SCENE = 1, 2, 4
+
+    def __init__(self, device, thresholds=(0.25, 0.5), capacity=1 << 21, records=None):
+        self.device = torch.device(device)
+        self.thresholds = tuple(float(t) for t in thresholds)
+        if not 1 <= len(self.thresholds) <= 8:
+            raise L.InvalidArgumentError("DetectionAccumulator: 1 to 8 IoU thresholds, got %d" % len(self.thresholds))
+        self.capacity = int(capacity)
+        if self.capacity < 0:
+            raise L.InvalidArgumentError("DetectionAccumulator: negative capacity")
+        if records is None:
+            records = torch.empty((max(self.capacity, 1), 4), dtype=torch.int32, device=self.device)
+        records = L.dev_i32(records, "DetectionAccumulator records", 2)
+        if records.shape[1] != 4 or records.shape[0] < self.capacity:
+            raise L.InvalidArgumentError("DetectionAccumulator: records must be (>= capacity, 4) int32, got %s" % (tuple(records.shape),))
+        self._records = records
+        self._thr = (ctypes.c_float * len(self.thresholds))(*self.thresholds)
+        self._state = torch.zeros(2 + NC, dtype=torch.int32, device=self.device)  # [records offered, flags, npos[NC]]
+        self._scene = self._arrival = 0
+
+    def reset(self):
+        self._state.zero_()
+        self._scene = self._arrival = 0
+
+    def add(self, pred, gt):
+        """pred: what VoteNetHotPath.predict returns (sync=True: nms_idx (K,2); sync=False: padded nms_idx + nms_count on the
+        device).  gt: gt_for_eval's dict, numpy (uploaded here) or device tensors (gt_to_device: used in place)."""
+        boxes = L.dev_f32(pred["bboxes"].detach(), "DetectionAccumulator.add: bboxes (B,N,8,3)", 4, 3)
+        b, n = boxes.shape[:2]
+        if boxes.shape[2] != 8:
+            raise L.InvalidArgumentError("DetectionAccumulator.add expects (B, N, 8, 3) boxes")
+        cls = L.dev_f32(pred["class_scores"].detach(), "DetectionAccumulator.add: class_scores (B,N,NC)", 3, NC)
+        if tuple(cls.shape[:2]) != (b, n):
+            raise L.InvalidArgumentError("DetectionAccumulator.add: class_scores %s do not match boxes %s" % (tuple(cls.shape), tuple(boxes.shape)))
+        rows = L.dev_i32(pred["nms_idx"], "DetectionAccumulator.add: nms_idx (K,2)", 2)
+        if rows.shape[1] != 2:
+            raise L.InvalidArgumentError("DetectionAccumulator.add: nms_idx must be (K, 2)")
+        count = pred.get("nms_count")
+        if count is not None:
+            count = L.dev_i32(count, "DetectionAccumulator.add: nms_count")
+        g = gt_to_device(gt, self.device)
+        if g["boxes"].dim() != 4 or tuple(g["boxes"].shape[2:]) != (8, 3) or g["boxes"].shape[0] != b:
+            raise L.InvalidArgumentError("DetectionAccumulator.add expects (B, G, 8, 3) ground-truth boxes, got %s" % (tuple(g["boxes"].shape),))
+        ng = g["boxes"].shape[1]
+        if tuple(g["labels"].shape) != (b, ng) or tuple(g["count"].shape) != (b,):
+            raise L.InvalidArgumentError("DetectionAccumulator.add: labels must be (B, G) and count (B,)")
+        k = rows.shape[0]
+        if self._arrival + k > 0xffffffff:
+            raise L.VotenetError("DetectionAccumulator: more than 2^32 kept rows offered")
+        st = self._state
+        with L.device_guard(self.device):
+            L.check(L.lib().votenet_eval_match(b, n, ng, NC, L.ptr(boxes), L.ptr(rows) if k else None, k, L.ptr(count), L.ptr(cls),
+                                               L.ptr(g["boxes"]), L.ptr(g["labels"]), L.ptr(g["count"]), len(self.thresholds), self._thr,
+                                               self._scene, self._arrival, L.ptr(self._records), self.capacity, st.data_ptr(),
+                                               st.data_ptr() + 8, st.data_ptr() + 4, L.stream_ptr()))
+        self._scene += b
+        self._arrival += k
+
+    def result(self, use_07_metric=False):
+        state = self._state.cpu().numpy()
+        offered, flags, npos = int(state[0]), int(state[1]), state[2:]
+        if flags & self.FLAG_OVERFLOW or offered > self.capacity:
+            raise L.VotenetError("DetectionAccumulator: capacity %d, %d detections offered" % (self.capacity, offered))
+        if flags & self.FLAG_BAD_ROW:
+            raise L.InvalidArgumentError("DetectionAccumulator: a kept row names a scene or a box outside its batch")
+        if flags & self.FLAG_SCENE:
+            raise L.InvalidArgumentError("DetectionAccumulator: more than 1024 kept rows in one scene")
+        return finalize_records(self._records[:offered].cpu().numpy(), npos, self.thresholds, use_07_metric)
+
+
+def evaluate(net, batches, gts, thresholds=(0.25, 0.5), iou_threshold=0.25):
+    """mAP of `net` over a validation set: batches[i] (B,n,3) device clouds, gts[i] gt_for_eval's dict (numpy or device).  Every
+    predict call is asynchronous with the next batch's geometry underneath it; one synchronisation at the end.
+    -> {threshold: dict(ap, mAP, rec, prec, npos)}."""
+    acc = None
+    for i, (x, g) in enumerate(zip(batches, gts)):
+        pred = net.predict(x, iou_threshold, next_x=batches[i + 1] if i + 1 < len(batches) else None, sync=False)
+        if acc is None:  # every proposal of every scene kept: the most the set can offer
+            acc = DetectionAccumulator(x.device, thresholds, capacity=sum(int(v.shape[0]) for v in batches) * int(pred["bboxes"].shape[1]))
+        acc.add(pred, g)
+    if acc is None:
+        raise L.InvalidArgumentError("evaluate: no batches")
+    return acc.result()
