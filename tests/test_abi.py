@@ -218,3 +218,132 @@ def test_library_has_no_packed_f32_op_reading_the_high_register_of_src1(hiplib):
     assert mod.BAD.search("v_pk_fma_f32 v[18:19], v[56:57], v[52:53], v[18:19] op_sel:[0,1,0]")
     assert not mod.BAD.search("v_pk_fma_f32 v[18:19], v[52:53], v[56:57], v[18:19] op_sel:[1,0,0]")
     assert not mod.BAD.search("v_pk_fma_f32 v[18:19], v[36:37], v[52:53], v[18:19] op_sel_hi:[1,0,1]")
+
+
+# ---- the Python prototypes are read from the two headers (votenet_amd/_lib.py: parse_header) ----
+
+def _declared_arity(headers):
+    """{function: number of parameters}, counted in the header text itself (not by the reader under test)."""
+    out = {}
+    for h in headers:
+        text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", h)).read(), flags=re.S)
+        for name, params in re.findall(r"\b(votenet_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", text):
+            out[name] = 0 if params.strip() == "void" else params.count(",") + 1
+    return out
+
+
+def test_every_declared_function_has_its_prototype(hiplib):
+    arity = _declared_arity(("votenet_hip.h",))
+    assert sorted(arity) == declared_symbols(("votenet_hip.h",)) and len(arity) == 131
+    for name, n in arity.items():
+        fn = hiplib.__dict__[name]  # bound when the library was loaded, not by this lookup
+        assert fn.argtypes is not None and len(fn.argtypes) == n, name
+    debug = _declared_arity(("votenet_hip_debug.h",))
+    assert sorted(debug) == sorted(set(declared_symbols()) - set(arity)) and len(debug) == 30
+    for name, n in debug.items():
+        fn = getattr(hiplib, name)
+        assert fn.argtypes is not None and len(fn.argtypes) == n, name
+        assert fn.restype is (ctypes.c_int if name == "votenet_debug_enabled" else
+                              ctypes.c_uint if name == "votenet_debug_fps_split_timeouts" else None), name
+
+
+def test_spot_prototypes(hiplib):
+    """Hand-read from the headers; together they cover the whole type mapping."""
+    from votenet_amd import _lib
+    I, L, F, V, Z = ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t
+    want = {
+        "votenet_farthest_point_sample": (I, [I, I, I, V, V, V, V]),
+        "votenet_query_ball_point": (I, [I, I, I, F, I, V, V, V, V, V]),
+        "votenet_nms3d": (I, [I, I, V, V, V, F, V, V, V, Z, V]),
+        "votenet_select_boxes": (I, [I, I, V, I, I, V, V, ctypes.c_ulonglong, L, V, V, V, V, V, V, V, V, V, V, V, V, V, V, V, V, V, Z, V]),
+        "votenet_mlp_linear": (I, [ctypes.POINTER(_lib.MlpInput), L, I, I, V, V, V, V, V]),
+        "votenet_bn_relu": (I, [L, I, V, V, V, ctypes.POINTER(_lib.BnRaw), I, V, V]),
+        "votenet_copy_segments": (I, [I, ctypes.POINTER(_lib.CopySegment), V]),
+        "votenet_eval_match": (I, [I, I, I, I, V, V, I, V, V, V, V, V, I, V, L, ctypes.c_uint, V, I, V, V, V, V]),
+        "votenet_clip_adam": (I, [I, V, V, V, V, V, V, F, F, F, F, I, F, F, V]),
+        "votenet_mlp_split_k_floats": (L, [L, I, I]),
+        "votenet_fps_temp_floats": (Z, [I, I]),
+        "votenet_last_error": (ctypes.c_char_p, []),
+        "votenet_half_piece_rows": (I, []),
+        "votenet_ball_threshold": (F, [F]),
+        "votenet_debug_fps_split_timeouts": (ctypes.c_uint, []),
+        "votenet_debug_fast_bf3": (None, [I]),
+        "votenet_debug_split_k": (None, [I, I, I, I]),
+    }
+    for name, (restype, argtypes) in want.items():
+        fn = getattr(hiplib, name)
+        assert fn.restype is restype, name
+        assert len(fn.argtypes) == len(argtypes) and all(a is b for a, b in zip(fn.argtypes, argtypes)), (name, fn.argtypes)
+    assert _lib.MlpInput._fields_[4] == ("in_bn", ctypes.POINTER(_lib.BnRaw))
+    assert _lib.CoefTail._fields_[:2] == [("ticket", V), ("rows", L)] and _lib.BnRaw._fields_[4] == ("eps", F)
+
+
+STRUCT_FIELDS = {  # hand-read from include/votenet_hip.h: Python class, C struct, fields in order
+    "BnRaw": ("votenet_bn_raw", "stats gamma beta rows eps out"),
+    "CoefTail": ("votenet_coef_tail", "ticket rows gamma coef dgamma dbeta"),
+    "MlpInput": ("votenet_mlp_input", "x in_scale in_shift in_relu in_bn xyz new_xyz feat idx b n m nsample c"),
+    "RowSegment": ("votenet_row_segment", "dst dst_pitch dst_off width a a_pitch a_off b b_pitch b_off"),
+    "CopySegment": ("votenet_copy_segment", "dst src bytes"),
+}
+
+
+def test_struct_layout_is_the_compilers(tmp_path):
+    """sizeof and every offsetof as g++ lays the header's structs out == what ctypes lays out for the classes read from the header."""
+    from votenet_amd import _lib
+    lines = ["#include <cstdio>", "#include <cstddef>", '#include "votenet_hip.h"', "int main() {"]
+    for cname, fields in STRUCT_FIELDS.values():
+        lines.append('    printf("%s sizeof %%zu\\n", sizeof(%s));' % (cname, cname))
+        lines += ['    printf("%s %s %%zu\\n", offsetof(%s, %s));' % (cname, f, cname, f) for f in fields.split()]
+    src = tmp_path / "layout.cpp"
+    src.write_text("\n".join(lines + ["    return 0;", "}", ""]))
+    r = subprocess.run(["g++", "-I" + os.path.join(ROOT, "include"), str(src), "-o", str(tmp_path / "layout")], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    out = subprocess.run([str(tmp_path / "layout")], capture_output=True, text=True, check=True).stdout
+    theirs = {tuple(l.split()[:2]): int(l.split()[2]) for l in out.splitlines()}
+    ours = {}
+    for pyname, (cname, fields) in STRUCT_FIELDS.items():
+        cls = getattr(_lib, pyname)
+        assert [f for f, _ in cls._fields_] == fields.split()
+        ours[(cname, "sizeof")] = ctypes.sizeof(cls)
+        ours.update({(cname, f): getattr(cls, f).offset for f in fields.split()})
+    assert ours == theirs and len(ours) == 5 + 39
+
+
+def test_header_reader_has_teeth():
+    from votenet_amd._lib import parse_header
+    for bad in ("int votenet_x(short a);", "short votenet_x(int a);", "int votenet_x(float **a);", "int votenet_x(int);",
+                "int votenet_x(const votenet_nope *p);", "const char *votenet_y(void);\nint votenet_x(const char *s, wchar_t c);"):
+        with pytest.raises(ValueError, match="votenet_x"):
+            parse_header(bad, {})
+    with pytest.raises(ValueError, match="votenet_s.a"):
+        parse_header("typedef struct votenet_s { int n; short a; } votenet_s;", {})
+    with pytest.raises(ValueError, match="votenet_x"):  # a definition, a macro call: anything that is not a declaration
+        parse_header("int votenet_x(int a) { return a; }", {})
+    structs = {}
+    funcs = parse_header("""
+        /* a comment with a declaration inside: int votenet_not(int a); */
+        #ifdef __cplusplus
+        extern "C" {
+        #endif
+        #define VOTENET_SOMETHING 3 /* (void) */
+        typedef struct votenet_pair {
+            const float *gamma, *beta; /* c each */
+            int b, n,
+                m;
+            unsigned *ticket;
+        } votenet_pair;
+        int votenet_many(int b, const votenet_pair *p /* may be NULL */,
+                         unsigned long long seed, unsigned arrival0,
+                         double *sums /* 2*c, pre-zeroed */, size_t bytes, void *stream);
+        size_t votenet_bytes(void);
+        void votenet_set(int on); // trailing
+        #ifdef __cplusplus
+        }
+        #endif
+        """, structs)
+    I, V = ctypes.c_int, ctypes.c_void_p
+    pair = structs["votenet_pair"]
+    assert issubclass(pair, ctypes.Structure) and pair.__name__ == "Pair"
+    assert pair._fields_ == [("gamma", V), ("beta", V), ("b", I), ("n", I), ("m", I), ("ticket", V)]
+    assert funcs == {"votenet_many": (I, [I, ctypes.POINTER(pair), ctypes.c_ulonglong, ctypes.c_uint, V, ctypes.c_size_t, V]),
+                     "votenet_bytes": (ctypes.c_size_t, []), "votenet_set": (None, [I])}

@@ -65,7 +65,6 @@ def test_fps_two_samples_per_round_experiment_is_the_same_sequence(ops, dev, O, 
     """fps_bucket2_kernel (votenet_fps_debug_two_pick): up to two picks per round when the runner-up is provably the next
     arg-max.  Off by default (slower, DESIGN_HISTORY.md 4.1); the indices must be the oracle's, duplicates and exact ties included."""
     from votenet_amd import synth
-    hiplib.votenet_fps_debug_two_pick.restype = None
     hiplib.votenet_fps_debug_two_pick(1)
     try:
         rng = np.random.default_rng(11)
@@ -84,7 +83,6 @@ def test_fps_of_an_fps_ordered_subset_short_cut_is_exact(ops, dev, O, hiplib):
     exact tie that the subset's tie key resolves differently, lets the sampling rounds run).  Against the oracle on the
     gathered subset, with the check on and off; lattice clouds provoke the ties."""
     from votenet_amd import synth
-    hiplib.votenet_fps_debug_prefix_check.restype = None
     rng = np.random.default_rng(3)
     clouds = [synth.room_batch(2, 20480, 5), rng.random((2, 6000, 3), dtype=np.float32) * 4,
               np.round(rng.random((2, 5000, 3), dtype=np.float32) * 8) / 2,    # lattice: exact ties and duplicates
@@ -249,9 +247,7 @@ def test_fps_scene_over_four_workgroups_gives_the_same_indices(ops, dev, hiplib,
     registers of four workgroups that agree on every round's winner through L2 -- the indices of tf_sampling_g.cu:105-170 exactly as
     the default kernel gives them (that one is pinned to the oracle and to the reference's kernel above), more scenes than XCDs,
     ragged sizes, both ends of the kernel's range; no poll may have given up."""
-    import ctypes
     from votenet_amd import synth
-    hiplib.votenet_debug_fps_split_timeouts.restype = ctypes.c_uint
     x = T(synth.room_batch(b, n, 5 + n % 7), dev)
     ref = ops.s.farthest_point_sample(m, x)
     hiplib.votenet_debug_fps_split(mode)  # 1: 4 workgroups x 12 waves per scene, 3: 12 x 4, 5: 6 x 8
@@ -352,7 +348,6 @@ def test_ball_query_small_cloud_forms_agree(ops, dev, hiplib, n):
     xyz1 = T(rng.random((3, n, 3), dtype=np.float32), dev)
     xyz2 = T(rng.random((3, 130, 3), dtype=np.float32), dev)
     hook = hiplib.votenet_debug_ball_query_small
-    hook.restype = None
     got = []
     try:
         for form in (0, 4, 16):

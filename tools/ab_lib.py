@@ -6,7 +6,6 @@ _s = _iu.spec_from_file_location("hp", os.path.join(R, "votenet_amd", "hostpin.p
 import torch
 from votenet_amd import loss as VL, model as VM, synth, _lib as L
 hook = getattr(L.lib(), sys.argv[1])
-hook.restype = None
 vals = [int(v) for v in sys.argv[2:]]
 dev = torch.device("cuda:0")
 B, n = 8, 20480

@@ -207,13 +207,10 @@ def ball_query_pairs(idx, cnt, n, chunk=4096, wg_queries=64):
 def indexed_pairs(index, xyz2, n, radius):
     """(query, candidate) pairs ball_query_indexed_kernel tests: 64 per bucket whose box passes the kernel's conservative
     test, recomputed here from the index's boxes with the same fp32 expression."""
-    import ctypes
     import torch
     from votenet_amd import _lib as L
     b, m, _ = xyz2.shape
     nb = (n + 63) // 64
-    L.lib().votenet_ball_threshold.restype = ctypes.c_float
-    L.lib().votenet_ball_threshold.argtypes = [ctypes.c_float]
     thr = float(L.lib().votenet_ball_threshold(float(radius)))
     box = index[b * n:b * n + b * nb * 6].view(b, 1, nb, 6)
     q = xyz2.view(b, m, 1, 3)

@@ -7,7 +7,6 @@ from votenet_amd import _lib as L, synth, tf_grouping as G, tf_sampling as S
 dev = torch.device("cuda:0")
 x = torch.from_numpy(synth.room_batch(8, 20480, 1000)).to(dev)
 hook = L.lib().votenet_debug_ball_query_small
-hook.restype = None
 def timeit(f, n=50):
     for _ in range(5): f()
     torch.cuda.synchronize(); t0 = time.perf_counter()

@@ -8,18 +8,14 @@ import ctypes, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 import torch
-from votenet_amd import synth
+from votenet_amd import _lib, synth
 dev = torch.device("cuda:0")
 b, n, m = 8, 20480, 2048
 CLK = 2.4e9
 
 
 def load(name):
-    L = ctypes.CDLL(os.path.join(ROOT, "tools", "probe", "lib", name))
-    L.votenet_fps_temp_floats.restype = ctypes.c_size_t
-    L.votenet_fps_temp_floats.argtypes = [ctypes.c_int, ctypes.c_int]
-    L.votenet_farthest_point_sample.argtypes = [ctypes.c_int] * 3 + [ctypes.c_void_p] * 4
-    return L
+    return _lib._Library(os.path.join(ROOT, "tools", "probe", "lib", name))  # the headers' prototypes, also for a probe build
 
 
 def time_ms(L, x, it=10):

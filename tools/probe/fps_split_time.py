@@ -7,7 +7,6 @@ import torch
 from votenet_amd import _lib as L_, synth, tf_sampling
 dev = torch.device("cuda:0")
 lib = L_.lib()
-lib.votenet_debug_fps_split_timeouts.restype = __import__("ctypes").c_uint
 def timeit(fn, it=6, warm=2):
     for _ in range(warm): fn()
     torch.cuda.synchronize()

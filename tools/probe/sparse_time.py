@@ -10,7 +10,6 @@ tape = []
 net.forward(x, tape)
 torch.cuda.synchronize()
 hook = L.lib().votenet_debug_sparse_workgroups
-hook.restype = None
 def timeit(f, n=20):
     for _ in range(3): f()
     torch.cuda.synchronize(); t0 = time.perf_counter()

@@ -6,6 +6,7 @@ is missing or a call fails, an exception is raised.
 """
 import ctypes
 import os
+import re
 import subprocess
 
 import torch
@@ -40,205 +41,107 @@ def build(force=False):
     return _LIB_PATH
 
 
-_c_f = ctypes.c_void_p  # all device pointers cross the ABI as void*
-_SIGS = {
-    "votenet_farthest_point_sample": [ctypes.c_int] * 3 + [_c_f] * 3 + [ctypes.c_void_p],
-    "votenet_gather_point": [ctypes.c_int] * 3 + [_c_f] * 3 + [ctypes.c_void_p],
-    "votenet_gather_point_grad": [ctypes.c_int] * 3 + [_c_f] * 3 + [ctypes.c_void_p],
-    "votenet_query_ball_point": [ctypes.c_int] * 3 + [ctypes.c_float, ctypes.c_int] + [_c_f] * 4 + [ctypes.c_void_p],
-    "votenet_query_ball_point_indexed": [ctypes.c_int] * 3 + [ctypes.c_float, ctypes.c_int] + [_c_f] * 5 + [ctypes.c_void_p],
-    "votenet_spatial_index": [ctypes.c_int] * 2 + [_c_f] * 2 + [ctypes.c_void_p],
-    "votenet_group_point": [ctypes.c_int] * 5 + [_c_f] * 3 + [ctypes.c_void_p],
-    "votenet_group_point_grad": [ctypes.c_int] * 5 + [_c_f] * 3 + [ctypes.c_void_p],
-    "votenet_three_nn": [ctypes.c_int] * 3 + [_c_f] * 4 + [ctypes.c_void_p],
-    "votenet_three_nn_weights": [ctypes.c_int] * 2 + [_c_f] * 2 + [ctypes.c_void_p],
-    "votenet_three_interpolate": [ctypes.c_int] * 4 + [_c_f] * 4 + [ctypes.c_void_p],
-    "votenet_three_interpolate_grad": [ctypes.c_int] * 4 + [_c_f] * 4 + [ctypes.c_void_p],
-    "votenet_iou3d_matrix": [ctypes.c_int] * 2 + [_c_f] * 2 + [ctypes.c_void_p],
-    "votenet_nms3d": [ctypes.c_int] * 2 + [_c_f] * 3 + [ctypes.c_float] + [_c_f] * 3 + [ctypes.c_size_t, ctypes.c_void_p],
-}
+# The C subset of include/votenet_hip.h and votenet_hip_debug.h -> ctypes.  The headers are the one statement of the ABI (every .hip
+# file is compiled against them); nothing below restates a prototype.
+_SCALARS = {"int": ctypes.c_int, "long": ctypes.c_long, "float": ctypes.c_float, "double": ctypes.c_double, "unsigned": ctypes.c_uint,
+            "unsigned long long": ctypes.c_ulonglong, "size_t": ctypes.c_size_t}
+_POINTEES = set(_SCALARS) | {"void", "char", "unsigned char", "unsigned short", "long long"}  # all cross the ABI as void*
 
 
-class BnRaw(ctypes.Structure):
-    """struct votenet_bn_raw (include/votenet_hip.h)."""
-    _fields_ = [("stats", ctypes.c_void_p), ("gamma", ctypes.c_void_p), ("beta", ctypes.c_void_p), ("rows", ctypes.c_long),
-                ("eps", ctypes.c_float), ("out", ctypes.c_void_p)]
+def _declarator(text, where):
+    """'const float *gamma' -> ('float', 1, 'gamma'): type, pointer depth, name"""
+    words = text.replace("*", " * ").split()
+    if not words or not words[-1].isidentifier():
+        raise ValueError("%s: cannot read the declaration '%s'" % (where, " ".join(text.split())))
+    return " ".join(w for w in words[:-1] if w != "const" and w != "*"), words.count("*"), words[-1]
 
 
-class CoefTail(ctypes.Structure):
-    """struct votenet_coef_tail (include/votenet_hip.h)."""
-    _fields_ = [("ticket", ctypes.c_void_p), ("rows", ctypes.c_long), ("gamma", ctypes.c_void_p), ("coef", ctypes.c_void_p),
-                ("dgamma", ctypes.c_void_p), ("dbeta", ctypes.c_void_p)]
+def _ctype(base, stars, structs, where, ret=False):
+    if stars == 0 and base in _SCALARS:
+        return _SCALARS[base]
+    if stars == 0 and ret and base == "void":
+        return None
+    if stars == 1 and base in structs:
+        return ctypes.POINTER(structs[base])
+    if stars == 1 and ret and base == "char":
+        return ctypes.c_char_p
+    if stars == 1 and base in _POINTEES:
+        return ctypes.c_void_p  # device pointers, host arrays and the stream alike: callers pass plain ints
+    raise ValueError("%s: no ctypes type for the C type '%s'" % (where, base + " *" * stars))
 
 
-class MlpInput(ctypes.Structure):
-    """struct votenet_mlp_input (include/votenet_hip.h)."""
-    _fields_ = [("x", ctypes.c_void_p), ("in_scale", ctypes.c_void_p), ("in_shift", ctypes.c_void_p),
-                ("in_relu", ctypes.c_int), ("in_bn", ctypes.POINTER(BnRaw)),
-                ("xyz", ctypes.c_void_p), ("new_xyz", ctypes.c_void_p), ("feat", ctypes.c_void_p), ("idx", ctypes.c_void_p),
-                ("b", ctypes.c_int), ("n", ctypes.c_int), ("m", ctypes.c_int), ("nsample", ctypes.c_int), ("c", ctypes.c_int)]
+def parse_header(text, structs):
+    """{function: (restype, argtypes)} of every declaration in a header's text; every `typedef struct {...} votenet_x;` becomes a
+    ctypes.Structure in structs[votenet_x].  A declaration this cannot type raises ValueError with its name."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    text = re.sub(r"#ifdef __cplusplus.*?#endif", "", text, flags=re.S)  # extern "C" { ... }
+    text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)
+
+    def struct(m):
+        name, fields = m.group(2), []
+        for line in filter(str.strip, m.group(1).split(";")):  # 'const float *gamma, *beta': the first declarator's type holds for all
+            decls = [_declarator(d, name) for d in line.split(",")]
+            fields += [(n, _ctype(decls[0][0], stars, structs, name + "." + n)) for _, stars, n in decls]
+        structs[name] = type("".join(w.capitalize() for w in name.split("_")[1:]), (ctypes.Structure,),
+                             {"_fields_": fields, "__doc__": "struct %s of the C ABI." % name})
+        return ""
+    text = re.sub(r"typedef\s+struct\s+\w+\s*\{(.*?)\}\s*(\w+)\s*;", struct, text, flags=re.S)
+    funcs = {}
+    for stmt in text.split(";"):
+        if not stmt.strip():
+            continue
+        m = re.fullmatch(r"(.*?)\((.*)\)\s*", stmt, flags=re.S)
+        if not m:
+            raise ValueError("not a function declaration: '%s'" % " ".join(stmt.split()))
+        base, stars, name = _declarator(m.group(1), "function")
+        params = [] if m.group(2).strip() == "void" else m.group(2).split(",")
+        funcs[name] = (_ctype(base, stars, structs, name, ret=True),
+                       [_ctype(*_declarator(p, name)[:2], structs, name) for p in params])
+    return funcs
 
 
-_SIGS.update({
-    "votenet_mlp_linear": [ctypes.POINTER(MlpInput), ctypes.c_long, ctypes.c_int, ctypes.c_int] + [_c_f] * 4 + [ctypes.c_void_p],
-    "votenet_group_linear": [ctypes.c_int] * 5 + [_c_f] * 8 + [ctypes.c_void_p],
-    "votenet_group_linear_backward": [ctypes.c_int] * 5 + [_c_f] * 7 + [ctypes.c_int] + [_c_f] * 3 + [ctypes.c_void_p],
-    "votenet_mlp_linear_pool": [ctypes.POINTER(MlpInput), ctypes.c_long, ctypes.c_int, ctypes.c_int] + [_c_f] * 4 + [ctypes.c_int]
-                               + [_c_f] * 4 + [ctypes.c_void_p],
-    "votenet_bn_pool_finalize": [ctypes.c_long, ctypes.c_int] + [_c_f] * 6 + [ctypes.POINTER(BnRaw), ctypes.c_int] + [_c_f] * 3
-                                + [ctypes.c_void_p],
-    "votenet_pool_backward_supported": [ctypes.c_int] * 3,
-    "votenet_bn_backward_reduce_pool": [ctypes.c_long, ctypes.c_int] + [_c_f] * 6 + [ctypes.c_float, ctypes.c_int, _c_f,
-                                        ctypes.POINTER(CoefTail), ctypes.c_void_p],
-    "votenet_pool_dgrad_prepare": [ctypes.c_int] * 2 + [_c_f] * 5 + [ctypes.c_void_p],
-    "votenet_pool_dgrad_prepare_split": [ctypes.c_int] * 2 + [_c_f] * 5 + [ctypes.c_void_p, ctypes.c_void_p],
-    "votenet_pool_dgrad_scatter": [ctypes.c_long] + [ctypes.c_int] * 3 + [_c_f] * 4 + [ctypes.c_int] + [_c_f] * 7
-                                  + [ctypes.c_float, ctypes.c_int, _c_f, ctypes.POINTER(CoefTail), ctypes.c_void_p],
-    "votenet_mlp_gram": [ctypes.c_long, ctypes.c_int] + [_c_f] * 2 + [ctypes.c_int, _c_f, _c_f, ctypes.c_void_p],
-    "votenet_pool_wgrad_sparse": [ctypes.c_long] + [ctypes.c_int] * 3 + [_c_f] * 3 + [ctypes.c_int] + [_c_f] * 4 + [ctypes.c_int]
-                                 + [_c_f] * 3 + [ctypes.c_void_p],
-    "votenet_pool_wgrad_finish": [ctypes.c_int] * 2 + [_c_f] * 6 + [ctypes.c_void_p],
-    "votenet_loss": [ctypes.c_int] * 7 + [_c_f] * 12 + [ctypes.c_float] * 2 + [_c_f] * 5 + [ctypes.c_void_p],
-    "votenet_loss_pitched": [ctypes.c_int] * 7 + [_c_f] * 4 + [ctypes.c_long] + [_c_f] * 8 + [ctypes.c_float] * 2 + [_c_f] * 5 + [ctypes.c_void_p],
-    "votenet_decode_boxes": [ctypes.c_int] * 5 + [_c_f] * 5 + [ctypes.c_void_p],
-    "votenet_iou3d_cross": [ctypes.c_int] * 3 + [_c_f] * 3 + [ctypes.c_void_p],
-    "votenet_eval_match": [ctypes.c_int] * 4 + [_c_f] * 2 + [ctypes.c_int] + [_c_f] * 5 + [ctypes.c_int, ctypes.POINTER(ctypes.c_float),
-                           ctypes.c_long, ctypes.c_uint, _c_f, ctypes.c_int] + [_c_f] * 3 + [ctypes.c_void_p],
-    "votenet_selection_sort": [ctypes.c_int] * 4 + [_c_f] * 3 + [ctypes.c_void_p],
-    "votenet_knn_point": [ctypes.c_int] * 5 + [_c_f] * 5 + [ctypes.c_void_p],
-    "votenet_prob_sample": [ctypes.c_int] * 3 + [_c_f] * 4 + [ctypes.c_void_p],
-    "votenet_subsample_augment": [ctypes.c_int, ctypes.c_int, _c_f, ctypes.c_int, ctypes.c_int, _c_f, _c_f, ctypes.c_ulonglong,
-                                  ctypes.c_long, ctypes.c_int] + [_c_f] * 5 + [ctypes.c_void_p],
-    "votenet_augment_boxes": [ctypes.c_int, ctypes.c_int] + [_c_f] * 11 + [ctypes.c_int, ctypes.c_int] + [_c_f] * 8 + [ctypes.c_void_p],
-    "votenet_select_boxes": [ctypes.c_int, ctypes.c_int, _c_f, ctypes.c_int, ctypes.c_int, _c_f, _c_f, ctypes.c_ulonglong,
-                             ctypes.c_long] + [_c_f] * 17 + [ctypes.c_size_t, ctypes.c_void_p],
-    "votenet_transpose_segments": [ctypes.c_int] + [_c_f] * 3 + [ctypes.c_void_p],
-    "votenet_split_weights": [ctypes.c_int, _c_f, ctypes.c_void_p],
-    "votenet_split_weights_h2": [ctypes.c_int, _c_f, ctypes.c_void_p],
-    "votenet_register_split_weights_pieces": [_c_f, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int],
-    "votenet_register_split_weights_scaled": [_c_f, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, _c_f, _c_f],
-    "votenet_pool_dgrad_prepare_h2": [ctypes.c_int, ctypes.c_int] + [_c_f] * 8 + [ctypes.c_void_p],
-    "votenet_split_weights_one": [_c_f, ctypes.c_int, ctypes.c_int, _c_f, ctypes.c_void_p],
-    "votenet_mlp_split_k_arm": [ctypes.c_void_p, ctypes.c_long],
-    "votenet_mlp_split_k_tickets": [ctypes.c_void_p, ctypes.c_long],
-    "votenet_register_split_weights": [_c_f, ctypes.c_int, ctypes.c_int, ctypes.c_void_p],
-    "votenet_bn_finalize": [ctypes.c_long, ctypes.c_int] + [_c_f] * 3 + [ctypes.c_float] + [_c_f] * 4 + [ctypes.c_void_p],
-    "votenet_bn_relu_max": [ctypes.c_long, ctypes.c_int, ctypes.c_int] + [_c_f] * 3 + [ctypes.c_int] + [_c_f] * 2 + [ctypes.c_void_p],
-    "votenet_bn_relu_pool": [ctypes.c_long, ctypes.c_int, ctypes.c_int] + [_c_f] * 3 + [ctypes.c_int] * 2 + [_c_f] * 4 + [ctypes.c_void_p],
-    "votenet_sa_pool_weights": [ctypes.c_int] * 4 + [_c_f] * 4 + [ctypes.c_void_p],
-    "votenet_sa_pool_grad": [ctypes.c_long] + [ctypes.c_int] * 3 + [_c_f] * 4 + [ctypes.c_void_p],
-    "votenet_sa_pool_weights_grad": [ctypes.c_int] * 5 + [_c_f] * 6 + [ctypes.c_int] + [_c_f] * 4 + [ctypes.c_void_p],
-    "votenet_bn_relu": [ctypes.c_long, ctypes.c_int] + [_c_f] * 3 + [ctypes.POINTER(BnRaw), ctypes.c_int, _c_f, ctypes.c_void_p],
-    "votenet_bn_backward_reduce": [ctypes.c_long, ctypes.c_int, ctypes.c_int] + [_c_f] * 7 + [ctypes.c_float, ctypes.c_int, _c_f,
-                                                                                             ctypes.POINTER(CoefTail), ctypes.c_void_p],
-    "votenet_bn_backward_apply": [ctypes.c_long, ctypes.c_int, ctypes.c_int] + [_c_f] * 4 + [ctypes.c_int, _c_f, ctypes.c_void_p],
-    "votenet_bias_grad": [ctypes.c_long, ctypes.c_int] + [_c_f] * 3 + [ctypes.c_void_p],
-    "votenet_mlp_wgrad": [ctypes.POINTER(MlpInput), ctypes.c_long, ctypes.c_int, ctypes.c_int] + [_c_f] * 3 + [ctypes.c_void_p],
-    "votenet_bn_backward_coef": [ctypes.c_long, ctypes.c_int] + [_c_f] * 4 + [ctypes.c_float] + [_c_f] * 5 + [ctypes.c_void_p],
-    "votenet_mlp_wgrad_bn": [ctypes.POINTER(MlpInput), ctypes.c_long, ctypes.c_int, ctypes.c_int] + [_c_f] * 3 + [ctypes.c_int]
-                            + [_c_f] * 2 + [ctypes.c_int, _c_f, _c_f, ctypes.c_void_p],
-    "votenet_mlp_dgrad_bn": [ctypes.c_long, ctypes.c_int, ctypes.c_int] + [_c_f] * 3 + [ctypes.c_int] + [_c_f] * 2 + [ctypes.c_int]
-                            + [_c_f] * 2 + [ctypes.c_void_p],
-    "votenet_mlp_dgrad_bn_reduce": [ctypes.c_long, ctypes.c_int, ctypes.c_int] + [_c_f] * 3 + [ctypes.c_int] + [_c_f] * 7
-                                   + [ctypes.c_float, ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(CoefTail), ctypes.c_void_p],
-    "votenet_assemble_rows": [ctypes.c_int] * 4 + [_c_f] * 7 + [ctypes.c_void_p],
-    "votenet_assemble_stats": [ctypes.c_long, ctypes.c_int] + [_c_f] * 5 + [ctypes.c_void_p],
-    "votenet_assemble_z0": [ctypes.c_long, ctypes.c_int] + [_c_f] * 4 + [ctypes.c_void_p],
-    "votenet_assembled_linear": [ctypes.c_long, ctypes.c_int, ctypes.c_int] + [_c_f] * 5 + [ctypes.POINTER(BnRaw), ctypes.c_int]
-                                + [_c_f] * 4 + [ctypes.c_void_p],
-    "votenet_assembled_wgrad_bn": [ctypes.c_long, ctypes.c_int, ctypes.c_int] + [_c_f] * 5 + [ctypes.c_int] + [_c_f] * 3 + [ctypes.c_int, _c_f, _c_f,
-                                   ctypes.c_void_p],
-    "votenet_assembled_dgrad_bn_reduce": [ctypes.c_long, ctypes.c_int, ctypes.c_int] + [_c_f] * 3 + [ctypes.c_int] + [_c_f] * 9
-                                         + [ctypes.c_float, ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(CoefTail), ctypes.c_void_p],
-    "votenet_group_linear_backward_assembled": [ctypes.c_int] * 5 + [_c_f] * 8 + [ctypes.c_int] + [_c_f] * 3 + [ctypes.c_void_p],
-    "votenet_narrow_rows": [ctypes.c_int] * 5 + [_c_f] * 6 + [ctypes.c_void_p],
-    "votenet_narrow_z0": [ctypes.c_long, ctypes.c_int, ctypes.c_int] + [_c_f] * 4 + [ctypes.c_void_p],
-    "votenet_narrow_stats": [ctypes.c_long, ctypes.c_int, ctypes.c_int] + [_c_f] * 4 + [ctypes.c_void_p],
-    "votenet_narrow_linear": [ctypes.c_long, ctypes.c_int, ctypes.c_int, ctypes.c_int] + [_c_f] * 5 + [ctypes.POINTER(BnRaw), ctypes.c_int]
-                             + [_c_f] * 4 + [ctypes.c_void_p],
-    "votenet_narrow_wgrad_bn": [ctypes.c_long, ctypes.c_int, ctypes.c_int, ctypes.c_int] + [_c_f] * 5 + [ctypes.c_int] + [_c_f] * 3
-                               + [ctypes.c_int, _c_f, _c_f, ctypes.c_void_p],
-    "votenet_narrow_dgrad_bn_reduce": [ctypes.c_long, ctypes.c_int, ctypes.c_int, ctypes.c_int] + [_c_f] * 3 + [ctypes.c_int] + [_c_f] * 8
-                                      + [ctypes.c_float, ctypes.c_int, _c_f, _c_f, ctypes.POINTER(CoefTail), ctypes.c_void_p],
-    "votenet_narrow_wgrad_first": [ctypes.c_int, ctypes.c_int] + [_c_f] * 6 + [ctypes.c_void_p],
-    "votenet_group_concat_grad": [ctypes.c_int] * 5 + [_c_f] * 7 + [ctypes.c_void_p],
-    "votenet_inverse_index": [ctypes.c_int] * 3 + [_c_f] * 3 + [ctypes.c_void_p],
-    "votenet_csr_gather_sum": [ctypes.c_long, ctypes.c_int] + [_c_f] * 4 + [ctypes.c_int, _c_f, ctypes.c_void_p],
-    "votenet_csr_gather_sum_pitched": [ctypes.c_long, ctypes.c_int, _c_f, ctypes.c_long] + [_c_f] * 3 + [ctypes.c_int, _c_f, ctypes.c_void_p],
-    "votenet_group_linear_backward_csr": [ctypes.c_int] * 5 + [_c_f] * 8 + [ctypes.c_int] + [_c_f] * 4 + [ctypes.c_void_p],
-    "votenet_rows_dot3": [ctypes.c_long, ctypes.c_int] + [_c_f] * 3 + [ctypes.c_void_p],
-    "votenet_clip_adam": [ctypes.c_int] + [_c_f] * 6 + [ctypes.c_float] * 4 + [ctypes.c_int, ctypes.c_float, ctypes.c_float,
-                                                                              ctypes.c_void_p],
-})
+_STRUCTS = ("BnRaw", "CoefTail", "MlpInput", "RowSegment", "CopySegment")  # votenet_bn_raw, ... of votenet_hip.h
+_abi_read = None
 
 
-class RowSegment(ctypes.Structure):
-    """struct votenet_row_segment (include/votenet_hip.h)."""
-    _fields_ = [("dst", ctypes.c_void_p), ("dst_pitch", ctypes.c_int), ("dst_off", ctypes.c_int), ("width", ctypes.c_int),
-                ("a", ctypes.c_void_p), ("a_pitch", ctypes.c_int), ("a_off", ctypes.c_int),
-                ("b", ctypes.c_void_p), ("b_pitch", ctypes.c_int), ("b_off", ctypes.c_int)]
+def _abi():
+    """({function: (restype, argtypes)} of votenet_hip.h, the same of votenet_hip_debug.h); the headers are read once, found relative
+    to the package as csrc/common.h finds them, and their structs become this module's BnRaw ... CopySegment."""
+    global _abi_read
+    if _abi_read is None:
+        structs, protos = {}, []
+        for h in ("votenet_hip.h", "votenet_hip_debug.h"):
+            with open(os.path.join(_HERE, os.pardir, "include", h)) as f:
+                protos.append(parse_header(f.read(), structs))
+        globals().update({cls.__name__: cls for cls in structs.values()})
+        _abi_read = tuple(protos)
+    return _abi_read
 
 
-class CopySegment(ctypes.Structure):
-    """struct votenet_copy_segment (include/votenet_hip.h)."""
-    _fields_ = [("dst", ctypes.c_void_p), ("src", ctypes.c_void_p), ("bytes", ctypes.c_long)]
-
-
-_SIGS["votenet_copy_segments"] = [ctypes.c_int, ctypes.POINTER(CopySegment), ctypes.c_void_p]
-_SIGS["votenet_three_interpolate_concat"] = [ctypes.c_int] * 4 + [_c_f] * 4 + [ctypes.c_int, _c_f, ctypes.c_void_p]
-_SIGS["votenet_three_interpolate_grad_strided"] = [ctypes.c_int] * 4 + [_c_f, ctypes.c_int, ctypes.c_int] + [_c_f] * 3 + [ctypes.c_void_p]
-_SIGS["votenet_bias_grad_strided"] = [ctypes.c_long, ctypes.c_int, _c_f, ctypes.c_int, _c_f, _c_f, ctypes.c_void_p]
-_SIGS["votenet_ema_update"] = [ctypes.c_long, ctypes.c_float, _c_f, _c_f, _c_f, ctypes.c_void_p]
-_SIGS["votenet_row_segments"] = [ctypes.c_long, ctypes.c_int, ctypes.POINTER(RowSegment), ctypes.c_void_p]
-# piece layout (csrc/half.hip)
-_I, _L, _F = ctypes.c_int, ctypes.c_long, ctypes.c_float
-_SIGS.update({
-    "votenet_half_groups": [_I] + [_c_f] * 6 + [ctypes.c_void_p],
-    "votenet_assemble_rows_half": [_I] * 3 + [_c_f] * 10 + [ctypes.c_void_p],
-    "votenet_assembled_linear_half": [_L, _I, _I] + [_c_f] * 5 + [ctypes.POINTER(BnRaw), _I] + [_c_f] * 6 + [ctypes.c_void_p],
-    "votenet_mlp_linear_half": [_c_f] * 3 + [_I, _L, _I, _I] + [_c_f] * 4 + [ctypes.c_void_p],
-    "votenet_half_centre_sums": [_L, _I] + [_c_f] * 7 + [_I, _c_f, ctypes.c_void_p],
-    "votenet_mlp_linear_pool_half": [ctypes.POINTER(MlpInput), _L, _I, _I] + [_c_f] * 9 + [ctypes.c_void_p],
-    "votenet_bn_pool_finalize_half": [_L, _I] + [_c_f] * 5 + [ctypes.POINTER(BnRaw), _I] + [_c_f] * 3 + [ctypes.c_void_p],
-    "votenet_pool_dgrad_scatter_half": [_L, _I, _I, _I] + [_c_f] * 4 + [_I] + [_c_f] * 9 + [_F, _I, _c_f, ctypes.POINTER(CoefTail), _c_f,
-                                                                                       ctypes.c_void_p],
-    "votenet_mlp_gram_half": [_L, _I, _c_f, _c_f, _I, _c_f, _c_f, _c_f, ctypes.c_void_p],
-    "votenet_pool_wgrad_sparse_half": [_L, _I, _I, _I] + [_c_f] * 3 + [_I] + [_c_f] * 4 + [_I] + [_c_f] * 5 + [ctypes.c_void_p],
-    "votenet_pool_wgrad_sparse_half_centres": [_L, _I, _I, _I] + [_c_f] * 3 + [_I] + [_c_f] * 4 + [_I] + [_c_f] * 5 + [ctypes.c_void_p],
-    "votenet_assembled_wgrad_bn_half": [_L, _I, _I] + [_c_f] * 5 + [_I] + [_c_f] * 3 + [_I, _c_f, _c_f, _c_f, ctypes.c_void_p],
-    "votenet_assembled_dgrad_bn_reduce_half": [_L, _I, _I] + [_c_f] * 3 + [_I] + [_c_f] * 9 + [_F, _I, ctypes.c_void_p,
-                                                                                             ctypes.POINTER(CoefTail), _c_f, _c_f, ctypes.c_void_p],
-    "votenet_half_piece_rows": [],
-    "votenet_half_sort_rows": [_I, _I] + [_c_f] * 3 + [_I, _c_f, ctypes.c_void_p],
-    "votenet_mlp_dgrad_bn_half": [_L, _I, _I] + [_c_f] * 3 + [_I] + [_c_f] * 4 + [ctypes.c_void_p],
-    "votenet_group_linear_backward_masked": [_L, _I] + [_c_f] * 9 + [_F, _I] + [_c_f] * 4 + [ctypes.c_void_p, _c_f, ctypes.c_void_p],
-    "votenet_assembled_point_grad": [_L, _I] + [_c_f] * 6 + [ctypes.c_void_p],
-    "votenet_assembled_wx_finish": [_I] + [_c_f] * 3 + [_I] + [_c_f] * 3 + [ctypes.c_void_p],
-    "votenet_group_linear_backward_sorted": [_L, _I] + [_c_f] * 7 + [_I] + [_c_f] * 3 + [ctypes.c_void_p],
-    "votenet_narrow_rows_half": [_I] * 4 + [_c_f] * 9 + [ctypes.c_void_p],
-    "votenet_narrow_linear_masked": [_L, _I, _I, _I] + [_c_f] * 5 + [ctypes.POINTER(BnRaw), _I] + [_c_f] * 6 + [ctypes.c_void_p],
-    "votenet_narrow_dgrad_bn_reduce_masked": [_L, _I, _I, _I] + [_c_f] * 3 + [_I] + [_c_f] * 8 + [_F, _I, _c_f, _c_f, ctypes.POINTER(CoefTail),
-                                              _c_f, _c_f, ctypes.c_void_p],
-    "votenet_narrow_linear_half": [_L, _I, _I, _I] + [_c_f] * 5 + [ctypes.POINTER(BnRaw), _I] + [_c_f] * 5 + [ctypes.c_void_p],
-    "votenet_narrow_wgrad_bn_half": [_L, _I, _I, _I] + [_c_f] * 5 + [_I] + [_c_f] * 3 + [_I, _c_f, _c_f, ctypes.c_void_p],
-    "votenet_narrow_dgrad_bn_reduce_half": [_L, _I, _I, _I] + [_c_f] * 3 + [_I] + [_c_f] * 8 + [_F, _I, _c_f, _c_f, ctypes.POINTER(CoefTail),
-                                                                                            _c_f, ctypes.c_void_p],
-})
+def __getattr__(name):  # the structs, for a caller that builds one before anything has loaded the library
+    if name in _STRUCTS:
+        _abi()
+        return globals()[name]
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))
 
 
 class _Library(ctypes.CDLL):
-    """The library's measurement / tuning switches (include/votenet_hip_debug.h) are inert until the host opts in.  This host opts in
-    the first time something (a test, a profile tool, mlp.debug_switch) looks one up; code that never touches a switch never does."""
+    """Every function gets its header's prototype when it is first looked up.  The library's measurement / tuning switches
+    (include/votenet_hip_debug.h) are inert until the host opts in.  This host opts in the first time something (a test, a profile tool,
+    mlp.debug_switch) looks one up; code that never touches a switch never does."""
 
     def __getattr__(self, name):  # only reached for names not bound yet (CDLL caches what it has resolved)
         fn = super().__getattr__(name)
+        for protos in _abi():
+            if name in protos:  # (anything else is one of the reference's eight C++ launcher names: the caller types those)
+                fn.restype, fn.argtypes = protos[name]
         if "debug" in name and name not in ("votenet_debug_enable", "votenet_debug_enabled", "votenet_debug_fps_split_timeouts"):
-            super().__getattr__("votenet_debug_enable")(1)
+            self.votenet_debug_enable(1)
         return fn
 
 
 def lib():
-    """Load the library once; raise loudly if it has not been built."""
+    """Load the library once; raise loudly if it has not been built or lacks a function votenet_hip.h declares."""
     global _lib
     if _lib is None:
         if not os.path.exists(_LIB_PATH):
@@ -246,36 +149,8 @@ def lib():
                 "libvotenet_hip.so not found at %s -- run `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(there is no CPU fallback)" % _LIB_PATH)
         L = _Library(_LIB_PATH)
-        L.votenet_last_error.restype = ctypes.c_char_p
-        L.votenet_version.restype = ctypes.c_char_p
-        L.votenet_fps_temp_floats.restype = ctypes.c_size_t
-        L.votenet_fps_temp_floats.argtypes = [ctypes.c_int, ctypes.c_int]
-        L.votenet_mlp_wgrad_scratch_floats.restype = ctypes.c_size_t
-        L.votenet_mlp_wgrad_scratch_floats.argtypes = [ctypes.POINTER(MlpInput), ctypes.c_long, ctypes.c_int, ctypes.c_int]
-        L.votenet_pool_wgrad_scratch_floats.restype = ctypes.c_size_t
-        L.votenet_pool_wgrad_scratch_floats.argtypes = [ctypes.c_long, ctypes.c_int, ctypes.c_int]
-        L.votenet_group_linear_backward_scratch_floats.restype = ctypes.c_size_t
-        L.votenet_group_linear_backward_scratch_floats.argtypes = [ctypes.c_int] * 3
-        L.votenet_spatial_index_floats.restype = ctypes.c_size_t
-        L.votenet_spatial_index_floats.argtypes = [ctypes.c_int, ctypes.c_int]
-        L.votenet_loss_workspace_floats.restype = ctypes.c_size_t
-        L.votenet_loss_workspace_floats.argtypes = [ctypes.c_int]
-        L.votenet_knn_workspace_bytes.restype = ctypes.c_size_t
-        L.votenet_knn_workspace_bytes.argtypes = [ctypes.c_int] * 3
-        L.votenet_select_boxes_workspace_bytes.restype = ctypes.c_size_t
-        L.votenet_select_boxes_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_long]
-        L.votenet_nms3d_workspace_bytes.restype = ctypes.c_size_t
-        L.votenet_nms3d_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int]
-        L.votenet_mlp_split_k_floats.restype = ctypes.c_long
-        L.votenet_mlp_split_k_floats.argtypes = [ctypes.c_long, ctypes.c_int, ctypes.c_int]
-        L.votenet_bn_relu_pool_workspace_floats.restype = ctypes.c_size_t
-        L.votenet_bn_relu_pool_workspace_floats.argtypes = [ctypes.c_long, ctypes.c_int, ctypes.c_int]
-        L.votenet_ball_threshold.restype = ctypes.c_float
-        L.votenet_ball_threshold.argtypes = [ctypes.c_float]
-        for name, sig in _SIGS.items():
-            fn = getattr(L, name)
-            fn.restype = ctypes.c_int
-            fn.argtypes = sig
+        for name in _abi()[0]:  # (not the debug header's: looking a switch up opts in)
+            getattr(L, name)
         _lib = L
     return _lib
 
