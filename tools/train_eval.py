@@ -2,9 +2,11 @@
 tower (decode -> 3D NMS) on held-out scenes and report mAP@0.25 / @0.5 with the reference's evaluator logic: "mAP" is the mean
 of the per-batch mAPs (the figure of every earlier log), "set mAP" the reference's own metric, detections ranked over the whole
 validation set (evaluator.evaluate).
-    python tools/train_eval.py [steps] [train_batches] [--save PATH] [--resume PATH]
+    python tools/train_eval.py [steps] [train_batches] [--save PATH] [--resume PATH] [--monitor K]
 --save PATH: a checkpoint (VoteNetHotPath.save) at every evaluation and at the end.  --resume PATH: continue the run a checkpoint
-holds -- parameters, moving averages, Adam state and step count -- up to `steps` steps in all, on the batches it would have seen."""
+holds -- parameters, moving averages, Adam state and step count -- up to `steps` steps in all, on the batches it would have seen.  --monitor K: the reference's training summaries from the device
+(VoteNetHotPath.enable_monitors): every K steps the moving averages of obj_accuracy / sem_accuracy / total_cost over the last 100 steps
+(run.py:127) beside the window's mean n_pos / n_neg, every 10 K steps the five tensors with the smallest and the largest gradient rms."""
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import importlib.util
@@ -20,6 +22,7 @@ ap.add_argument("steps", nargs="?", type=int, default=600)
 ap.add_argument("train_batches", nargs="?", type=int, default=16)
 ap.add_argument("--save", metavar="PATH", help="write a checkpoint at every evaluation and at the end")
 ap.add_argument("--resume", metavar="PATH", help="continue from this checkpoint")
+ap.add_argument("--monitor", metavar="K", type=int, default=0, help="print the moving averages of the accuracies and the cost every K steps")
 args = ap.parse_args()
 steps, nb = args.steps, args.train_batches
 dev = torch.device("cuda:0")
@@ -29,6 +32,8 @@ net.init_optimizer(1e-3)
 if args.resume:
     net.load(args.resume)
 start = net._step
+if args.monitor > 0:
+    net.enable_monitors(window=100, tensors_every=10 * args.monitor)
 xs = [torch.from_numpy(synth.room_batch(B, n, 5000 + B * i)).to(dev) for i in range(nb)]
 gts = [VL.gt_to_device(synth.room_gt(B, n, 5000 + B * i), dev) for i in range(nb)]
 val_x = [torch.from_numpy(synth.room_batch(B, n, 90000 + B * i)).to(dev) for i in range(4)]
@@ -66,6 +71,18 @@ for i in range(start, steps):
         l = net.last_losses.cpu().numpy()
         print("step %d  cost %.3f  vote %.3f obj %.3f box %.3f sem %.3f  pos %d  (%.1f s)" % (i + 1, l[0], l[1], l[2], l[9], l[8], int(l[10]),
                                                                                               time.time() - t0))
+    if args.monitor > 0 and (i + 1) % args.monitor == 0:
+        r = net.monitors.read()  # (the one read-back of the monitors: every K steps)
+        m = r["mean"]
+        print("step %d  moving averages over %d steps: obj_accuracy %.4f  sem_accuracy %.4f  total_cost %.4f  n_pos %.1f  n_neg %.1f"
+              % (i + 1, r["filled"], m["obj_accuracy"], m["sem_accuracy"], m["total_cost"], m["n_pos"], m["n_neg"]))
+        if (i + 1) % (10 * args.monitor) == 0 and r["tensors"]:
+            by_rms = sorted(r["tensors"].items(), key=lambda kv: kv[1]["grad"]["rms"])
+            for title, rows in (("smallest", by_rms[:5]), ("largest", by_rms[-5:])):
+                print("step %d  %s gradient rms (of step %d; rms of the clipped gradient = rms x clip factor):" % (i + 1, title, r["tensors_step"]))
+                for name, t in rows:
+                    print("    %-28s grad rms %.3e  clip factor %.3e  param rms %.3e  non-finite %d" % (name, t["grad"]["rms"], t["grad"]["clip_factor"],
+                                                                                                    t["param"]["rms"], t["grad"]["nonfinite"] + t["param"]["nonfinite"]))
     if (i + 1) % 300 == 0:
         report(i + 1)
         save()

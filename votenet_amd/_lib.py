@@ -13,7 +13,9 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_PATH = os.path.join(_HERE, "lib", "libvotenet_hip.so")
+_MON_PATH = os.path.join(_HERE, "lib", "libvotenet_monitors.so")  # the training summaries (include/votenet_monitors.h): a library of its own
 _lib = None
+_mon = None
 
 
 class VotenetError(RuntimeError):
@@ -32,7 +34,8 @@ def build(force=False):
     """Compile libvotenet_hip.so for gfx950 with hipcc (cross-compiles without a GPU)."""
     if force:  # a clean build: the library AND every cached object file (build.sh recompiles what is missing)
         import glob
-        for f in [_LIB_PATH] + glob.glob(os.path.join(_HERE, "csrc", "obj", "*.o")):
+        mon = os.path.join(os.path.dirname(_LIB_PATH), os.path.basename(_MON_PATH))
+        for f in [_LIB_PATH, mon] + glob.glob(os.path.join(_HERE, "csrc", "obj", "*.o")) + glob.glob(os.path.join(_HERE, "csrc", "monitors", "obj", "*.o")):
             if os.path.exists(f):
                 os.remove(f)
     out = subprocess.run(["bash", os.path.join(_HERE, "csrc", "build.sh")], capture_output=True, text=True)
@@ -153,6 +156,34 @@ def lib():
             getattr(L, name)
         _lib = L
     return _lib
+
+
+def monitors_lib():
+    """libvotenet_monitors.so, loaded when a summary is first asked for; every function of include/votenet_monitors.h gets its header's
+    prototype (parse_header, as for the main library).  No fallback: a missing library is an error."""
+    global _mon
+    if _mon is None:
+        if not os.path.exists(_MON_PATH):
+            raise VotenetError("libvotenet_monitors.so not found at %s -- run `python -c 'import __graft_entry__ as g; g.build()'` "
+                               "(there is no CPU fallback)" % _MON_PATH)
+        with open(os.path.join(_HERE, os.pardir, "include", "votenet_monitors.h")) as f:
+            protos = parse_header(f.read(), {})
+        M = ctypes.CDLL(_MON_PATH)
+        for name, (restype, argtypes) in protos.items():
+            fn = getattr(M, name)
+            fn.restype, fn.argtypes = restype, argtypes
+        _mon = M
+    return _mon
+
+
+def check_monitors(rc):
+    """check() for a status libvotenet_monitors.so returned (it keeps its own error text)."""
+    if rc == 0:
+        return
+    msg = monitors_lib().votenet_monitors_last_error().decode()
+    if rc == 1:
+        raise InvalidArgumentError(msg)
+    raise VotenetError("libvotenet_monitors error %d: %s" % (rc, msg))
 
 
 def check(rc):

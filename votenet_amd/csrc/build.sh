@@ -13,6 +13,7 @@ for src in "$HERE"/*.hip; do
   obj="$HERE/obj/$(basename "${src%.hip}").o"
   # (this script carries the flags: an object older than it is stale too)
   if [ ! -f "$obj" ] || [ "$src" -nt "$obj" ] || [ "$HERE/common.h" -nt "$obj" ] || [ "$HERE/mlp_types.h" -nt "$obj" ] || [ "$HERE/iou3d.h" -nt "$obj" ] \
+     || [ "$HERE/nearest_box.h" -nt "$obj" ] \
      || [ "$HERE/../../include/votenet_hip.h" -nt "$obj" ] || [ "$HERE/../../include/votenet_hip_debug.h" -nt "$obj" ] \
      || [ "${BASH_SOURCE[0]}" -nt "$obj" ]; then
     extra=""
@@ -36,3 +37,17 @@ $HIPCC --offload-arch=gfx950 -shared -fPIC -Wl,--version-script="$HERE/exports.m
 python3 "$HERE/../../tools/check_isa_hazards.py" "$TMP"
 mv -f "$TMP" "$OUT/libvotenet_hip.so"
 echo "built $OUT/libvotenet_hip.so"
+# libvotenet_monitors.so (include/votenet_monitors.h): the training summaries, a library of its own -- the drop-in library's export
+# list stays the reference's ops.  Same flags, same gate; -fno-slp-vectorize as loss.hip, whose assignment loop it shares.
+MOBJ="$HERE/monitors/obj/monitors.o"
+mkdir -p "$HERE/monitors/obj"
+if [ ! -f "$MOBJ" ] || [ "$HERE/monitors/monitors.hip" -nt "$MOBJ" ] || [ "$HERE/nearest_box.h" -nt "$MOBJ" ] \
+   || [ "$HERE/../../include/votenet_monitors.h" -nt "$MOBJ" ] || [ "${BASH_SOURCE[0]}" -nt "$MOBJ" ]; then
+  $HIPCC $FLAGS -fno-slp-vectorize -c "$HERE/monitors/monitors.hip" -o "$MOBJ"
+fi
+MTMP="$OUT/.libvotenet_monitors.so.tmp.$$"
+trap 'rm -f "$TMP" "$MTMP"' EXIT
+$HIPCC --offload-arch=gfx950 -shared -fPIC -Wl,--version-script="$HERE/monitors/exports.map" "$MOBJ" -o "$MTMP"
+python3 "$HERE/../../tools/check_isa_hazards.py" "$MTMP"
+mv -f "$MTMP" "$OUT/libvotenet_monitors.so"
+echo "built $OUT/libvotenet_monitors.so"

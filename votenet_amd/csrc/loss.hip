@@ -6,6 +6,7 @@
 // one workgroup walks them (B*1024 seeds, B*256 proposals, <= 16 boxes per scene): the step is launch-latency, not work.
 // Reductions are wave shuffles + a fixed-order combine: the loss values are reproducible bit for bit.
 #include "common.h"
+#include "nearest_box.h"
 
 namespace votenet {
 
@@ -49,23 +50,7 @@ __device__ __forceinline__ float softmax_ce(const float *lg, int c, int label, f
     return logf(s) + m - lg[label];
 }
 
-// nearest ground-truth centre of proposal (px,py,pz) among the scene's boxes staged in LDS: -> distance, box index
-__device__ __forceinline__ float nearest_box(const float (*s_box)[8], int BB, float px, float py, float pz, int &g)
-{
-    float best = 0.0f;
-    g = 0;
-    for (int j = 0; j < BB; j++) {
-        const float dx = px - s_box[j][0], dy = py - s_box[j][1], dz = pz - s_box[j][2];
-        const float d = sqrtf(dx * dx + dy * dy + dz * dz);
-        if (j == 0 || d < best) { // tf.argmin: first minimum
-            best = d;
-            g = j;
-        }
-    }
-    return best;
-}
-
-constexpr int LOSS_MAXBOX = 256; // boxes per scene
+// nearest_box, LOSS_MAXBOX: nearest_box.h (shared with the accuracy kernel of monitors/monitors.hip: one assignment for both)
 
 // pass 1: one workgroup per scene counts its positive / negative proposals (model.py:147-153); the means of the loss are
 // over the counts of the WHOLE batch, so they have to exist before any cotangent can be written.

@@ -67,6 +67,53 @@ def votenet_loss(out, gt, nh=NH, ns=NS, nc=NC, buffers=None):
     return losses, dict(votes_xyz=d_votes, proposals_xyz=d_pxyz, proposals_output=d_pout)
 
 
+ACCURACY_COUNTS = ("n_obj_correct", "n_sem_correct", "n_pos", "n_neg")
+RING_COLS = 5  # VOTENET_MONITOR_RING_COLS (include/votenet_monitors.h): obj_accuracy, sem_accuracy, total_cost, n_pos, n_neg
+
+
+def votenet_accuracies(out, gt, nh=NH, ns=NS, nc=NC, losses=None, ring=None, ring_row=0, buffers=None):
+    """obj_accuracy and sem_accuracy of one step (model.py:164-166, 215-216) on the device, one launch (votenet_accuracies of
+    libvotenet_monitors.so, csrc/monitors/monitors.hip).
+    out, gt: as votenet_loss takes them.  -> accuracies (2,) f32, counts (4,) int32 (ACCURACY_COUNTS), both on the device; nothing is
+    read back.  losses: the vector votenet_loss returned; with ring (window, RING_COLS) f32 the launch also writes row ring_row of it:
+    (obj_accuracy, sem_accuracy, losses[0], n_pos, n_neg).  buffers: (accuracies, counts, workspace) of a caller that keeps them
+    (monitors.Monitors; the workspace is 8 int32 zeros, left zero by every launch)."""
+    pxyz = L.dev_f32(out["proposals_xyz"], "accuracies proposals_xyz", 3, 3)
+    pout = out["proposals_output"]
+    if not (isinstance(pout, torch.Tensor) and pout.is_cuda and pout.dtype == torch.float32 and pout.dim() == 3 and pout.stride(2) == 1
+            and pout.stride(1) >= pout.shape[2] and pout.stride(0) == pout.shape[1] * pout.stride(1)):
+        pout = L.dev_f32(pout, "accuracies proposals_output", 3)
+    b, p = pxyz.shape[:2]
+    if pout.shape[2] != 5 + 2 * nh + 4 * ns + nc or tuple(pout.shape[:2]) != (b, p):
+        raise L.InvalidArgumentError("accuracies: proposals_output has shape %s, expected (%d, %d, %d)"
+                                     % (tuple(pout.shape), b, p, 5 + 2 * nh + 4 * ns + nc))
+    gxyz, sem = L.dev_f32(gt["bboxes_xyz"], "accuracies bboxes_xyz", 3, 3), L.dev_i32(gt["semantic_labels"], "accuracies semantic_labels", 2)
+    if gxyz.shape[0] != b or tuple(sem.shape) != tuple(gxyz.shape[:2]):
+        raise L.InvalidArgumentError("accuracies: ground truth of %s boxes / %s labels for %d scenes" % (tuple(gxyz.shape), tuple(sem.shape), b))
+    dev = pxyz.device
+    if buffers is not None:
+        acc, counts, work = buffers
+    else:
+        acc = torch.empty(2, dtype=torch.float32, device=dev)
+        counts = torch.empty(4, dtype=torch.int32, device=dev)
+        work = torch.zeros(8, dtype=torch.int32, device=dev)
+    if acc.numel() != 2 or counts.numel() != 4 or work.numel() < 8:
+        raise L.InvalidArgumentError("accuracies: buffers of the wrong size")
+    rows = 0
+    if ring is not None:
+        ring = L.dev_f32(ring, "accuracies ring", 2, RING_COLS)
+        rows = ring.shape[0]
+        if not 0 <= ring_row < rows:
+            raise L.InvalidArgumentError("accuracies: row %d outside a ring of %d rows" % (ring_row, rows))
+    if losses is not None and (losses.numel() != 12 or losses.dtype != torch.float32 or not losses.is_cuda):
+        raise L.InvalidArgumentError("accuracies: losses must be the 12 floats of votenet_loss on the device")
+    with L.device_guard(dev):
+        L.check_monitors(L.monitors_lib().votenet_accuracies(b, p, gxyz.shape[1], nh, ns, nc, L.ptr(pxyz), L.ptr(pout), pout.stride(1), L.ptr(gxyz), L.ptr(sem),
+                                           POSITIVE_THRES, NEGATIVE_THRES, L.ptr(losses), L.ptr(ring), rows, ring_row, L.ptr(acc),
+                                           L.ptr(counts), L.ptr(work), L.stream_ptr()))
+    return acc, counts
+
+
 def decode_boxes(proposals_xyz, proposals_output, nh=NH, ns=NS, nc=NC):
     """model.py:100-129 on the device: -> bboxes (B,P,8,3), scores (B,P) = max class logit (the inputs of NMS3D)."""
     from .synth import MEAN_SIZES

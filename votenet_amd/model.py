@@ -221,10 +221,11 @@ class StretchGraph:
     def copy_inputs(self, ins):
         M.copy_segments([(self.fixed[k], ins[k]) for k in self.names])
 
-    def replay(self, ins, gt, wgrad_stream=None):
+    def replay(self, ins, gt, wgrad_stream=None, after_loss=None):
         """One copy launch, then the segments in order -- the loss graph on gt as launches where it belongs --; a segment's
         weight-gradient thunks go to wgrad_stream (None: the current one) behind its graph.  The caller joins the weight-gradient stream
-        (pointnet2.wgrad_join) before it reads the gradient bucket."""
+        (pointnet2.wgrad_join) before it reads the gradient bucket.  after_loss(out, gt, losses): called behind the loss launch (the
+        monitors' accuracy launch: a launch between two segments like the loss, no graph is captured again or gets a node)."""
         from . import loss as VL
         self.copy_inputs(ins)
         prev = P.WGRAD_STREAM
@@ -236,6 +237,8 @@ class StretchGraph:
                     # vector of a small ring, so a handle to last_losses kept across a few steps still shows ITS step (no copy launch)
                     losses = self._loss_ring[self.replays % len(self._loss_ring)]
                     VL.votenet_loss(self.out, gt, buffers=(losses, self.loss_bufs[1]))
+                    if after_loss is not None:
+                        after_loss(self.out, gt, losses)
                 graph.replay()
                 if thunks and wgrad_stream is not None:
                     P._hand_over([f for f, _ in thunks], ())  # (their tensors live in the graphs' pool: nothing for the allocator to track)
@@ -795,6 +798,8 @@ class VoteNetHotPath:
         out = self._head_forward(lv, geom("fp1"), geom("fp2"), I["prop_fps"], tail, copy_seeds=copy_seeds)
         self.update_moving_averages(list(tape_levels) + tail)
         losses, cot = loss_hook(out) if loss_hook is not None else VL.votenet_loss(out, gt)
+        if loss_hook is None and self.monitors is not None:
+            self.last_accuracies = self.monitors.after_loss(out, gt, losses)
         P.WGRAD_STREAM = wgrad_stream
         try:
             grads = self._head_backward(tail, cot, cut=cut)
@@ -851,7 +856,11 @@ class VoteNetHotPath:
         self.store._fresh_wait()
         if self.overlap_wgrad and self._wgrad_stream is None:
             self._wgrad_stream = torch.cuda.Stream(device=self.device, priority=WGRAD_PRIORITY)
-        out, self.last_losses, grads = sg.replay(ins, gt, self._wgrad_stream if self.overlap_wgrad else None)  # (a vector of the graph's ring: rewritten eight replays later)
+        mon = self.monitors
+        out, self.last_losses, grads = sg.replay(ins, gt, self._wgrad_stream if self.overlap_wgrad else None,  # (a vector of the graph's ring: rewritten eight replays later)
+                                                 after_loss=mon.after_loss if mon is not None else None)
+        if mon is not None:
+            self.last_accuracies = mon.accuracies
         self._ema_version += 1  # (the replay ran votenet_ema_update: inference_bn() must not serve a table built before it)
         self._backward_levels_pass(tape, grads)
         return out
@@ -921,6 +930,26 @@ class VoteNetHotPath:
         self.__dict__.setdefault("_prefetched", {}).clear()
         self._geometry_current = None
 
+    # ---- training summaries on the device (monitors.py): off unless asked for --------------------------------------------------
+    monitors = None          # a monitors.Monitors while enable_monitors is in force
+    last_accuracies = None   # (2,) f32 on the device: obj_accuracy, sem_accuracy of the last monitored step
+
+    def enable_monitors(self, window=100, tensors_every=0):
+        """From now on every train_step(..., gt=...) runs one more launch behind its loss launch: obj_accuracy / sem_accuracy of the step
+        (model.py:164-166, 215-216) into self.last_accuracies and, with the total cost, into a device ring of `window` rows (run.py:127);
+        every tensors_every-th step (0: never) two more behind the optimizer: rms, extrema and histogram of every parameter and gradient
+        tensor (model.py:236, 250).  Nothing is read back until self.monitors.read().  A step with fixed cotangents (cot=) has no loss
+        and is not monitored.  -> the Monitors object."""
+        from . import monitors
+        self.monitors = monitors.Monitors(self, window, tensors_every)
+        self.last_accuracies = None
+        return self.monitors
+
+    def disable_monitors(self):
+        """Back to the launches of an unmonitored step (the default)."""
+        self.monitors = None
+        self.last_accuracies = None
+
     def init_optimizer(self, lr=LEARNING_RATE):
         s = self.store
         base = s.flat.data_ptr()
@@ -988,6 +1017,8 @@ class VoteNetHotPath:
                 if gt is not None:
                     from . import loss as VL
                     self.last_losses, cot = VL.votenet_loss(out, gt)
+                    if self.monitors is not None:
+                        self.last_accuracies = self.monitors.after_loss(out, gt, self.last_losses)
                 self._gsync.begin()
                 if PREFETCH_AFTER >= 5:  # the next batch's geometry chain under the BACKWARD pass
                     for nx in (next_x if isinstance(next_x, (list, tuple)) else ([next_x] if next_x is not None else [])):
@@ -1000,4 +1031,6 @@ class VoteNetHotPath:
         self._step += 1
         M.clip_adam(self._seg, self._sumsq, self.store.flat, self.store.grad, self._m, self._v, self._lr, self._step,
                     grad_scale=gscale)
+        if self.monitors is not None:
+            self.monitors.after_optimizer(self, gscale, 0.5)  # (0.5: clip_adam's clip_by_average_norm, model.py:249)
         return out
