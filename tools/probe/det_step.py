@@ -40,7 +40,7 @@ for net in nets:
         if m + "_before" in SYNC:
             _sync_before(getattr(net, m), "backward")
 if "handover" in SYNC:
-    _sync_after(P, "_hand_over")
+    _sync_after(P.WGRAD, "hand_over")
 if "step" in SYNC:
     for net in nets:
         _sync_after(net, "train_step")

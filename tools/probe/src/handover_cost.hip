@@ -1,7 +1,7 @@
 // probe (round 5): what does handing work to a second stream cost the MAIN queue, by mechanism?  A chain of small dependent kernels
 // on stream A; after every kernel a second stream B is told "A has got this far" and runs a small kernel of its own:
 //   0  nothing between the links (the chain alone)
-//   1  hipEventRecord(A) + hipStreamWaitEvent(B) + kernel on B            (what pointnet2._hand_over does, torch events)
+//   1  hipEventRecord(A) + hipStreamWaitEvent(B) + kernel on B            (what pointnet2.WgradLane.hand_over does, torch events)
 //   2  the same with events created hipEventDisableTiming
 //   3  hipStreamWriteValue32(A, flag, k) + hipStreamWaitValue32(B, flag, k, >=) + kernel on B   (signal memory, no event)
 //   4  no synchronisation at all, kernel on B every link                  (what B's own work costs A: contention only)

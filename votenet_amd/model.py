@@ -170,8 +170,6 @@ class StretchGraph:
         gc.collect()
         pool = torch.cuda.graph_pool_handle()
         keep, defer = [], []
-        prev = (P.CAPTURE_KEEP, P.CAPTURE_DEFER, P.WGRAD_STREAM)
-        P.CAPTURE_KEEP, P.CAPTURE_DEFER = keep, (defer if STRETCH_SEGMENTS else None)
         cur = [None]
 
         def begin():
@@ -205,7 +203,7 @@ class StretchGraph:
             begin()
             return losses, cot
         cs.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(cs):
+        with torch.cuda.stream(cs), P.WGRAD.capturing(keep, defer if STRETCH_SEGMENTS else None):
             begin()
             try:
                 self.arena.zero_()
@@ -214,7 +212,6 @@ class StretchGraph:
             finally:
                 if cur[0] is not None:
                     end()
-                P.CAPTURE_KEEP, P.CAPTURE_DEFER, P.WGRAD_STREAM = prev
         self.arena_used = pa.used
         self.keep = keep
 
@@ -228,9 +225,7 @@ class StretchGraph:
         monitors' accuracy launch: a launch between two segments like the loss, no graph is captured again or gets a node)."""
         from . import loss as VL
         self.copy_inputs(ins)
-        prev = P.WGRAD_STREAM
-        P.WGRAD_STREAM = wgrad_stream
-        try:
+        with P.WGRAD.on(wgrad_stream):
             for i, (graph, thunks) in enumerate(self.segments):
                 if i == self.loss_at:
                     # the loss launch is not captured and no captured kernel reads the 12 losses: each replay writes them into the next
@@ -241,12 +236,10 @@ class StretchGraph:
                         after_loss(self.out, gt, losses)
                 graph.replay()
                 if thunks and wgrad_stream is not None:
-                    P._hand_over([f for f, _ in thunks], ())  # (their tensors live in the graphs' pool: nothing for the allocator to track)
+                    P.WGRAD.hand_over([f for f, _ in thunks])  # (their tensors live in the graphs' pool: nothing for the allocator to track)
                 else:
                     for f, _ in thunks:
                         f()
-        finally:
-            P.WGRAD_STREAM = prev
         self.replays += 1
         return _StretchOutputs(self.out, self), losses, self.grads
 
@@ -274,6 +267,12 @@ class VoteNetHotPath:
         s.materialize(seed)
         s.enable_split(SPLIT_BF16)  # forward() refreshes the images at its start, refresh_transposes() those of the copies
 
+    def _wgrad_side(self):
+        """The weight-gradient stream; None with overlap_wgrad off: weight gradients then run on the chain's own stream."""
+        if self.overlap_wgrad and self._wgrad_stream is None:
+            self._wgrad_stream = torch.cuda.Stream(device=self.device, priority=WGRAD_PRIORITY)
+        return self._wgrad_stream if self.overlap_wgrad else None
+
     # ---- forward pieces -------------------------------------------------------------
     def _side_stream(self):
         if getattr(self, "_side", None) is None:
@@ -299,7 +298,7 @@ class VoteNetHotPath:
             ev["fp"].record()
 
     @staticmethod
-    def _hand_over(g, main):
+    def _record_on_main(g, main):
         for v in g.values():  # tensors born on the side stream are consumed on the main stream
             for t in (v if isinstance(v, tuple) else (v,)):
                 for u in getattr(t, "tensors", tuple)() if not isinstance(t, torch.Tensor) else ():  # mlp.HalfLayout
@@ -323,7 +322,7 @@ class VoteNetHotPath:
         with torch.cuda.stream(side):
             side.wait_event(start)
             self._geometry_chain(x, g, ev, ("sa2", "sa3", "sa4"))
-        self._hand_over(g, main)
+        self._record_on_main(g, main)
         return g, ev
 
     def prefetch_geometry(self, next_x):
@@ -356,7 +355,7 @@ class VoteNetHotPath:
             else:
                 self._geometry_chain(next_x, g, ev, ("sa1", "sa2", "sa3", "sa4"))
         if gg is None:
-            self._hand_over(g, main)
+            self._record_on_main(g, main)
         while len(pool) >= (GEOMETRY_RING - 1 if gg is not None else 4):  # never picked up: drop the oldest
             pool.pop(next(iter(pool)))
         pool[id(next_x)] = (next_x, next_x._version, g, ev, gg, gg.generation if gg is not None else 0)
@@ -665,15 +664,11 @@ class VoteNetHotPath:
         """Reverse sweep over the tape of forward(); parameter gradients accumulate into store.grad."""
         self.check_tape(tape)
         M.arena_begin(self.device)  # one fill for all BatchNorm-backward reductions of the pass
-        if self.overlap_wgrad:
-            if self._wgrad_stream is None:
-                self._wgrad_stream = torch.cuda.Stream(device=self.device, priority=WGRAD_PRIORITY)
-            P.WGRAD_STREAM = self._wgrad_stream
         try:
-            self._backward(tape, cot)
-            P.wgrad_join()  # the optimizer (and the next pass's arena fill) come after every weight gradient
+            with P.WGRAD.on(self._wgrad_side()):
+                self._backward(tape, cot)
+                P.wgrad_join()  # the optimizer (and the next pass's arena fill) come after every weight gradient
         finally:
-            P.WGRAD_STREAM = None
             M.arena_end()
 
     @staticmethod
@@ -743,22 +738,14 @@ class VoteNetHotPath:
         # every gradient of sa3 ... proposal (the tail of the flat bucket) is enqueued: its all-reduce runs on the
         # communication stream underneath the backward pass of sa2 and sa1 (dp.GradSync; a no-op on one GPU)
         if getattr(self, "_gsync", None) is not None:
-            self._gsync.start_tail([P.WGRAD_STREAM])
+            self._gsync.start_tail([P.WGRAD.stream])
         # inline_wgrad_tail (experiment, default off): the weight gradients of the two largest modules on the MAIN stream -- by the time
         # their backward runs the next batch's sampling kernel has finished, and pairs of GPU-filling kernels gain nothing from two streams
-        keep_stream = P.WGRAD_STREAM
-        if getattr(self, "inline_wgrad_tail", INLINE_WGRAD_TAIL):
-            P.WGRAD_STREAM = None
-        try:
+        with P.WGRAD.on(None if getattr(self, "inline_wgrad_tail", INLINE_WGRAD_TAIL) else P.WGRAD.stream):
             g1, _ = self.sa2.backward(sa2, d_l2p)
             P.wgrad_flush()
-            P.wgrad_fine(True)  # the last module: nothing follows to hide its weight gradients under, so they start layer by layer
-            try:
+            with P.WGRAD.fine():  # the last module: nothing follows to hide its weight gradients under, so they start layer by layer
                 self.sa1.backward(sa1, g1, need_feat_grad=False)
-            finally:
-                P.wgrad_fine(False)
-        finally:
-            P.WGRAD_STREAM = keep_stream
 
     # ---- the static stretch of a train step as one HIP graph (StretchGraph) -------------------------------------------------------
     def _stretch_eligible(self, x, cot, gt):
@@ -800,13 +787,10 @@ class VoteNetHotPath:
         losses, cot = loss_hook(out) if loss_hook is not None else VL.votenet_loss(out, gt)
         if loss_hook is None and self.monitors is not None:
             self.last_accuracies = self.monitors.after_loss(out, gt, losses)
-        P.WGRAD_STREAM = wgrad_stream
-        try:
+        with P.WGRAD.on(wgrad_stream):
             grads = self._head_backward(tail, cot, cut=cut)
             if cut is None:
                 P.wgrad_join()
-        finally:
-            P.WGRAD_STREAM = None
         self._stretch_tail = tail  # (kept: the records own the tensors the captured kernels read)
         return out, losses, grads
 
@@ -839,11 +823,9 @@ class VoteNetHotPath:
                 a = M._StatsArena
                 off0, want0 = a.off, a.want32
                 self.check_tape(tape)
-                if self.overlap_wgrad and self._wgrad_stream is None:
-                    self._wgrad_stream = torch.cuda.Stream(device=self.device, priority=WGRAD_PRIORITY)
                 # (launch by launch on the live inputs: seeds_xyz would alias sa2's centres inside a GeometryGraph buffer that a later
                 # prefetch overwrites -- handed out as a copy, as forward() does)
-                out, self.last_losses, grads = self._stretch_body(ins, tape, self._wgrad_stream if self.overlap_wgrad else None, gt=gt,
+                out, self.last_losses, grads = self._stretch_body(ins, tape, self._wgrad_side(), gt=gt,
                                                                   copy_seeds=getattr(self, "_geometry_current", None) is not None)
                 self._stretch_demand[dkey] = (a.off - off0, a.want32 - want0)
                 self._backward_levels_pass(tape, grads)
@@ -854,10 +836,8 @@ class VoteNetHotPath:
         self._stretch_clock = getattr(self, "_stretch_clock", 0) + 1
         sg.last_used = self._stretch_clock
         self.store._fresh_wait()
-        if self.overlap_wgrad and self._wgrad_stream is None:
-            self._wgrad_stream = torch.cuda.Stream(device=self.device, priority=WGRAD_PRIORITY)
         mon = self.monitors
-        out, self.last_losses, grads = sg.replay(ins, gt, self._wgrad_stream if self.overlap_wgrad else None,  # (a vector of the graph's ring: rewritten eight replays later)
+        out, self.last_losses, grads = sg.replay(ins, gt, self._wgrad_side(),  # (a vector of the graph's ring: rewritten eight replays later)
                                                  after_loss=mon.after_loss if mon is not None else None)
         if mon is not None:
             self.last_accuracies = mon.accuracies
@@ -871,7 +851,7 @@ class VoteNetHotPath:
         (arg-max scatter, dense input gradient, narrow input gradient: 0.31 ms alone) and the weight-gradient stream (Gram matrix, sparse
         gather, narrow weight gradient: 0.28 ms alone) run beside each other at 0.45 ms: sa1's matrix ahead takes a third of that
         stream's tail away and runs beside sa4's / sa3's smaller kernels instead."""
-        if not GRAM_EARLY or M.DETERMINISTIC or P.WGRAD_STREAM is None:
+        if not GRAM_EARLY or M.DETERMINISTIC or P.WGRAD.stream is None:
             return
         todo = [levels[n]["recs"][-1] for n in GRAM_EARLY if n in levels]
         todo = [r for r in todo if r.get("gram_form") and r.get("in_affine") is not None and "gram_ahead" not in r]
@@ -893,32 +873,22 @@ class VoteNetHotPath:
         todo = [t["recs"][-1] for t in tape[:4] if t.get("op") == "sa" and t["recs"][-1].get("gram_form") and t["recs"][-1].get("in_affine") is not None]
         if not todo:
             return
-        if self._wgrad_stream is None:
-            self._wgrad_stream = torch.cuda.Stream(device=self.device, priority=WGRAD_PRIORITY)
-        prev = P.WGRAD_STREAM
-        P.WGRAD_STREAM = self._wgrad_stream
 
         def run():
             for r in todo:
                 r["gram_ahead"] = M.gram(r["x"], r["in_affine"][:2], r["in_relu"], half=r.get("half"))
-        try:
+        with P.WGRAD.on(self._wgrad_side()):
             P.on_wgrad_stream(run, *[r["x"] for r in todo])
-        finally:
-            P.WGRAD_STREAM = prev
 
     def _backward_levels_pass(self, tape, grads):
         """backward() for the four levels only (the head's gradients given)."""
         self.check_tape(tape)
         M.arena_begin(self.device)
-        if self.overlap_wgrad:
-            if self._wgrad_stream is None:
-                self._wgrad_stream = torch.cuda.Stream(device=self.device, priority=WGRAD_PRIORITY)
-            P.WGRAD_STREAM = self._wgrad_stream
         try:
-            self._levels_backward(tape[:4], *grads)
-            P.wgrad_join()
+            with P.WGRAD.on(self._wgrad_side()):
+                self._levels_backward(tape[:4], *grads)
+                P.wgrad_join()
         finally:
-            P.WGRAD_STREAM = None
             M.arena_end()
 
     def drop_graphs(self):

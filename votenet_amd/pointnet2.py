@@ -494,115 +494,143 @@ def mlp_chain_forward(layers, rows, first, tape, pool_k=0, keep_z=True):
     return z, pend
 
 
-# Weight gradients hang off the backward chain (reduce -> coef -> dgrad -> reduce ...): nothing downstream needs them before
-# the optimizer.  When the owner sets WGRAD_STREAM (a second HIP stream) they are launched there, concurrently with the input
-# gradient of the same layer; wgrad_join() makes the current stream wait for them.  Tensors a side-stream kernel reads are
-# tagged with record_stream so the caching allocator does not hand their memory out early.
-WGRAD_STREAM = None
-_wgrad_pending = False
-
-
-# Every hand-over to WGRAD_STREAM costs an event (a barrier packet in the main queue: a few microseconds in which the chain
-# stands still).  WGRAD_BATCH = True collects the weight-gradient launches of a module and hands them over together at
-# wgrad_flush() (one event per module: its weight gradients then run underneath the NEXT module's chain); modules named in
-# WGRAD_FINE (the last one of the backward pass, whose weight gradients have nothing after them to hide under) keep one
-# hand-over per launch.
+# Every hand-over to the weight-gradient stream costs an event (a barrier packet in the main queue: a few microseconds in which the
+# chain stands still).  WGRAD_BATCH = True collects the weight-gradient launches of a module and hands them over together at
+# wgrad_flush() (one event per module: its weight gradients then run underneath the NEXT module's chain); inside WGRAD.fine() (the
+# last module of the backward pass, whose weight gradients have nothing after them to hide under) every launch keeps its own hand-over.
 WGRAD_BATCH = False  # measured (tools/ab_step.py, same box): 7.81 ms per step per launch vs 7.99 ms batched per module -- where the weight gradients run matters more than the ~30 events saved
-_wgrad_deferred = []
-_wgrad_fine = False
 
 
-def wgrad_fine(on):
-    global _wgrad_fine
-    _wgrad_fine = bool(on)
+class _LaneScope:
+    """`with` scope over attributes of the lane: sets them on entry and puts back exactly what it found on exit, also when the body
+    raises.  An exception that leaves the OUTERMOST stream scope also drops what the failed pass left behind: deferred thunks (they
+    close over a dead step's tensors) and the pending flag (the next join would wait on a stream nobody used)."""
+
+    def __init__(self, lane, **values):
+        self.lane, self.values = lane, values
+
+    def __enter__(self):
+        self.found = {k: getattr(self.lane, k) for k in self.values}
+        self.lane.__dict__.update(self.values)
+        self.lane._stream_scopes += "stream" in self.values
+
+    def __exit__(self, exc_type, exc, tb):
+        lane = self.lane
+        lane.__dict__.update(self.found)
+        if "stream" in self.values:
+            lane._stream_scopes -= 1
+            if exc_type is not None and not lane._stream_scopes:
+                lane._deferred.clear()
+                lane._pending = False
 
 
-# hand-over events, reused round-robin: a wait that has been enqueued keeps the record it saw, so an event may be recorded again as
-# soon as its wait is in the queue (creating and destroying a HIP event per hand-over was ~3 us of host time, 25 times per step)
-_EVENTS = []
-_event_turn = 0
+class WgradLane:
+    """Weight gradients hang off the backward chain (reduce -> coef -> dgrad -> reduce ...): nothing downstream needs them before the
+    optimizer.  Inside `with WGRAD.on(stream)` (a second HIP stream) they are launched there, concurrently with the input gradient of
+    the same layer; join() makes the current stream wait for them.  Tensors a side-stream kernel reads are tagged with record_stream so
+    the caching allocator does not hand their memory out early.  One lane per process (WGRAD below); the scopes on() / fine() /
+    capturing() are the only way its state changes from outside."""
 
+    def __init__(self):
+        self.stream = None  # where weight gradients go; None: inline on the current stream
+        self._stream_scopes = 0
+        self._pending = False  # something was handed over since the last join()
+        self._deferred = []  # WGRAD_BATCH: (thunk, tensors) waiting for the next flush()
+        self._fine = False
+        # hand-over events, reused round-robin: a wait that has been enqueued keeps the record it saw, so an event may be recorded again
+        # as soon as its wait is in the queue (creating and destroying a HIP event per hand-over was ~3 us of host time, 25 times per step)
+        self._events, self._event_turn = [], 0
+        # A list while a stretch of the step is being captured into a HIP graph (model.StretchGraph): hand-overs then use fresh events (a
+        # captured record must not be mixed with the eager life of a pooled event) and, instead of record_stream -- whose bookkeeping
+        # the caching allocator defers during a capture -- every tensor a side-branch kernel reads is kept alive until the capture ends, so
+        # that the graph's private pool cannot hand its memory to a later allocation of the main branch.
+        self._keep = None
+        # A list while a stretch is being captured in SEGMENTS (model.StretchGraph): a weight-gradient launch is then not captured at all
+        # but recorded as (thunk, tensors) -- the owner replays the segment's graph and runs its thunks on the weight-gradient stream
+        # afterwards, launch by launch, beside the next segment.  (Captured on a side branch of the graph instead, the branch's internal
+        # stream shared a hardware queue with the geometry prefetch: the whole graph then waited for the 1.6 ms sampling kernel -- 3.94 ->
+        # 5.8 ms per step.)
+        self._defer = None
 
-# Set to a list while a stretch of the step is being captured into a HIP graph (model.StretchGraph): hand-overs then use fresh events
-# (a captured record must not be mixed with the eager life of a pooled event) and, instead of record_stream -- whose bookkeeping
-# the caching allocator defers during a capture -- every tensor a side-branch kernel reads is kept alive until the capture ends, so that
-# the graph's private pool cannot hand its memory to a later allocation of the main branch.
-CAPTURE_KEEP = None
-# A list while a stretch is being captured in SEGMENTS (model.StretchGraph): a weight-gradient launch is then not captured at all but
-# recorded as (thunk, tensors) -- the owner replays the segment's graph and runs its thunks on the weight-gradient stream afterwards,
-# launch by launch, beside the next segment.  (Captured on a side branch of the graph instead, the branch's internal stream shared a
-# hardware queue with the geometry prefetch: the whole graph then waited for the 1.6 ms sampling kernel -- 3.94 -> 5.8 ms per step.)
-CAPTURE_DEFER = None
+    def on(self, stream):
+        """Scope: weight gradients go to `stream`, or run inline when it is None."""
+        return _LaneScope(self, stream=stream)
 
+    def fine(self):
+        """Scope: one hand-over per launch, whatever WGRAD_BATCH says."""
+        return _LaneScope(self, _fine=True)
 
-def _pooled_event():
-    global _event_turn
-    if CAPTURE_KEEP is not None:
-        return torch.cuda.Event()
-    if len(_EVENTS) < 64:
-        _EVENTS.append(torch.cuda.Event())
-        return _EVENTS[-1]
-    _event_turn = (_event_turn + 1) % 64
-    return _EVENTS[_event_turn]
+    def capturing(self, keep, defer=None):
+        """Scope: a graph capture is under way -- `keep` collects what the side-stream kernels read, `defer` (when a list) the launches."""
+        return _LaneScope(self, _keep=keep, _defer=defer)
 
+    def _event(self):
+        if self._keep is not None:
+            return torch.cuda.Event()
+        if len(self._events) < 64:
+            self._events.append(torch.cuda.Event())
+            return self._events[-1]
+        self._event_turn = (self._event_turn + 1) % 64
+        return self._events[self._event_turn]
 
-def _hand_over(thunks, tensors):
-    global _wgrad_pending
-    main = torch.cuda.current_stream()
-    ev = _pooled_event()
-    ev.record(main)
-    WGRAD_STREAM.wait_event(ev)
-    if CAPTURE_KEEP is not None:
-        CAPTURE_KEEP.extend(tensors)
-        CAPTURE_KEEP.append(thunks)  # (the closures hold what the kernels they launch read)
-    else:
-        for t in tensors:
-            t.record_stream(WGRAD_STREAM)
-    # set_stream both ways instead of the `with torch.cuda.stream(...)` context: the context manager looks the current stream up
-    # twice on entry and exit (~40 us per hand-over on the host, ~24 hand-overs per step)
-    torch.cuda.set_stream(WGRAD_STREAM)
-    try:
-        for f in thunks:
-            f()
-    finally:
-        torch.cuda.set_stream(main)
-    _wgrad_pending = True
-
-
-def on_wgrad_stream(fn, *tensors):
-    """Run fn() -- launches of weight-gradient kernels reading `tensors` -- on WGRAD_STREAM after everything issued so far on the
-    current stream (now, or together with the module's other weight gradients at the next wgrad_flush()); on the current
-    stream when there is no weight-gradient stream."""
-    tensors = [t for t in tensors if isinstance(t, torch.Tensor)]
-    if CAPTURE_DEFER is not None:
-        CAPTURE_DEFER.append((fn, tensors))
-    elif WGRAD_STREAM is None:
-        fn()
-    elif WGRAD_BATCH and not _wgrad_fine:
-        _wgrad_deferred.append((fn, tensors))
-    else:
-        _hand_over([fn], tensors)
-
-
-def wgrad_flush():
-    if _wgrad_deferred:
-        if WGRAD_STREAM is None:
-            for f, _ in _wgrad_deferred:
-                f()
+    def hand_over(self, thunks, tensors=()):
+        """Run the thunks on the lane's stream behind everything issued so far on the current one.  tensors: what their kernels read
+        (none when it lives in a graph's pool: nothing for the allocator to track)."""
+        main = torch.cuda.current_stream()
+        ev = self._event()
+        ev.record(main)
+        self.stream.wait_event(ev)
+        if self._keep is not None:
+            self._keep.extend(tensors)
+            self._keep.append(thunks)  # (the closures hold what the kernels they launch read)
         else:
-            _hand_over([f for f, _ in _wgrad_deferred], [t for _, ts in _wgrad_deferred for t in ts])
-        _wgrad_deferred.clear()
+            for t in tensors:
+                t.record_stream(self.stream)
+        # set_stream both ways instead of the `with torch.cuda.stream(...)` context: the context manager looks the current stream up
+        # twice on entry and exit (~40 us per hand-over on the host, ~24 hand-overs per step)
+        torch.cuda.set_stream(self.stream)
+        try:
+            for f in thunks:
+                f()
+        finally:
+            torch.cuda.set_stream(main)
+        self._pending = True
+
+    def run(self, fn, *tensors):
+        """Run fn() -- launches of weight-gradient kernels reading `tensors` -- on the lane's stream after everything issued so far on
+        the current stream (now, or together with the module's other weight gradients at the next flush()); on the current stream when
+        there is no weight-gradient stream."""
+        tensors = [t for t in tensors if isinstance(t, torch.Tensor)]
+        if self._defer is not None:
+            self._defer.append((fn, tensors))
+        elif self.stream is None:
+            fn()
+        elif WGRAD_BATCH and not self._fine:
+            self._deferred.append((fn, tensors))
+        else:
+            self.hand_over([fn], tensors)
+
+    def flush(self):
+        if self._deferred:
+            if self.stream is None:
+                for f, _ in self._deferred:
+                    f()
+            else:
+                self.hand_over([f for f, _ in self._deferred], [t for _, ts in self._deferred for t in ts])
+            self._deferred.clear()
+
+    def join(self):
+        """The current stream waits for every weight-gradient kernel launched on the lane's stream so far."""
+        self.flush()
+        if self.stream is not None and self._pending:
+            ev = self._event()
+            ev.record(self.stream)
+            torch.cuda.current_stream().wait_event(ev)
+            self._pending = False
 
 
-def wgrad_join():
-    """The current stream waits for every weight-gradient kernel launched on WGRAD_STREAM so far."""
-    global _wgrad_pending
-    wgrad_flush()
-    if WGRAD_STREAM is not None and _wgrad_pending:
-        ev = _pooled_event()
-        ev.record(WGRAD_STREAM)
-        torch.cuda.current_stream().wait_event(ev)
-        _wgrad_pending = False
+WGRAD = WgradLane()
+on_wgrad_stream, wgrad_flush, wgrad_join = WGRAD.run, WGRAD.flush, WGRAD.join
 
 
 def check_bn_block(rec):
