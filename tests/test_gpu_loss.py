@@ -111,3 +111,189 @@ def test_decode_boxes_vs_oracle(hiplib, dev):
     assert (scores.cpu().numpy() == es).all()
     b = boxes.cpu().numpy()
     assert np.allclose(b[:, :, :4, 1], b[:, :, :1, 1], atol=1e-6) and (b[:, :, 0, 1] >= b[:, :, 4, 1]).all()
+
+
+# ---------------------------------------------------------------- every role split, tie and threshold edge of votenet_loss_kernel
+from loss_cases import case_ids, load_case, reference  # noqa: E402
+
+
+def _to_dev(a, dev):
+    return torch.from_numpy(a.copy()).to(dev)
+
+
+def run_case(dev, cid, wide=0):
+    """The case on the device: through loss.votenet_loss, or, where the case brings thresholds of its own, through the C ABI the way
+    loss.py calls it.  wide: proposals_output as the first columns of a tensor that many columns wide (the pitched entry)."""
+    from votenet_amd import _lib as L
+    from votenet_amd import loss as VL
+    seeds, votes, prop, out, gt, kw = load_case(cid)
+    g = VL.gt_to_device({k: x.copy() for k, x in gt.items()}, dev)
+    pout = _to_dev(out, dev)
+    if wide:
+        buf = torch.full(out.shape[:2] + (wide,), 1e30, device=dev)
+        buf[:, :, :out.shape[2]] = pout
+        pout = buf[:, :, :out.shape[2]]
+        assert not pout.is_contiguous()
+    o = dict(seeds_xyz=_to_dev(seeds, dev), votes_xyz=_to_dev(votes, dev), proposals_xyz=_to_dev(prop, dev), proposals_output=pout)
+    if "pos_thr" not in kw:
+        return VL.votenet_loss(o, g, nh=kw["nh"], ns=kw["ns"], nc=kw["nc"])
+    assert not wide
+    b, n, p, bb = seeds.shape[0], seeds.shape[1], prop.shape[1], gt["bboxes_xyz"].shape[1]
+    losses = torch.empty(12, dtype=torch.float32, device=dev)
+    cot = dict(votes_xyz=torch.zeros_like(o["votes_xyz"]), proposals_xyz=torch.zeros_like(o["proposals_xyz"]),
+               proposals_output=torch.zeros_like(pout))
+    ws = torch.zeros(int(L.lib().votenet_loss_workspace_floats(b)), dtype=torch.float32, device=dev)
+    L.check(L.lib().votenet_loss_pitched(b, n, p, bb, kw["nh"], kw["ns"], kw["nc"], L.ptr(o["seeds_xyz"]), L.ptr(o["votes_xyz"]),
+                                         L.ptr(o["proposals_xyz"]), L.ptr(pout), pout.stride(1), L.ptr(g["bboxes_xyz"]),
+                                         L.ptr(g["bboxes_lwh"]), L.ptr(g["bboxes_roty"]), L.ptr(g["semantic_labels"]),
+                                         L.ptr(g["heading_labels"]), L.ptr(g["heading_residuals"]), L.ptr(g["size_labels"]),
+                                         L.ptr(g["size_residuals"]), kw["pos_thr"], kw["neg_thr"], L.ptr(losses), L.ptr(cot["votes_xyz"]),
+                                         L.ptr(cot["proposals_xyz"]), L.ptr(cot["proposals_output"]), L.ptr(ws), L.stream_ptr()))
+    return losses, cot
+
+
+@pytest.mark.parametrize("cid", case_ids())
+def test_loss_role_splits_ties_and_thresholds(hiplib, dev, cid):
+    """The assertions of test_loss_values_and_cotangents (values and autograd cotangents of the float64 restatement at 1e-5 relative,
+    floors 1.0 and 1e-3; a second run bit-identical) at every shape where votenet_loss_kernel splits its waves differently
+    (loss_cases.SHAPES) and on the hand-made decisions (loss_ref.HAND_CASES), plus: a cotangent element whose float64 gradient is exactly
+    zero (dead zone, seed outside every box, residual slot of another class, the loser of a tie) is bit-zero on the device.
+    Measured on an MI355X: profiles/r07_loss_case_errors.txt."""
+    losses, cot = run_case(dev, cid)
+    r, g = reference(cid)
+    got = dict(zip(NAMES + ["n_pos", "n_neg"], losses.cpu().tolist()))
+    verr = {k: abs(got[k] - float(r[k])) / max(1.0, abs(float(r[k]))) for k in NAMES}
+    cerr, stray = {}, {}
+    for name, ref in g.items():
+        d = cot[name].cpu()
+        cerr[name] = float((d.double() - ref).abs().max()) / max(1e-3, float(ref.abs().max()))
+        stray[name] = int((d.contiguous().view(torch.int32)[ref == 0] != 0).sum())
+    print("loss_case %s n_pos=%d/%d n_neg=%d/%d value=%.2e (%s) votes_xyz=%.2e proposals_xyz=%.2e proposals_output=%.2e nonzero_where_ref_zero=%d"
+          % (cid, got["n_pos"], r["n_pos"], got["n_neg"], r["n_neg"], max(verr.values()), max(verr, key=verr.get), cerr["votes_xyz"],
+             cerr["proposals_xyz"], cerr["proposals_output"], sum(stray.values())))
+    assert int(got["n_pos"]) == r["n_pos"] > 0 and int(got["n_neg"]) == r["n_neg"] > 0
+    for k in NAMES:
+        assert verr[k] <= 1e-5, (k, got[k], float(r[k]))
+    for name in g:
+        assert cerr[name] <= 1e-5, (name, cerr[name])
+        assert stray[name] == 0, name
+    losses2, cot2 = run_case(dev, cid)
+    assert torch.equal(losses, losses2)
+    for name in g:
+        assert torch.equal(cot[name], cot2[name]), name
+
+
+def test_loss_pitched_entry_on_the_not_early_path(hiplib, dev):
+    """P = 961 (every wave owns proposals): the column slice of a wider tensor gives the contiguous copy's result bit for bit."""
+    ref_l, ref_c = run_case(dev, "shape-p961")
+    got_l, got_c = run_case(dev, "shape-p961", wide=128)
+    assert torch.equal(got_l, ref_l)
+    for k in ref_c:
+        assert torch.equal(got_c[k], ref_c[k]) and got_c[k].is_contiguous(), k
+
+
+def test_loss_rejects_shapes_beyond_its_tables(hiplib, dev):
+    """257 boxes (LOSS_MAXBOX = 256) and nh = 33 (LOSS_MAXC = 32) raise before any launch, and the next valid call is unaffected."""
+    from votenet_amd import InvalidArgumentError
+    from votenet_amd import loss as VL
+    before_l, before_c = run_case(dev, "shape-p63")
+    for shape in (dict(bb=257), dict(nh=33)):
+        seeds, votes, prop, out, gt = loss_ref.random_case(8, b=2, n=16, p=16, **shape)
+        o = dict(seeds_xyz=_to_dev(seeds, dev), votes_xyz=_to_dev(votes, dev), proposals_xyz=_to_dev(prop, dev),
+                 proposals_output=_to_dev(out, dev))
+        with pytest.raises(InvalidArgumentError):
+            VL.votenet_loss(o, VL.gt_to_device(gt, dev), nh=shape.get("nh", 12))
+    after_l, after_c = run_case(dev, "shape-p63")
+    assert torch.equal(before_l, after_l)
+    for k in before_c:
+        assert torch.equal(before_c[k], after_c[k]), k
+
+
+@pytest.mark.parametrize("bad", [float("nan"), float("inf")], ids=["nan", "inf"])
+def test_loss_nonfinite_proposals_stay_inside_the_buffers(hiplib, dev, bad):
+    """A diverged run: every proposal centre of scene 0 is NaN (or +inf), scene 1 is ordinary.  No proposal is then at a distance below
+    infinity from any box, and the dual term's arg-min keeps its sentinel index: it used to be turned into an address.  It falls back to
+    proposal 0, as tf.argmin over all-NaN / all-inf distances: total_cost and center_loss are NaN for NaN centres (+inf for +inf centres:
+    Huber of an infinite error is +inf and nothing turns it into NaN, in the float64 restatement as on the device), the vote loss and the
+    votes' cotangents are those of the run with scene 0 finite, bit for bit, and guard bands around the output buffers are untouched."""
+    from votenet_amd import _lib as L
+    from votenet_amd import loss as VL
+    seeds, votes, prop, out, gt = loss_ref.random_case(9, b=2, n=64, p=70, bb=6)
+    g = VL.gt_to_device(gt, dev)
+    o = dict(seeds_xyz=_to_dev(seeds, dev), votes_xyz=_to_dev(votes, dev), proposals_xyz=_to_dev(prop, dev), proposals_output=_to_dev(out, dev))
+    fin_l, fin_c = VL.votenet_loss(o, g)
+    broken = prop.copy()
+    broken[0] = bad
+    o["proposals_xyz"] = _to_dev(broken, dev)
+    GUARD, SENTINEL = 1024, -7777.0
+    need = votes.size + prop.size + out.size + int(L.lib().votenet_loss_workspace_floats(2))
+    big = torch.full((GUARD + need + GUARD,), SENTINEL, device=dev)
+    bigl = torch.full((GUARD + 12 + GUARD,), SENTINEL, device=dev)
+    flat, losses = big[GUARD:GUARD + need], bigl[GUARD:GUARD + 12]
+    flat.zero_()
+    got_l, got_c = VL.votenet_loss(o, g, buffers=(losses, flat))
+    torch.cuda.synchronize()
+    assert got_l.data_ptr() == losses.data_ptr() and got_c["votes_xyz"].data_ptr() == flat.data_ptr()
+    for t, n in ((big, need), (bigl, 12)):
+        assert (t[:GUARD] == SENTINEL).all() and (t[GUARD + n:] == SENTINEL).all()
+    l, f = got_l.cpu().numpy(), fin_l.cpu().numpy()
+    T = lambda a: torch.from_numpy(a).double() if a.dtype == np.float32 else torch.from_numpy(a)
+    r = loss_ref.votenet_loss(T(seeds), T(votes), T(broken), T(out), {k: T(x) for k, x in gt.items()})
+    want = np.nan if np.isnan(bad) else np.inf
+    for k in ("total_cost", "center_loss"):
+        assert np.array_equal(float(r[k]), want, equal_nan=True) and np.array_equal(l[NAMES.index(k)], want, equal_nan=True), (k, l)
+    assert (l[10], l[11]) == (r["n_pos"], r["n_neg"]) and r["n_pos"] > 0
+    for i, k in enumerate(NAMES):  # the terms the broken scene cannot reach keep the bar of the other tests
+        if np.isfinite(float(r[k])):
+            assert abs(l[i] - float(r[k])) <= 1e-5 * max(1.0, abs(float(r[k]))), (k, l[i], float(r[k]))
+    assert np.isfinite(l[1]) and l[1] == f[1]
+    assert torch.equal(got_c["votes_xyz"], fin_c["votes_xyz"]) and bool((got_c["votes_xyz"][1] != 0).any())
+
+
+@pytest.mark.parametrize("b,p,nh", [(3, 85, 12), (2, 128, 12), (1, 257, 12), (1, 257, 1)])
+def test_decode_boxes_hand_cases(hiplib, dev, b, p, nh):
+    """decode_boxes_kernel where a draw of Gaussians never goes: 2 * bin + residual below zero, at 2 * nh exactly and above it (both sides
+    of floormod), a size residual of -1 and below (the 1e-6 floor), exact ties in the heading and the size arg-max (the first wins: the
+    tied bins carry different residuals), nh = 1, and b * P = 255, 256, 257 proposals on blocks of 256 (the cases sit in the first rows
+    and again in the last one).  Bar: that of test_decode_boxes_vs_oracle."""
+    from oracle import oracle_loss
+    from votenet_amd import loss as VL
+    from votenet_amd import synth
+    rng = np.random.default_rng(12)
+    ns, nc = 10, 10
+    W, so = 5 + 2 * nh + 4 * ns + nc, 5 + 2 * nh
+    prop = (rng.random((b, p, 3)) * 4).astype(np.float32)
+    out = rng.normal(0, 1.0, (b, p, W)).astype(np.float32)
+    rows, hb = out.reshape(-1, W), nh - 1
+
+    def heading(r, bins, residuals):
+        r[5:5 + nh] = -4.0
+        for i, res in zip(bins, residuals):
+            r[5 + i], r[5 + nh + i] = 2.0, res
+
+    def size(r, classes, residuals):
+        r[so:so + ns] = -4.0
+        for i, res in zip(classes, residuals):
+            r[so + i] = 2.0
+            r[so + ns + 3 * i:so + ns + 3 * i + 3] = res
+
+    heading(rows[0], [0], [-0.5])                   # negative
+    heading(rows[1], [hb], [2.5])                   # 2 (nh - 1) + 2.5 >= 2 nh
+    heading(rows[2], [hb], [2.0])                   # 2 nh exactly
+    heading(rows[3], [hb, 0], [0.25, -30.0])        # tie: bin 0 wins, far below zero
+    size(rows[4], [3, 6], [(0.5, -0.25, 0.125), (-0.5, 2.0, 1.0)])   # tie: class 3 wins
+    size(rows[5], [7], [(-1.0, -1.0, 0.0)])         # 1 + residual = 0: the floor
+    size(rows[6], [9, 2], [(-3.5, 0.5, -1.0 - 2.0 ** -20), (0.0, 0.0, 0.0)])  # tie: class 2 wins, although class 9 was written first
+    heading(rows[-1], [hb, 0], [3.0, -0.5])
+    size(rows[-1], [8, 4], [(0.0, 0.0, 0.0), (-1.5, 0.25, -1.0)])
+    boxes, scores = VL.decode_boxes(_to_dev(prop, dev), _to_dev(out, dev), nh=nh)
+    eb, es = oracle_loss.decode_boxes(prop, out, synth.MEAN_SIZES.astype(np.float32), nh=nh)
+    got = boxes.cpu().numpy()
+    assert got.shape == (b, p, 8, 3)
+    assert np.abs(got - eb).max() <= 1e-5 * max(1.0, np.abs(eb).max())
+    assert (scores.cpu().numpy() == es).all()
+    flat = got.reshape(-1, 8, 3)
+    extent = lambda q: flat[q].max(0) - flat[q].min(0)
+    assert extent(5)[1] > 0.1 and np.hypot(extent(5)[0], extent(5)[2]) < 1e-5    # l and w on the floor, h untouched
+    # the first of a tie, told by its residuals: class 4 of the last row has h on the floor, class 8 would not
+    assert extent(-1)[1] < 1e-5 and extent(4)[1] == pytest.approx(synth.MEAN_SIZES[3][2] * 1.125, rel=1e-5)

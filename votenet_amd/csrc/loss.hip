@@ -224,6 +224,9 @@ __global__ __launch_bounds__(LOSS_T) void votenet_loss_kernel(LossArgs A, int *c
                 bp = op;
             }
         }
+        // no proposal of the scene at a finite distance (a diverged run: every centre NaN or +-inf): no lane ever took d < best and bp
+        // is still the sentinel.  Proposal 0 then, as argmin over all-NaN / all-inf distances: a NaN / inf loss, every index inside [0, P)
+        if ((unsigned)bp >= (unsigned)P) bp = 0;
         if (lane < 3) {
             const int k = lane, q = b * P + bp;
             const float cgk = (k == 0 ? gx : (k == 1 ? gy : gz)) - A.pxyz[q * 3 + k];
