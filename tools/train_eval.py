@@ -2,11 +2,13 @@
 tower (decode -> 3D NMS) on held-out scenes and report mAP@0.25 / @0.5 with the reference's evaluator logic: "mAP" is the mean
 of the per-batch mAPs (the figure of every earlier log), "set mAP" the reference's own metric, detections ranked over the whole
 validation set (evaluator.evaluate).
-    python tools/train_eval.py [steps] [train_batches] [--save PATH] [--resume PATH] [--monitor K]
+    python tools/train_eval.py [steps] [train_batches] [--save PATH] [--resume PATH] [--monitor K] [--guard]
 --save PATH: a checkpoint (VoteNetHotPath.save) at every evaluation and at the end.  --resume PATH: continue the run a checkpoint
 holds -- parameters, moving averages, Adam state and step count -- up to `steps` steps in all, on the batches it would have seen.  --monitor K: the reference's training summaries from the device
 (VoteNetHotPath.enable_monitors): every K steps the moving averages of obj_accuracy / sem_accuracy / total_cost over the last 100 steps
-(run.py:127) beside the window's mean n_pos / n_neg, every 10 K steps the five tensors with the smallest and the largest gradient rms."""
+(run.py:127) beside the window's mean n_pos / n_neg, every 10 K steps the five tensors with the smallest and the largest gradient rms.
+--guard: the step guard (VoteNetHotPath.enable_step_guard): a step whose gradient is not finite is skipped on the device; the skipped steps
+and the restores of the moving averages are printed at the end (with --monitor K: every K steps too)."""
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import importlib.util
@@ -23,6 +25,7 @@ ap.add_argument("train_batches", nargs="?", type=int, default=16)
 ap.add_argument("--save", metavar="PATH", help="write a checkpoint at every evaluation and at the end")
 ap.add_argument("--resume", metavar="PATH", help="continue from this checkpoint")
 ap.add_argument("--monitor", metavar="K", type=int, default=0, help="print the moving averages of the accuracies and the cost every K steps")
+ap.add_argument("--guard", action="store_true", help="skip steps whose gradient is not finite (on the device); print how many were")
 args = ap.parse_args()
 steps, nb = args.steps, args.train_batches
 dev = torch.device("cuda:0")
@@ -34,6 +37,8 @@ if args.resume:
 start = net._step
 if args.monitor > 0:
     net.enable_monitors(window=100, tensors_every=10 * args.monitor)
+if args.guard:
+    net.enable_step_guard()  # (after the resume: its snapshot is of the restored moving averages)
 xs = [torch.from_numpy(synth.room_batch(B, n, 5000 + B * i)).to(dev) for i in range(nb)]
 gts = [VL.gt_to_device(synth.room_gt(B, n, 5000 + B * i), dev) for i in range(nb)]
 val_x = [torch.from_numpy(synth.room_batch(B, n, 90000 + B * i)).to(dev) for i in range(4)]
@@ -63,6 +68,12 @@ def report(step):
     print("step %d: mAP" % step, evaluate(), " set mAP", {thr: res[thr]["mAP"] for thr in (0.25, 0.5)})
 
 
+def guard_line(step):
+    r = net.step_guard.read()  # (the one read-back of the guard)
+    print("step %d  step guard: %d of %d steps skipped (%d in a row now, the last at step %d), %d restores of the moving averages"
+          % (step, r["skipped"], r["seen"], r["consecutive"], r["last_skip_step"], r["ema_restores"]))
+
+
 t0 = time.time()
 report(start)
 for i in range(start, steps):
@@ -83,8 +94,12 @@ for i in range(start, steps):
                 for name, t in rows:
                     print("    %-28s grad rms %.3e  clip factor %.3e  param rms %.3e  non-finite %d" % (name, t["grad"]["rms"], t["grad"]["clip_factor"],
                                                                                                     t["param"]["rms"], t["grad"]["nonfinite"] + t["param"]["nonfinite"]))
+    if args.guard and args.monitor > 0 and (i + 1) % args.monitor == 0:
+        guard_line(i + 1)
     if (i + 1) % 300 == 0:
         report(i + 1)
         save()
 if steps % 300 or steps <= start:  # (a run that ends on an evaluation has just saved)
     save()
+if args.guard:
+    guard_line(net._step)

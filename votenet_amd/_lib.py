@@ -14,8 +14,10 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_PATH = os.path.join(_HERE, "lib", "libvotenet_hip.so")
 _MON_PATH = os.path.join(_HERE, "lib", "libvotenet_monitors.so")  # the training summaries (include/votenet_monitors.h): a library of its own
+_GUARD_PATH = os.path.join(_HERE, "lib", "libvotenet_guard.so")  # the guarded optimizer step (include/votenet_step_guard.h): likewise
 _lib = None
 _mon = None
+_guard = None
 
 
 class VotenetError(RuntimeError):
@@ -35,7 +37,9 @@ def build(force=False):
     if force:  # a clean build: the library AND every cached object file (build.sh recompiles what is missing)
         import glob
         mon = os.path.join(os.path.dirname(_LIB_PATH), os.path.basename(_MON_PATH))
-        for f in [_LIB_PATH, mon] + glob.glob(os.path.join(_HERE, "csrc", "obj", "*.o")) + glob.glob(os.path.join(_HERE, "csrc", "monitors", "obj", "*.o")):
+        guard = os.path.join(os.path.dirname(_LIB_PATH), os.path.basename(_GUARD_PATH))
+        for f in [_LIB_PATH, mon, guard] + [o for d in ("obj", os.path.join("monitors", "obj"), os.path.join("guard", "obj"))
+                                            for o in glob.glob(os.path.join(_HERE, "csrc", d, "*.o"))]:
             if os.path.exists(f):
                 os.remove(f)
     out = subprocess.run(["bash", os.path.join(_HERE, "csrc", "build.sh")], capture_output=True, text=True)
@@ -174,6 +178,34 @@ def monitors_lib():
             fn.restype, fn.argtypes = restype, argtypes
         _mon = M
     return _mon
+
+
+def guard_lib():
+    """libvotenet_guard.so, loaded when a step guard is first asked for; every function of include/votenet_step_guard.h gets its
+    header's prototype (parse_header, as for the main library).  No fallback: a missing library is an error."""
+    global _guard
+    if _guard is None:
+        if not os.path.exists(_GUARD_PATH):
+            raise VotenetError("libvotenet_guard.so not found at %s -- run `python -c 'import __graft_entry__ as g; g.build()'` "
+                               "(there is no CPU fallback)" % _GUARD_PATH)
+        with open(os.path.join(_HERE, os.pardir, "include", "votenet_step_guard.h")) as f:
+            protos = parse_header(f.read(), {})
+        G = ctypes.CDLL(_GUARD_PATH)
+        for name, (restype, argtypes) in protos.items():
+            fn = getattr(G, name)
+            fn.restype, fn.argtypes = restype, argtypes
+        _guard = G
+    return _guard
+
+
+def check_guard(rc):
+    """check() for a status libvotenet_guard.so returned (it keeps its own error text)."""
+    if rc == 0:
+        return
+    msg = guard_lib().votenet_step_guard_last_error().decode()
+    if rc == 1:
+        raise InvalidArgumentError(msg)
+    raise VotenetError("libvotenet_guard error %d: %s" % (rc, msg))
 
 
 def check_monitors(rc):

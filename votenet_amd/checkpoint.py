@@ -199,6 +199,8 @@ def _restore(net, arrays, optimizer):
         net._step = 0
     st.params_changed()     # images, transposes, padded copies: rebuilt before their next use
     net._ema_version += 1   # inference_bn() rebuilds its tables, and predict() does not warn about untrained moving averages
+    if getattr(net, "step_guard", None) is not None:
+        net.step_guard.refresh_snapshot()  # (or a bad step after this restore would bring back the averages from before it)
 
 
 def save(net, path, optimizer=True):

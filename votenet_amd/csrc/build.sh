@@ -13,7 +13,7 @@ for src in "$HERE"/*.hip; do
   obj="$HERE/obj/$(basename "${src%.hip}").o"
   # (this script carries the flags: an object older than it is stale too)
   if [ ! -f "$obj" ] || [ "$src" -nt "$obj" ] || [ "$HERE/common.h" -nt "$obj" ] || [ "$HERE/mlp_types.h" -nt "$obj" ] || [ "$HERE/iou3d.h" -nt "$obj" ] \
-     || [ "$HERE/nearest_box.h" -nt "$obj" ] \
+     || [ "$HERE/nearest_box.h" -nt "$obj" ] || [ "$HERE/sumsq.h" -nt "$obj" ] \
      || [ "$HERE/../../include/votenet_hip.h" -nt "$obj" ] || [ "$HERE/../../include/votenet_hip_debug.h" -nt "$obj" ] \
      || [ "${BASH_SOURCE[0]}" -nt "$obj" ]; then
     extra=""
@@ -51,3 +51,18 @@ $HIPCC --offload-arch=gfx950 -shared -fPIC -Wl,--version-script="$HERE/monitors/
 python3 "$HERE/../../tools/check_isa_hazards.py" "$MTMP"
 mv -f "$MTMP" "$OUT/libvotenet_monitors.so"
 echo "built $OUT/libvotenet_monitors.so"
+# libvotenet_guard.so (include/votenet_step_guard.h): the guarded optimizer step, a library of its own for the same reason.  Same
+# flags, same gate; sumsq.h is the text of votenet_clip_adam's partial sums, so both libraries form the same bits.
+GOBJ="$HERE/guard/obj/step_guard.o"
+mkdir -p "$HERE/guard/obj"
+if [ ! -f "$GOBJ" ] || [ "$HERE/guard/step_guard.hip" -nt "$GOBJ" ] || [ "$HERE/sumsq.h" -nt "$GOBJ" ] \
+   || [ "$HERE/../../include/votenet_step_guard.h" -nt "$GOBJ" ] || [ "$HERE/../../include/votenet_hip.h" -nt "$GOBJ" ] \
+   || [ "${BASH_SOURCE[0]}" -nt "$GOBJ" ]; then
+  $HIPCC $FLAGS -fno-slp-vectorize -c "$HERE/guard/step_guard.hip" -o "$GOBJ"
+fi
+GTMP="$OUT/.libvotenet_guard.so.tmp.$$"
+trap 'rm -f "$TMP" "$MTMP" "$GTMP"' EXIT
+$HIPCC --offload-arch=gfx950 -shared -fPIC -Wl,--version-script="$HERE/guard/exports.map" "$GOBJ" -o "$GTMP"
+python3 "$HERE/../../tools/check_isa_hazards.py" "$GTMP"
+mv -f "$GTMP" "$OUT/libvotenet_guard.so"
+echo "built $OUT/libvotenet_guard.so"

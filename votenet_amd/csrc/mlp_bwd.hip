@@ -574,35 +574,7 @@ __global__ __launch_bounds__(256) void group_concat_grad_kernel(long groups, int
 }
 
 // ---------------------------------------------------------------- optimizer
-// sum of squares of every tensor's gradient segment: grid (kSumsqSlices slices, ntensors) -> out[tensor * kSumsqSlices + slice]; the
-// optimizer adds the partials in slice order (no atomics: every data-parallel replica must compute bit-identical clip factors from
-// the same all-reduced gradient, or the replicas drift apart).  32 slices and four loads in flight per thread: the largest tensors
-// (512 x 256) bound the launch -- 27 -> see profiles (8 slices, one load at a time)
-constexpr int kSumsqSlices = VOTENET_SUMSQ_SLICES;
-__global__ __launch_bounds__(256) void seg_sumsq_kernel(const float *__restrict__ g, const long *__restrict__ seg,
-                                                        float *__restrict__ out)
-{
-    __shared__ float sh[256];
-    const long a = seg[2 * blockIdx.y], b = seg[2 * blockIdx.y + 1];
-    const long step = 256L * gridDim.x;
-    float s0 = 0, s1 = 0, s2 = 0, s3 = 0;
-    long i = a + (long)blockIdx.x * 256 + threadIdx.x;
-    for (; i + 3 * step < b; i += 4 * step) {
-        const float v0 = g[i], v1 = g[i + step], v2 = g[i + 2 * step], v3 = g[i + 3 * step];
-        s0 += v0 * v0;
-        s1 += v1 * v1;
-        s2 += v2 * v2;
-        s3 += v3 * v3;
-    }
-    for (; i < b; i += step) s0 += g[i] * g[i];
-    sh[threadIdx.x] = (s0 + s1) + (s2 + s3);
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) sh[threadIdx.x] += sh[threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[blockIdx.y * kSumsqSlices + blockIdx.x] = sh[0];
-}
+#include "sumsq.h" // seg_sumsq_kernel, kSumsqSlices (shared with guard/step_guard.hip)
 
 // tf.clip_by_average_norm(g, clip): g * clip / max(||g||/numel, clip)   (model.py:249), then tf.train.AdamOptimizer
 // (model.py:246) in TensorFlow's form: lr_t = lr * sqrt(1 - b2^t) / (1 - b1^t);  p -= lr_t * m / (sqrt(v) + eps)

@@ -1594,3 +1594,34 @@ def clip_adam(seg, sumsq, p, g, m, v, lr, step, grad_scale=1.0, clip=0.5, beta1=
         L.check(L.lib().votenet_clip_adam(seg.numel() // 2, L.ptr(seg), L.ptr(sumsq), L.ptr(p), L.ptr(g), L.ptr(m), L.ptr(v),
                                           float(lr), float(beta1), float(beta2), float(eps), int(step), float(grad_scale),
                                           float(clip), L.stream_ptr()))
+
+
+def clip_adam_guarded(seg, sumsq, p, g, m, v, lr, step, guard_state, ema=None, ema_snapshot=None, grad_scale=1.0, clip=0.5, beta1=0.9,
+                      beta2=0.999, eps=1e-8):
+    """clip_adam behind the step guard (include/votenet_step_guard.h, libvotenet_guard.so): a gradient bucket with a non-finite partial
+    sum of squares leaves p, m, v untouched and is counted in guard_state (int32, votenet_step_guard_state_ints()); a good step is
+    clip_adam bit for bit.  ema / ema_snapshot (both or neither): the BatchNorm moving averages and the guard's copy of them."""
+    nt = seg.numel() // 2
+    if sumsq.numel() < SUMSQ_SLICES * nt:
+        raise L.InvalidArgumentError("clip_adam_guarded: the scratch holds %d floats, %d tensors need %d" % (sumsq.numel(), nt, SUMSQ_SLICES * nt))
+    G = L.guard_lib()
+    want = G.votenet_step_guard_state_ints()
+    if guard_state.dtype != torch.int32 or guard_state.numel() != want or not guard_state.is_contiguous():
+        raise L.InvalidArgumentError("clip_adam_guarded: guard_state must be %d contiguous int32, got %d %s"
+                                     % (want, guard_state.numel(), guard_state.dtype))
+    if (ema is None) != (ema_snapshot is None):
+        raise L.InvalidArgumentError("clip_adam_guarded: ema and ema_snapshot go together")
+    n_ema = 0
+    if ema is not None:
+        n_ema = ema.numel()
+        if ema_snapshot.numel() != n_ema or ema.dtype != torch.float32 or ema_snapshot.dtype != torch.float32 \
+                or not (ema.is_contiguous() and ema_snapshot.is_contiguous()):
+            raise L.InvalidArgumentError("clip_adam_guarded: ema and ema_snapshot must be contiguous float32 of one size (%d, %d)"
+                                         % (n_ema, ema_snapshot.numel()))
+    if not p.is_cuda:
+        raise L.VotenetError("clip_adam_guarded: the buffers must live on the GPU (no CPU fallback in votenet_amd)")
+    with L.device_guard(p.device):
+        L.check_guard(G.votenet_clip_adam_guarded(nt, L.ptr(seg), L.ptr(sumsq), L.ptr(p), L.ptr(g), L.ptr(m), L.ptr(v), float(lr),
+                                                  float(beta1), float(beta2), float(eps), int(step), float(grad_scale), float(clip),
+                                                  L.ptr(ema) if n_ema else None, L.ptr(ema_snapshot) if n_ema else None, n_ema,
+                                                  L.ptr(guard_state), L.stream_ptr()))

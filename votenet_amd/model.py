@@ -920,6 +920,23 @@ class VoteNetHotPath:
         self.monitors = None
         self.last_accuracies = None
 
+    # ---- the step guard (step_guard.py): off unless asked for ------------------------------------------------------------------
+    step_guard = None        # a step_guard.StepGuard while enable_step_guard is in force
+
+    def enable_step_guard(self):
+        """From now on the optimizer of every train_step runs behind a verdict on the device (step_guard.py): a step whose gradient is
+        not finite leaves parameters, Adam moments and BatchNorm moving averages bit for bit as they were and is counted; a good step
+        is the unguarded update bit for bit.  One launch more per step; nothing is read back until self.step_guard.read().  The
+        optimizer must exist (init_optimizer / a loaded checkpoint); the counters start at zero, the snapshot of the moving averages is
+        taken now.  -> the StepGuard."""
+        from . import step_guard
+        self.step_guard = step_guard.StepGuard(self)
+        return self.step_guard
+
+    def disable_step_guard(self):
+        """Back to the launches of an unguarded step (the default)."""
+        self.step_guard = None
+
     def init_optimizer(self, lr=LEARNING_RATE):
         s = self.store
         base = s.flat.data_ptr()
@@ -999,8 +1016,11 @@ class VoteNetHotPath:
         self.store.invalidate_transposes()      # the optimizer changes W
         gscale = self._gsync.finish()           # head all-reduce + wait for both; 1/world goes to the optimizer
         self._step += 1
-        M.clip_adam(self._seg, self._sumsq, self.store.flat, self.store.grad, self._m, self._v, self._lr, self._step,
-                    grad_scale=gscale)
+        if self.step_guard is not None:
+            self.step_guard.apply(self, gscale)  # the same update behind the verdict on this gradient (step_guard.py)
+        else:
+            M.clip_adam(self._seg, self._sumsq, self.store.flat, self.store.grad, self._m, self._v, self._lr, self._step,
+                        grad_scale=gscale)
         if self.monitors is not None:
             self.monitors.after_optimizer(self, gscale, 0.5)  # (0.5: clip_adam's clip_by_average_norm, model.py:249)
         return out
