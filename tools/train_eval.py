@@ -2,13 +2,15 @@
 tower (decode -> 3D NMS) on held-out scenes and report mAP@0.25 / @0.5 with the reference's evaluator logic: "mAP" is the mean
 of the per-batch mAPs (the figure of every earlier log), "set mAP" the reference's own metric, detections ranked over the whole
 validation set (evaluator.evaluate).
-    python tools/train_eval.py [steps] [train_batches] [--save PATH] [--resume PATH] [--monitor K] [--guard]
+    python tools/train_eval.py [steps] [train_batches] [--save PATH] [--resume PATH] [--monitor K] [--guard] [--height]
 --save PATH: a checkpoint (VoteNetHotPath.save) at every evaluation and at the end.  --resume PATH: continue the run a checkpoint
 holds -- parameters, moving averages, Adam state and step count -- up to `steps` steps in all, on the batches it would have seen.  --monitor K: the reference's training summaries from the device
 (VoteNetHotPath.enable_monitors): every K steps the moving averages of obj_accuracy / sem_accuracy / total_cost over the last 100 steps
 (run.py:127) beside the window's mean n_pos / n_neg, every 10 K steps the five tensors with the smallest and the largest gradient rms.
 --guard: the step guard (VoteNetHotPath.enable_step_guard): a step whose gradient is not finite is skipped on the device; the skipped steps
-and the restores of the moving averages are printed at the end (with --monitor K: every K steps too)."""
+and the restores of the moving averages are printed at the end (with --monitor K: every K steps too).
+--height: the network takes one input feature per point, the height above the scene's floor (VoteNetHotPath(point_features=1)), made on
+the device by input_pipeline.subsample_augment_features from the same clouds (already in the camera frame; the rooms have no colour)."""
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import importlib.util
@@ -16,7 +18,7 @@ _spec = importlib.util.spec_from_file_location("votenet_hostpin", os.path.join(o
 hostpin = importlib.util.module_from_spec(_spec); _spec.loader.exec_module(hostpin)  # by path: the package's __init__ would import torch first
 hostpin.pin(0)  # as bench.py: the host threads on eight cores of the GPU's NUMA node
 import numpy as np, torch
-from votenet_amd import evaluator as E, loss as VL, synth
+from votenet_amd import evaluator as E, input_pipeline as IP, loss as VL, synth
 from votenet_amd.model import VoteNetHotPath
 
 ap = argparse.ArgumentParser()
@@ -26,11 +28,12 @@ ap.add_argument("--save", metavar="PATH", help="write a checkpoint at every eval
 ap.add_argument("--resume", metavar="PATH", help="continue from this checkpoint")
 ap.add_argument("--monitor", metavar="K", type=int, default=0, help="print the moving averages of the accuracies and the cost every K steps")
 ap.add_argument("--guard", action="store_true", help="skip steps whose gradient is not finite (on the device); print how many were")
+ap.add_argument("--height", action="store_true", help="feed the height above the floor as a point feature (point_features=1)")
 args = ap.parse_args()
 steps, nb = args.steps, args.train_batches
 dev = torch.device("cuda:0")
 B, n = 8, 20480
-net = VoteNetHotPath(dev, seed=0)
+net = VoteNetHotPath(dev, seed=0, point_features=1 if args.height else 0)
 net.init_optimizer(1e-3)
 if args.resume:
     net.load(args.resume)
@@ -45,12 +48,25 @@ val_x = [torch.from_numpy(synth.room_batch(B, n, 90000 + B * i)).to(dev) for i i
 val_gt = [E.gt_for_eval(synth.room_gt(B, n, 90000 + B * i)) for i in range(4)]
 
 
+def heights(x):
+    """(B, n, 1): the cloud's own rows in their order (choice = arange), camera frame already -> the points again and their height"""
+    b, m = x.shape[:2]
+    points, feats, _ = IP.subsample_augment_features(x.reshape(b * m, 3), np.arange(b + 1, dtype=np.int64) * m, m,
+                                                     choice=torch.arange(m, dtype=torch.int32, device=dev).repeat(b, 1), depth_to_camera=False)
+    assert torch.equal(points, x)
+    return feats
+
+
+fs = [heights(x) for x in xs] if args.height else [None] * nb
+val_f = [heights(x) for x in val_x] if args.height else [None] * 4
+
+
 def evaluate():
     res = {}
     for thr in (0.25, 0.5):
         aps = []
-        for x, g in zip(val_x, val_gt):
-            pred = net.predict(x, 0.25)
+        for x, f, g in zip(val_x, val_f, val_gt):
+            pred = net.predict(x, 0.25, feats=f)
             aps.append(E.eval_det(pred, g, thr)[1])
         res[thr] = float(np.nanmean(aps))
     return res
@@ -64,7 +80,7 @@ def save():
 
 def report(step):
     """The line of every earlier log (mean of the per-batch mAPs), and beside it the reference's metric: mAP over the whole set."""
-    res = E.evaluate(net, val_x, val_gt, (0.25, 0.5))
+    res = E.evaluate(net, list(zip(val_x, val_f)) if args.height else val_x, val_gt, (0.25, 0.5))
     print("step %d: mAP" % step, evaluate(), " set mAP", {thr: res[thr]["mAP"] for thr in (0.25, 0.5)})
 
 
@@ -77,7 +93,7 @@ def guard_line(step):
 t0 = time.time()
 report(start)
 for i in range(start, steps):
-    net.train_step(xs[i % nb], gt=gts[i % nb], next_x=xs[(i + 1) % nb])  # geometry of the next batch under this step
+    net.train_step(xs[i % nb], gt=gts[i % nb], next_x=xs[(i + 1) % nb], feats=fs[i % nb], next_feats=fs[(i + 1) % nb])  # geometry of the next batch under this step
     if (i + 1) % 100 == 0:
         l = net.last_losses.cpu().numpy()
         print("step %d  cost %.3f  vote %.3f obj %.3f box %.3f sem %.3f  pos %d  (%.1f s)" % (i + 1, l[0], l[1], l[2], l[9], l[8], int(l[10]),

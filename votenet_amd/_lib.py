@@ -15,9 +15,11 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_PATH = os.path.join(_HERE, "lib", "libvotenet_hip.so")
 _MON_PATH = os.path.join(_HERE, "lib", "libvotenet_monitors.so")  # the training summaries (include/votenet_monitors.h): a library of its own
 _GUARD_PATH = os.path.join(_HERE, "lib", "libvotenet_guard.so")  # the guarded optimizer step (include/votenet_step_guard.h): likewise
+_FEAT_PATH = os.path.join(_HERE, "lib", "libvotenet_features.so")  # the input step with point features (include/votenet_point_features.h): likewise
 _lib = None
 _mon = None
 _guard = None
+_feat = None
 
 
 class VotenetError(RuntimeError):
@@ -38,7 +40,8 @@ def build(force=False):
         import glob
         mon = os.path.join(os.path.dirname(_LIB_PATH), os.path.basename(_MON_PATH))
         guard = os.path.join(os.path.dirname(_LIB_PATH), os.path.basename(_GUARD_PATH))
-        for f in [_LIB_PATH, mon, guard] + [o for d in ("obj", os.path.join("monitors", "obj"), os.path.join("guard", "obj"))
+        feat = os.path.join(os.path.dirname(_LIB_PATH), os.path.basename(_FEAT_PATH))
+        for f in [_LIB_PATH, mon, guard, feat] + [o for d in ("obj", os.path.join("monitors", "obj"), os.path.join("guard", "obj"), os.path.join("features", "obj"))
                                             for o in glob.glob(os.path.join(_HERE, "csrc", d, "*.o"))]:
             if os.path.exists(f):
                 os.remove(f)
@@ -196,6 +199,34 @@ def guard_lib():
             fn.restype, fn.argtypes = restype, argtypes
         _guard = G
     return _guard
+
+
+def features_lib():
+    """libvotenet_features.so, loaded when point features are first asked for; every function of include/votenet_point_features.h gets
+    its header's prototype (parse_header, as for the main library).  No fallback: a missing library is an error."""
+    global _feat
+    if _feat is None:
+        if not os.path.exists(_FEAT_PATH):
+            raise VotenetError("libvotenet_features.so not found at %s -- run `python -c 'import __graft_entry__ as g; g.build()'` "
+                               "(there is no CPU fallback)" % _FEAT_PATH)
+        with open(os.path.join(_HERE, os.pardir, "include", "votenet_point_features.h")) as f:
+            protos = parse_header(f.read(), {})
+        F = ctypes.CDLL(_FEAT_PATH)
+        for name, (restype, argtypes) in protos.items():
+            fn = getattr(F, name)
+            fn.restype, fn.argtypes = restype, argtypes
+        _feat = F
+    return _feat
+
+
+def check_features(rc):
+    """check() for a status libvotenet_features.so returned (it keeps its own error text)."""
+    if rc == 0:
+        return
+    msg = features_lib().votenet_point_features_last_error().decode()
+    if rc == 1:
+        raise InvalidArgumentError(msg)
+    raise VotenetError("libvotenet_features error %d: %s" % (rc, msg))
 
 
 def check_guard(rc):

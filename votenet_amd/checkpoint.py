@@ -10,7 +10,8 @@ The state carries the reference's variable names (Tensorpack's Conv2D / FullyCon
     <var>/Adam, <var>/Adam_1                first and second Adam moments, shaped like <var>        (optimizer=True)
     global_step (int64), learning_rate      the optimizer's step count and rate (model.py:241)     (optimizer=True)
 
-tests/golden/votenet_variable_names.txt lists every key with its shape.  The rows of every kernel are in the reference's order already
+tests/golden/votenet_variable_names.txt lists every key with its shape (sa1/conv0/W: 6 input rows, the reference's xyz-as-features; a
+model built with point_features = c has 3 + c there, under the same name, and a file of another width is refused).  The rows of every kernel are in the reference's order already
 for the modules VoteNetHotPath builds -- [xyz | features] at an SA layer's first conv, [interpolated | points1] at FP, [seeds_xyz |
 seeds_points] at voting -- so a kernel is the store's (cin, cout) matrix reshaped, never permuted.
 
@@ -30,6 +31,7 @@ import torch
 
 FORMAT_VERSION = 1
 HEADER_KEY = "__header__"
+SA1_FIRST = "sa1/conv0/W"  # (1, 1, 3 + c, 64): the kernel whose input width follows the model's point_features
 
 
 def _layers(net):
@@ -144,6 +146,11 @@ def _validate(net, sd, strict, optimizer=None, problems=(), unreadable=()):
             a = _as_array(sd[key])
         except Exception as e:  # (whatever the value is, it is not an array)
             problems.append("%s: not an array (%s)" % (key, e))
+            continue
+        if key == SA1_FIRST and a.ndim == len(shape) and a.shape[-2] != shape[-2]:
+            # the one width that is the model's choice (VoteNetHotPath(point_features=c): 3 + c rows; 0: the coordinates twice, 6)
+            problems.append("%s: the checkpoint's sa1 takes %d input rows, this model's takes %d (3 coordinates + the point features: "
+                            "VoteNetHotPath(point_features=%d))" % (key, a.shape[-2], shape[-2], getattr(net, "point_features", 0)))
             continue
         if kind == "step":
             ok = a.dtype.kind in "iu" and a.shape == () and int(a) >= 0

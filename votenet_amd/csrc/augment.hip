@@ -4,59 +4,9 @@
 // worker processes; here one launch serves a batch: a row gather (random 12-24 byte reads, coalesced 12-byte writes), pure
 // HBM traffic.  Arithmetic is double precision, un-fused, in the reference's order, rounded once to float -- what numpy
 // float64 followed by the float32 feed does.
-#include "common.h"
+#include "augment_points.h" // AugScenes, subsample_augment_kernel and its launches: shared with libvotenet_features.so
 
 namespace votenet {
-
-constexpr int AUG_CHUNK = 16; // scenes per launch: their parameters travel as kernel arguments
-
-struct AugScenes {
-    long off[AUG_CHUNK + 1];
-    double c[AUG_CHUNK], s[AUG_CHUNK], scale[AUG_CHUNK], angle[AUG_CHUNK];
-    int flip[AUG_CHUNK];
-    unsigned key[AUG_CHUNK];
-};
-
-template <typename T>
-__global__ __launch_bounds__(256) void subsample_augment_kernel(AugScenes P, int n_out, const T *__restrict__ raw, int stride,
-                                                                const int *__restrict__ choice, int to_camera, int train,
-                                                                float *__restrict__ out)
-{
-    const int sc = blockIdx.y;
-    const int j = blockIdx.x * 256 + threadIdx.x;
-    if (j >= n_out) return;
-    const long n = P.off[sc + 1] - P.off[sc];
-    long i;
-    if (choice) {
-        i = choice[(long)sc * n_out + j];
-        i = i < 0 ? 0 : (i >= n ? n - 1 : i); // validated on the host side of the Python mirror; never read out of range
-    } else {
-        int bits = 2;
-        while ((1ll << bits) < n) bits += 2;
-        i = feistel_perm(j, n, P.key[sc], bits >> 1);
-    }
-    const T *p = raw + (P.off[sc] + i) * stride;
-    double x = (double)p[0], y = (double)p[1], z = (double)p[2];
-    if (to_camera) { // sunutils.py:70-77: (x, y, z) -> (x, -z, y)
-        const double t = y;
-        y = -z;
-        z = t;
-    }
-    if (train) {
-        if (P.flip[sc] & 1) x = -x; // dataset.py:303-306
-        if (P.flip[sc] & 2) z = -z;
-        const double c = P.c[sc], s = P.s[sc];
-        const double xr = c * x + s * z; // roty(a) @ p, sunutils.py:133-139
-        const double zr = -s * x + c * z;
-        x = xr * P.scale[sc]; // dataset.py:308
-        y = y * P.scale[sc];
-        z = zr * P.scale[sc];
-    }
-    float *o = out + ((long)sc * n_out + j) * 3;
-    o[0] = (float)x;
-    o[1] = (float)y;
-    o[2] = (float)z;
-}
 
 __device__ __forceinline__ double py_mod(double a, double m) // CPython float %: fmod, then the sign of the divisor
 {
@@ -144,39 +94,11 @@ extern "C" int votenet_subsample_augment(int b, int n_out, const void *raw, int 
                                          const int *flip, const double *rot_cos, const double *rot_sin, const double *scale,
                                          float *out, void *stream)
 {
-    VN_REQUIRE(b > 0 && n_out > 0, "subsample_augment: b and n_out must be positive, got %d, %d", b, n_out);
-    VN_REQUIRE(raw && raw_offset && out, "subsample_augment: null pointer");
-    VN_REQUIRE(raw_stride >= 3, "subsample_augment: raw rows need at least 3 elements, got %d", raw_stride);
-    VN_REQUIRE(!flip || (rot_cos && rot_sin && scale), "subsample_augment: flip given without rot_cos / rot_sin / scale");
-    for (int s = 0; s < b; s++) {
-        const long n = raw_offset[s + 1] - raw_offset[s];
-        VN_REQUIRE(n >= n_out, "subsample_augment: scene %d has %ld points, cannot take %d without replacement", s, n, n_out);
-        VN_REQUIRE(n < (1l << 31), "subsample_augment: scene %d has %ld points (limit 2^31)", s, n);
-    }
-    for (int s0 = 0; s0 < b; s0 += AUG_CHUNK) {
-        const int ns = b - s0 < AUG_CHUNK ? b - s0 : AUG_CHUNK;
-        AugScenes P = {};
-        for (int s = 0; s < ns; s++) {
-            P.off[s] = raw_offset[s0 + s];
-            P.off[s + 1] = raw_offset[s0 + s + 1];
-            P.key[s] = scene_key(seed, scene0 + s0 + s);
-            if (flip) {
-                P.flip[s] = flip[s0 + s];
-                P.c[s] = rot_cos[s0 + s];
-                P.s[s] = rot_sin[s0 + s];
-                P.scale[s] = scale[s0 + s];
-            }
-        }
-        const dim3 grid((n_out + 255) / 256, ns);
-        const int *ch = choice ? choice + (long)s0 * n_out : nullptr;
-        float *o = out + (long)s0 * n_out * 3;
-        if (raw_f64)
-            hipLaunchKernelGGL(subsample_augment_kernel<double>, grid, dim3(256), 0, as_stream(stream), P, n_out,
-                               (const double *)raw, raw_stride, ch, depth_to_camera, flip ? 1 : 0, o);
-        else
-            hipLaunchKernelGGL(subsample_augment_kernel<float>, grid, dim3(256), 0, as_stream(stream), P, n_out,
-                               (const float *)raw, raw_stride, ch, depth_to_camera, flip ? 1 : 0, o);
-    }
+    char msg[256];
+    VN_REQUIRE(points_args_ok("subsample_augment", b, n_out, raw, raw_stride, raw_offset, flip, rot_cos, rot_sin, scale, out, msg, sizeof msg),
+               "%s", msg);
+    launch_points(b, n_out, raw, raw_f64, raw_stride, raw_offset, choice, seed, scene0, depth_to_camera, flip, rot_cos, rot_sin, scale,
+                  out, nullptr, 0, 0, 0, as_stream(stream));
     return check_launch("subsample_augment");
 }
 

@@ -13,7 +13,7 @@ for src in "$HERE"/*.hip; do
   obj="$HERE/obj/$(basename "${src%.hip}").o"
   # (this script carries the flags: an object older than it is stale too)
   if [ ! -f "$obj" ] || [ "$src" -nt "$obj" ] || [ "$HERE/common.h" -nt "$obj" ] || [ "$HERE/mlp_types.h" -nt "$obj" ] || [ "$HERE/iou3d.h" -nt "$obj" ] \
-     || [ "$HERE/nearest_box.h" -nt "$obj" ] || [ "$HERE/sumsq.h" -nt "$obj" ] \
+     || [ "$HERE/nearest_box.h" -nt "$obj" ] || [ "$HERE/sumsq.h" -nt "$obj" ] || [ "$HERE/augment_points.h" -nt "$obj" ] \
      || [ "$HERE/../../include/votenet_hip.h" -nt "$obj" ] || [ "$HERE/../../include/votenet_hip_debug.h" -nt "$obj" ] \
      || [ "${BASH_SOURCE[0]}" -nt "$obj" ]; then
     extra=""
@@ -66,3 +66,20 @@ $HIPCC --offload-arch=gfx950 -shared -fPIC -Wl,--version-script="$HERE/guard/exp
 python3 "$HERE/../../tools/check_isa_hazards.py" "$GTMP"
 mv -f "$GTMP" "$OUT/libvotenet_guard.so"
 echo "built $OUT/libvotenet_guard.so"
+# libvotenet_features.so (include/votenet_point_features.h): the input step of a network with point features, a library of its own for
+# the same reason.  Same flags, same gate; augment_points.h is the text of votenet_subsample_augment's points, so both libraries write
+# the same bits.
+FOBJ="$HERE/features/obj/point_features.o"
+mkdir -p "$HERE/features/obj"
+if [ ! -f "$FOBJ" ] || [ "$HERE/features/point_features.hip" -nt "$FOBJ" ] || [ "$HERE/augment_points.h" -nt "$FOBJ" ] \
+   || [ "$HERE/common.h" -nt "$FOBJ" ] || [ "$HERE/../../include/votenet_point_features.h" -nt "$FOBJ" ] \
+   || [ "$HERE/../../include/votenet_hip.h" -nt "$FOBJ" ] || [ "$HERE/../../include/votenet_hip_debug.h" -nt "$FOBJ" ] \
+   || [ "${BASH_SOURCE[0]}" -nt "$FOBJ" ]; then
+  $HIPCC $FLAGS -c "$HERE/features/point_features.hip" -o "$FOBJ"
+fi
+FTMP="$OUT/.libvotenet_features.so.tmp.$$"
+trap 'rm -f "$TMP" "$MTMP" "$GTMP" "$FTMP"' EXIT
+$HIPCC --offload-arch=gfx950 -shared -fPIC -Wl,--version-script="$HERE/features/exports.map" "$FOBJ" -o "$FTMP"
+python3 "$HERE/../../tools/check_isa_hazards.py" "$FTMP"
+mv -f "$FTMP" "$OUT/libvotenet_features.so"
+echo "built $OUT/libvotenet_features.so"

@@ -235,14 +235,20 @@ class DetectionAccumulator:
 
 
 def evaluate(net, batches, gts, thresholds=(0.25, 0.5), iou_threshold=0.25):
-    """mAP of `net` over a validation set: batches[i] (B,n,3) device clouds, gts[i] gt_for_eval's dict (numpy or device).  Every
-    predict call is asynchronous with the next batch's geometry underneath it; one synchronisation at the end.
+    """mAP of `net` over a validation set: batches[i] (B,n,3) device clouds -- or (cloud, feats (B,n,c)) pairs for a network built with
+    point features --, gts[i] gt_for_eval's dict (numpy or device).  Every predict call is asynchronous with the next batch's
+    geometry underneath it; one synchronisation at the end.
     -> {threshold: dict(ap, mAP, rec, prec, npos)}."""
     acc = None
-    for i, (x, g) in enumerate(zip(batches, gts)):
-        pred = net.predict(x, iou_threshold, next_x=batches[i + 1] if i + 1 < len(batches) else None, sync=False)
+    pairs = [tuple(v) if isinstance(v, (tuple, list)) else (v, None) for v in batches]
+    for i, ((x, f), g) in enumerate(zip(pairs, gts)):
+        nx, nf = pairs[i + 1] if i + 1 < len(pairs) else (None, None)
+        if f is None:  # (the call of every network without point features, as it was)
+            pred = net.predict(x, iou_threshold, next_x=nx, sync=False)
+        else:
+            pred = net.predict(x, iou_threshold, next_x=nx, sync=False, feats=f, next_feats=nf)
         if acc is None:  # every proposal of every scene kept: the most the set can offer
-            acc = DetectionAccumulator(x.device, thresholds, capacity=sum(int(v.shape[0]) for v in batches) * int(pred["bboxes"].shape[1]))
+            acc = DetectionAccumulator(x.device, thresholds, capacity=sum(int(v.shape[0]) for v, _ in pairs) * int(pred["bboxes"].shape[1]))
         acc.add(pred, g)
     if acc is None:
         raise L.InvalidArgumentError("evaluate: no batches")

@@ -100,6 +100,43 @@ def subsample_augment(raw, raw_offset, n_out=POINT_NUM, aug=None, choice=None, s
     return out
 
 
+def subsample_augment_features(raw, raw_offset, n_out=POINT_NUM, aug=None, choice=None, seed=0, scene0=0, depth_to_camera=True,
+                               height=True, extra_cols=0, order_stats=None):
+    """subsample_augment plus the input features of a network built with point_features = height + extra_cols (beyond the reference,
+    which drops the colour, dataset.py:310): the same points bit for bit, feats (b, n_out, c) = [height above the scene's floor | raw
+    columns 3 .. 3+extra_cols of the rows the points came from, rounded to float, un-augmented], floor (b) float32 -- the
+    np.percentile(-y, 0.99) of the OUTPUT points of each scene (votenet_subsample_augment_features); None without height.
+    order_stats: None, or a (b, 2) float32 device tensor that receives the two order statistics the floor interpolates (tests).
+    -> (points, feats, floor), all on the device; nothing is read back."""
+    raw, off, b, ch = _check_raw(raw, raw_offset, n_out, choice, "subsample_augment_features")
+    if aug is not None and aug.b != b:
+        raise L.InvalidArgumentError("subsample_augment_features: %d scenes but %d augmentation draws" % (b, aug.b))
+    want_height, extra_cols = (1 if height else 0), int(extra_cols)
+    c = want_height + extra_cols
+    if not 0 <= extra_cols <= 4 or not 1 <= c <= 5:
+        raise L.InvalidArgumentError("subsample_augment_features: height + extra_cols must be in [1, 5] with extra_cols in [0, 4], "
+                                     "got height=%r, extra_cols=%d" % (bool(height), extra_cols))
+    if 3 + extra_cols > raw.shape[1]:
+        raise L.InvalidArgumentError("subsample_augment_features: extra_cols = %d needs raw rows of %d elements, raw has %d"
+                                     % (extra_cols, 3 + extra_cols, raw.shape[1]))
+    out = torch.empty((b, n_out, 3), dtype=torch.float32, device=raw.device)
+    feats = torch.empty((b, n_out, c), dtype=torch.float32, device=raw.device)
+    floor = torch.empty((b,), dtype=torch.float32, device=raw.device) if want_height else None
+    if order_stats is not None and (order_stats.dtype != torch.float32 or tuple(order_stats.shape) != (b, 2) or order_stats.device != raw.device
+                                    or not order_stats.is_contiguous()):
+        raise L.InvalidArgumentError("subsample_augment_features: order_stats must be a contiguous (b, 2) float32 tensor on raw's device")
+    flip = c_ = s = sc = None
+    if aug is not None:
+        flip, _, c_, s, sc = aug.host_arrays()
+    with L.device_guard(raw.device):
+        L.check_features(L.features_lib().votenet_subsample_augment_features(b, n_out, L.ptr(raw), 1 if raw.dtype == torch.float64 else 0, raw.shape[1],
+                                                           _hp(off), L.ptr(ch), int(seed) & (2 ** 64 - 1), int(scene0),
+                                                           1 if depth_to_camera else 0, _hp(flip), _hp(c_), _hp(s), _hp(sc), want_height,
+                                                           extra_cols, L.ptr(out), L.ptr(feats), L.ptr(floor), L.ptr(order_stats),
+                                                           L.stream_ptr()))
+    return out, feats, floor
+
+
 GT_FIELDS = (("bboxes_xyz", 3, torch.float32), ("bboxes_lwh", 3, torch.float32), ("bboxes_roty", 0, torch.float32),
              ("semantic_labels", 0, torch.int32), ("heading_labels", 0, torch.int32), ("heading_residuals", 0, torch.float32),
              ("size_labels", 0, torch.int32), ("size_residuals", 3, torch.float32))
@@ -225,12 +262,14 @@ def select_boxes(raw, raw_offset, calib, objects, n_out=POINT_NUM, choice=None, 
     return res
 
 
-def build_batch(raw, raw_offset, calib, objects, aug=None, choice=None, seed=0, scene0=0, n_out=POINT_NUM):
+def build_batch(raw, raw_offset, calib, objects, aug=None, choice=None, seed=0, scene0=0, n_out=POINT_NUM, height=False, extra_cols=0):
     """Parsed scenes -> model inputs: select_boxes, then subsample_augment and augment_boxes with the same choice / seed for
     the scenes that kept at least one box (the reference skips the others, dataset.py:300).  aug holds one draw per INPUT
     scene: the reference draws before it looks at the objects (dataset.py:219-231), so a dropped scene consumes its draw.
     -> (points (k, n_out, 3) float32, gt dict of augment_boxes, scene_index host int64 (k)); (None, None, empty) when every
-    scene is dropped."""
+    scene is dropped.  height / extra_cols (subsample_augment_features): the dict also holds "features" (k, n_out, c), the input
+    features of a network built with point_features = c, and the points come from that entry (the same bits); the boxes are
+    selected on the same un-augmented rows either way."""
     b = len(raw_offset) - 1
     if aug is not None and aug.b != b:
         raise L.InvalidArgumentError("build_batch: %d scenes but %d augmentation draws" % (b, aug.b))
@@ -240,11 +279,19 @@ def build_batch(raw, raw_offset, calib, objects, aug=None, choice=None, seed=0, 
     if len(scene_index) == 0:
         return None, None, scene_index
     # every input scene goes through the point kernel with its own rows and its own draw; the dropped ones are left out after
-    points = subsample_augment(raw, raw_offset, n_out, aug, choice, seed, scene0)
+    feats = None
+    if height or extra_cols:
+        points, feats, _ = subsample_augment_features(raw, raw_offset, n_out, aug, choice, seed, scene0, height=height, extra_cols=extra_cols)
+    else:
+        points = subsample_augment(raw, raw_offset, n_out, aug, choice, seed, scene0)
     if len(scene_index) < b:
-        points = points[torch.from_numpy(scene_index).to(points.device)]
+        keep = torch.from_numpy(scene_index).to(points.device)
+        points = points[keep]
+        feats = feats[keep] if feats is not None else None
         if aug is not None:
             aug = Augmentation(aug.flip_x[scene_index], aug.flip_z[scene_index], aug.angle[scene_index], aug.scale[scene_index])
     box_offset = np.concatenate([[0], np.cumsum(cnt[scene_index])]).astype(np.int64)
     gt = augment_boxes(sel["center"], sel["size"], sel["heading"], sel["cls"], box_offset, aug)
+    if feats is not None:
+        gt["features"] = feats
     return points, gt, scene_index

@@ -43,21 +43,24 @@ class GeometryGraph:
     generation.  The piece counts still reach the host through mapped pinned ints (the graph's own), the layouts are re-armed with the
     event that follows the replay."""
 
-    def __init__(self, net, x, side):
+    def __init__(self, net, x, side, feats=None):
         self.x = torch.empty_like(x)
+        self.feats = torch.empty_like(feats) if feats is not None else None  # sa1's input features (a net with point_features): its narrow rows are built from them
         self.slots = torch.zeros(16, dtype=torch.int32).pin_memory()
         self.generation = 0
         self.graph = torch.cuda.CUDAGraph()
         g = {}
         # thread_local: a process group's watchdog thread (RCCL, one rank per GPU) queries its events while this thread captures
         with M.layout_slots(self.slots), torch.cuda.graph(self.graph, stream=side, capture_error_mode="thread_local"):
-            net._geometry_chain(self.x, g, None, ("sa1", "sa2", "sa3", "sa4"))
+            net._geometry_chain(self.x, g, None, ("sa1", "sa2", "sa3", "sa4"), self.feats)
         self.g = g
         self.layouts = [t for v in g.values() if isinstance(v, tuple) for t in v if isinstance(t, M.HalfLayout)]
 
-    def replay(self, x, side):
-        """On `side` (current): copy the points in, run the chain -> (g, ev) as _geometry_chain leaves them."""
+    def replay(self, x, side, feats=None):
+        """On `side` (current): copy the points (and sa1's input features) in, run the chain -> (g, ev) as _geometry_chain leaves them."""
         self.x.copy_(x, non_blocking=True)
+        if self.feats is not None:
+            self.feats.copy_(feats, non_blocking=True)
         self.graph.replay()
         done = torch.cuda.Event()
         done.record(side)
@@ -248,14 +251,23 @@ SPLIT_BF16 = True  # fused GEMMs on bf16 x 3 split operands (fp32-accurate produ
 
 
 class VoteNetHotPath:
-    def __init__(self, device, seed=0, npoints=(2048, 1024, 512, 256)):
+    def __init__(self, device, seed=0, npoints=(2048, 1024, 512, 256), point_features=0):
+        """point_features: 0 -- the reference's network: sa1's input features are the coordinates themselves (model.py:36,39) --, or c in
+        1..5: sa1 takes c features per point beside the coordinates (height above the floor, colour, intensity:
+        input_pipeline.subsample_augment_features), handed to forward / predict / train_step as feats (B, n, c).  3 + c <= 8, so sa1
+        keeps its narrow first layer (csrc/narrow.hip); sa1/conv0/W then has 3 + c input rows."""
         self.device = device
+        c = int(point_features)
+        if not 0 <= c <= 5:
+            raise M.L.InvalidArgumentError("VoteNetHotPath: point_features must be in [0, 5] (sa1's narrow first layer serves 3 + c <= 8 "
+                                           "grouped channels), got %r" % (point_features,))
+        self.point_features = c
         self.overlap_wgrad = True  # weight gradients on a second stream, next to the input-gradient chain
         self._wgrad_stream = None
         s = P.ParamStore(device)
         self.store = s
         n1, n2, n3, n4 = npoints
-        self.sa1 = P.SAModule(s, "sa1", n1, 0.2, 64, 3, [64, 64, 128], leaf=True)      # model.py:39 (l0_points = xyz, C=3)
+        self.sa1 = P.SAModule(s, "sa1", n1, 0.2, 64, c if c else 3, [64, 64, 128], leaf=True)  # model.py:39 (l0_points = xyz, C=3)
         self.sa2 = P.SAModule(s, "sa2", n2, 0.4, 64, 128, [128, 128, 256])  # model.py:41
         self.sa3 = P.SAModule(s, "sa3", n3, 0.8, 64, 256, [128, 128, 256])  # model.py:43
         self.sa4 = P.SAModule(s, "sa4", n4, 1.2, 64, 256, [128, 128, 256])  # model.py:45
@@ -279,12 +291,43 @@ class VoteNetHotPath:
             self._side = torch.cuda.Stream(device=self.device, priority=SIDE_PRIORITY)
         return self._side
 
-    def _geometry_chain(self, x, g, ev, levels):
+    def _sa1_points(self, x, feats, what="forward"):
+        """sa1's input features for the batch x: the coordinates themselves (model.py:39), or feats (B, n, point_features) checked."""
+        c = getattr(self, "point_features", 0)
+        if not c:
+            if feats is not None:
+                raise M.L.InvalidArgumentError("%s: feats given to a network built without point features (VoteNetHotPath(point_features=0))" % what)
+            return x
+        if feats is None:
+            raise M.L.InvalidArgumentError("%s: this network was built with point_features=%d: pass feats (B, n, %d)" % (what, c, c))
+        if not torch.is_tensor(feats) or feats.dtype != torch.float32 or feats.device != x.device or tuple(feats.shape) != tuple(x.shape[:2]) + (c,):
+            raise M.L.InvalidArgumentError("%s: feats must be a float32 tensor of shape %s on %s, got %s" % (
+                what, tuple(x.shape[:2]) + (c,), x.device, (tuple(feats.shape), feats.dtype, feats.device) if torch.is_tensor(feats) else type(feats)))
+        if not feats.is_contiguous():
+            raise M.L.InvalidArgumentError("%s: feats must be contiguous" % what)
+        return feats
+
+    @staticmethod
+    def _feats_kw(feats, next_feats):
+        """The feature arguments of an inner call: none at all for a network without point features (the call it always made)."""
+        return {} if feats is None and next_feats is None else dict(feats=feats, next_feats=next_feats)
+
+    @staticmethod
+    def _pair_next(next_x, next_feats):
+        """next_x / next_feats as given to forward() (None, a tensor, or a list of them) -> [(x, feats or None) ...]."""
+        xs = list(next_x) if isinstance(next_x, (list, tuple)) else ([next_x] if next_x is not None else [])
+        fs = list(next_feats) if isinstance(next_feats, (list, tuple)) else ([next_feats] if next_feats is not None else [])
+        if fs and len(fs) != len(xs):
+            raise M.L.InvalidArgumentError("next_feats must match next_x: %d batches, %d feature tensors" % (len(xs), len(fs)))
+        return list(zip(xs, fs if fs else [None] * len(xs)))
+
+    def _geometry_chain(self, x, g, ev, levels, feats=None):
         """FPS / ball query of `levels`, the proposal layer's FPS (it samples the SEEDS, utils.py:42-43) and both three_nn on
         the current stream; an event per level so that a consumer waits only for what it needs."""
         xyz = x if "sa1" in levels else g["sa1"][1]
         for name in levels:
-            g[name] = getattr(self, name).geometry(xyz, points=x if name == "sa1" else None)  # sa1's input features are the coordinates (model.py:39)
+            # sa1's input features are the coordinates (model.py:39), or the caller's feats (point_features)
+            g[name] = getattr(self, name).geometry(xyz, points=(feats if feats is not None else x) if name == "sa1" else None)
             xyz = g[name][1]
             if name == "sa2":  # seeds = l2_xyz: the proposal layer's FPS can start as soon as they exist
                 g["prop_fps"] = P.tf_sampling.farthest_point_sample(self.proposal.npoint, xyz)
@@ -308,7 +351,7 @@ class VoteNetHotPath:
                     for u in getattr(t, "_inv", None) or ():  # the grouping's inverse index rides on idx (mlp.attach_inverse)
                         u.record_stream(main)
 
-    def geometry_ahead(self, x):
+    def geometry_ahead(self, x, feats=None):
         """Every FPS / ball query / three_nn of the backbone depends on coordinates only, never on features.
         Level 1 stays on the caller's stream (the sa1 MLP needs it first); levels 2-4, both three_nn and the
         proposal layer's FPS run on a side HIP stream underneath the MLP GEMMs -- they are latency-bound chains on 8
@@ -316,7 +359,7 @@ class VoteNetHotPath:
         main = torch.cuda.current_stream()
         side = self._side_stream()
         g, ev = {}, {}
-        g["sa1"] = self.sa1.geometry(x, points=x)
+        g["sa1"] = self.sa1.geometry(x, points=self._sa1_points(x, feats, "geometry_ahead"))
         start = torch.cuda.Event()
         start.record(main)
         with torch.cuda.stream(side):
@@ -325,7 +368,7 @@ class VoteNetHotPath:
         self._record_on_main(g, main)
         return g, ev
 
-    def prefetch_geometry(self, next_x):
+    def prefetch_geometry(self, next_x, next_feats=None):
         """Software pipelining across steps: the WHOLE coordinate-only part of an upcoming batch (all four FPS + ball queries,
         the proposal FPS, both three_nn) is launched now on a side stream, underneath this step's GEMMs -- FPS is a
         latency chain on one workgroup per scene (8 of 256 CUs), the one thing a step cannot hide from itself because
@@ -336,7 +379,11 @@ class VoteNetHotPath:
         than one geometry chain, so it wants a lookahead of two.  The input pipeline knows the next batches ahead (the
         reference prefetches them through QueueInput, run.py:121-122)."""
         pool = self.__dict__.setdefault("_prefetched", {})
-        if id(next_x) in pool and pool[id(next_x)][0] is next_x and pool[id(next_x)][1] == next_x._version:
+        pts = self._sa1_points(next_x, next_feats, "prefetch_geometry")
+        next_feats = pts if pts is not next_x else None  # (sa1's narrow rows and their moments are built ahead from the features)
+        had = pool.get(id(next_x))
+        if had is not None and had[0] is next_x and had[1] == next_x._version and (
+                next_feats is None or (had[6] is next_feats and had[7] == next_feats._version)):
             return
         main = torch.cuda.current_stream()
         if getattr(self, "_pf_streams", None) is None:
@@ -344,23 +391,24 @@ class VoteNetHotPath:
             self._pf_turn = 0
         side = self._pf_streams[self._pf_turn]
         self._pf_turn ^= 1
-        gg = self._geometry_graph(next_x, side)
+        gg = self._geometry_graph(next_x, side, next_feats)
         g, ev = {}, {}
         start = torch.cuda.Event()
         start.record(main)  # next_x may have been produced on the main stream; a graph's buffers may still serve the step before
         with torch.cuda.stream(side):
             side.wait_event(start)
             if gg is not None:
-                g, ev = gg.replay(next_x, side)
+                g, ev = gg.replay(next_x, side, next_feats)
             else:
-                self._geometry_chain(next_x, g, ev, ("sa1", "sa2", "sa3", "sa4"))
+                self._geometry_chain(next_x, g, ev, ("sa1", "sa2", "sa3", "sa4"), next_feats)
         if gg is None:
             self._record_on_main(g, main)
         while len(pool) >= (GEOMETRY_RING - 1 if gg is not None else 4):  # never picked up: drop the oldest
             pool.pop(next(iter(pool)))
-        pool[id(next_x)] = (next_x, next_x._version, g, ev, gg, gg.generation if gg is not None else 0)
+        pool[id(next_x)] = (next_x, next_x._version, g, ev, gg, gg.generation if gg is not None else 0,
+                            next_feats, next_feats._version if next_feats is not None else 0)
 
-    def _geometry_graph(self, x, side):
+    def _geometry_graph(self, x, side, feats=None):
         """The next graph of the ring for inputs shaped like x (captured on first use), or None when the chain is enqueued launch by
         launch: graphs off, the deterministic mode (its inverse indices ride on tensors as attributes), a capture under way, per-launch
         profiling events switched on."""
@@ -368,7 +416,7 @@ class VoteNetHotPath:
             return None
         if P.tf_sampling.PROFILE_EVENTS is not None or P.tf_grouping.PROFILE_EVENTS is not None:
             return None  # HIP events around single launches of the chain are wanted (bench.py's roofline legs): they need the launches
-        key = (tuple(x.shape), x.dtype, P.HALF_GROUPS, P.ASSEMBLE_INLINE, self.proposal.npoint)
+        key = (tuple(x.shape), x.dtype, P.HALF_GROUPS, P.ASSEMBLE_INLINE, self.proposal.npoint) + ((tuple(feats.shape),) if feats is not None else ())
         rings = self.__dict__.setdefault("_geometry_rings", {})
         ring = rings.get(key)
         if ring is None:
@@ -387,7 +435,7 @@ class VoteNetHotPath:
             if ring.setdefault("warm", 0) < 1:
                 ring["warm"] += 1
                 return None
-            ring["graphs"].append(GeometryGraph(self, x, side))
+            ring["graphs"].append(GeometryGraph(self, x, side, *([feats] if feats is not None else [])))  # (without features: the three arguments it always took)
             return ring["graphs"][-1]
         gg = ring["graphs"][ring["turn"]]
         ring["turn"] = (ring["turn"] + 1) % GEOMETRY_RING
@@ -395,45 +443,52 @@ class VoteNetHotPath:
             return None
         return gg
 
-    def _take_prefetched(self, x):
+    def _take_prefetched(self, x, feats=None):
+        """The geometry prefetched for exactly this batch, or None: the point tensor AND the feature tensor must be the objects the
+        prefetch saw, unchanged since (_version) -- sa1's narrow rows were built from the features -- and the graph that holds the
+        result must not have served another batch."""
         pf = self.__dict__.setdefault("_prefetched", {}).pop(id(x), None)
         self._geometry_current = None
-        if pf is not None and pf[0] is x and pf[1] == x._version and (pf[4] is None or pf[4].generation == pf[5]):
+        pf_feats, pf_fver = (pf[6], pf[7]) if pf is not None and len(pf) > 6 else (None, 0)
+        if pf is not None and pf[0] is x and pf[1] == x._version and (pf[4] is None or pf[4].generation == pf[5]) and \
+                pf_feats is feats and (feats is None or pf_fver == feats._version):
             self._geometry_current = pf[4]
             return pf[2], pf[3]
         return None
 
-    def backbone(self, x, tape=None, overlap=True, next_x=None):
+    def backbone(self, x, tape=None, overlap=True, next_x=None, feats=None, next_feats=None):
         """model.py:35-50.  x (B,n,3) -> seeds_xyz (B,1024,3), seeds_points (B,1024,256)."""
-        lv, g = self.backbone_levels(x, tape, overlap, next_x)
+        lv, g = self.backbone_levels(x, tape, overlap, next_x, feats, next_feats)
         l3_p2 = self.fp1.forward(lv["l3_xyz"], lv["l4_xyz"], lv["l3_p"], lv["l4_p"], tape=tape, geom=g.get("fp1"))
         seeds_p = self.fp2.forward(lv["l2_xyz"], lv["l3_xyz"], lv["l2_p"], l3_p2, tape=tape, geom=g.get("fp2"))
         return lv["l2_xyz"], seeds_p
 
-    def backbone_levels(self, x, tape=None, overlap=True, next_x=None):
+    def backbone_levels(self, x, tape=None, overlap=True, next_x=None, feats=None, next_feats=None):
         """The four set-abstraction levels of model.py:39-45 (the part of the pass whose row counts depend on the data: the piece layout).
         -> (dict l2_xyz, l2_p, l3_xyz, l3_p, l4_xyz, l4_p; the geometry dict g with the feature-propagation taps "fp1" / "fp2" and the
         proposal layer's "prop_fps" when they were computed ahead).  The current stream has waited for all of g."""
         main = torch.cuda.current_stream()
-        pf = self._take_prefetched(x)
+        pts = self._sa1_points(x, feats)
+        feats = pts if pts is not x else None
+        pf = self._take_prefetched(x, feats)
         if pf is not None:
             g, ev = pf
             main.wait_event(ev["sa1"])
         elif overlap:
-            g, ev = self.geometry_ahead(x)
+            g, ev = self.geometry_ahead(x, feats)
         else:
             g, ev = {}, {}
-        nexts = next_x if isinstance(next_x, (list, tuple)) else ([next_x] if next_x is not None else [])
+        nexts = self._pair_next(next_x, next_feats)
         if PREFETCH_AFTER < 0:
-            for nx in nexts:
-                self.prefetch_geometry(nx)
+            for nx, nf in nexts:
+                self.prefetch_geometry(nx, nf)
         overlap = overlap or pf is not None
         self._prop_fps = g.get("prop_fps")
         def launch_prefetch(after):
             if PREFETCH_AFTER == after:
-                for nx in nexts:
-                    self.prefetch_geometry(nx)
-        l1_xyz, l1_p, _ = self.sa1.forward(x, x, tape=tape, geom=g.get("sa1"))
+                for nx, nf in nexts:
+                    self.prefetch_geometry(nx, nf)
+        l1_xyz, l1_p, _ = self.sa1.forward(x, pts, tape=tape, geom=g.get("sa1"))
         launch_prefetch(1)
         if overlap:
             main.wait_event(ev["sa2"])
@@ -485,13 +540,15 @@ class VoteNetHotPath:
         p_xyz, p_out, _ = self.proposal.forward(votes_xyz, votes_points, sample_xyz=seeds_xyz, tape=tape, geom=geom)
         return p_xyz, p_out
 
-    def forward(self, x, tape=None, next_x=None):
+    def forward(self, x, tape=None, next_x=None, feats=None, next_feats=None):
         """next_x: the batch of the NEXT call (or a list of the next few), if known: their geometry is computed underneath this
-        pass (prefetch_geometry)."""
+        pass (prefetch_geometry).  feats (B, n, point_features) float32: sa1's input features, for a network built with them (an
+        error otherwise, and an error when missing); next_feats: those of next_x (a list when next_x is one)."""
+        self._sa1_points(x, feats)  # (before anything is enqueued)
         self.store.refresh_split()  # bf16 x 3 images of the weights as they are NOW (one launch; no-op unless enable_split())
         M.arena_begin(self.device)  # one fill for all BatchNorm statistics of the pass
         try:
-            lv, g = self.backbone_levels(x, tape, next_x=next_x)
+            lv, g = self.backbone_levels(x, tape, next_x=next_x, feats=feats, next_feats=next_feats)
             self._stamp_tape(tape)
             out = self._head_forward(lv, g.get("fp1"), g.get("fp2"), g.get("prop_fps"), tape,
                                      copy_seeds=getattr(self, "_geometry_current", None) is not None)
@@ -630,21 +687,22 @@ class VoteNetHotPath:
             self._frozen_key = key
         return self._frozen
 
-    def predict(self, x, iou_threshold=0.25, next_x=None, sync=True, batch_statistics=False):
+    def predict(self, x, iou_threshold=0.25, next_x=None, sync=True, batch_statistics=False, feats=None, next_feats=None):
         """Predict tower of model.py:98-139: forward -> decode -> NMS3D(bboxes, max class logit, objectness, 0.25), every
         BatchNorm in inference mode (moving averages, as the reference's BNReLU under `not is_training`): a scene's
         detections do not depend on its batch-mates.  batch_statistics=True normalises with the current batch instead
         (what a model without trained moving averages needs, e.g. random-init benchmarks).
         next_x: the batch(es) of the next call(s), as in forward().  sync=False: nms_idx stays padded on the device with its
-        length in nms_count (no host synchronisation: calls pipeline)."""
+        length in nms_count (no host synchronisation: calls pipeline).  feats / next_feats: as in forward()."""
         from . import tf_nms3d
+        self._sa1_points(x, feats, "predict")
         if not batch_statistics and self._ema_state() is not None and self._ema_version == 0 and not getattr(self, "_warned_ema", False):
             import warnings
             warnings.warn("VoteNetHotPath.predict: no training step has updated the BatchNorm moving averages yet (mean 0, variance 1): "
                           "pass batch_statistics=True for a freshly initialised model", stacklevel=2)
             self._warned_ema = True
         with P.frozen_bn(None if batch_statistics else self.inference_bn()):
-            out = self.forward(x, next_x=next_x)
+            out = self.forward(x, next_x=next_x, **self._feats_kw(feats, next_feats))
         boxes, score = self.decode_boxes(out["proposals_xyz"], out["proposals_output"])
         keep = tf_nms3d.NMS3D(boxes, score, out["proposals_output"][..., :2].contiguous(), iou_threshold, padded=not sync)
         extra = {} if sync else dict(nms_count=keep[1])
@@ -794,11 +852,11 @@ class VoteNetHotPath:
         self._stretch_tail = tail  # (kept: the records own the tensors the captured kernels read)
         return out, losses, grads
 
-    def _train_step_stretch(self, x, gt, tape, next_x):
+    def _train_step_stretch(self, x, gt, tape, next_x, feats=None, next_feats=None):
         """train_step's middle with the stretch replayed as a graph: levels forward (launches: their row counts are the data's) ->
         ONE copy launch + ONE graph launch -> levels backward (launches)."""
         self.store.refresh_split()
-        lv, g = self.backbone_levels(x, tape, next_x=next_x)
+        lv, g = self.backbone_levels(x, tape, next_x=next_x, feats=feats, next_feats=next_feats)
         self._stamp_tape(tape)
         self._grams_ahead(tape)
         if not all(k in g for k in ("fp1", "fp2", "prop_fps")):  # geometry computed without the taps (overlap off): the launch path
@@ -979,11 +1037,13 @@ class VoteNetHotPath:
         """Restore a file written by save(): in place, between two train_step calls or before predict."""
         checkpoint.load(self, path, strict)
 
-    def train_step(self, x, cot=None, world=1, gt=None, next_x=None):
+    def train_step(self, x, cot=None, world=1, gt=None, next_x=None, feats=None, next_feats=None):
         """forward + loss + backward + (world>1: the RCCL all-reduce of the flat gradient bucket, its tail overlapped with the
         backward pass of sa2 / sa1: dp.GradSync) + clip/Adam.
         gt: ground truth on the device (loss.gt_to_device): the reference's total cost (model.py:228) drives the backward
-        pass, its components are left in self.last_losses (device, loss.NAMES).  cot: fixed cotangents instead (tests)."""
+        pass, its components are left in self.last_losses (device, loss.NAMES).  cot: fixed cotangents instead (tests).
+        feats / next_feats: sa1's input features of x / next_x, for a network built with point_features (forward())."""
+        self._sa1_points(x, feats, "train_step")  # (before anything is zeroed or enqueued)
         if not hasattr(self, "_seg"):
             self.init_optimizer()
         self.store.grad.zero_()
@@ -996,9 +1056,9 @@ class VoteNetHotPath:
             if getattr(self, "_gsync", None) is None:
                 self._gsync = dp.GradSync(self.store, self.store.offset_of("sa3/"))
             if self._stretch_eligible(x, cot, gt):
-                out = self._train_step_stretch(x, gt, tape, next_x)
+                out = self._train_step_stretch(x, gt, tape, next_x, **self._feats_kw(feats, next_feats))
             else:
-                out = self.forward(x, tape, next_x=next_x)
+                out = self.forward(x, tape, next_x=next_x, **self._feats_kw(feats, next_feats))
                 self._grams_ahead(tape)
                 self.update_moving_averages(tape)
                 if gt is not None:
@@ -1008,8 +1068,8 @@ class VoteNetHotPath:
                         self.last_accuracies = self.monitors.after_loss(out, gt, self.last_losses)
                 self._gsync.begin()
                 if PREFETCH_AFTER >= 5:  # the next batch's geometry chain under the BACKWARD pass
-                    for nx in (next_x if isinstance(next_x, (list, tuple)) else ([next_x] if next_x is not None else [])):
-                        self.prefetch_geometry(nx)
+                    for nx, nf in self._pair_next(next_x, next_feats):
+                        self.prefetch_geometry(nx, nf)
                 self.backward(tape, cot)            # world > 1: starts the all-reduce of the bucket's tail after sa3's backward
         finally:
             M.arena_end()
