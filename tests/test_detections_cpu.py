@@ -1,0 +1,277 @@
+"""CPU: per-class detections without a device -- the numpy restatement of include/votenet_detections.h (tests/detections_ref.py) over
+the oracle's IoU tables against the reference's own NMS (oracle.nms3d) and the repository's eval_det, hand-built cases for every
+rule, conf_logit, and the C ABI entry points in the header, their derived binding and their argument checks."""
+import ctypes
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import detections_ref as R  # noqa: E402
+
+import cases  # noqa: E402  (tests/golden, on the path by conftest.py)
+from votenet_amd import _lib as L  # noqa: E402
+from votenet_amd import detections as D  # noqa: E402
+
+
+def tables(O, boxes):
+    return np.stack([O.iou3d_matrix(boxes[s]) for s in range(boxes.shape[0])])
+
+
+# ------------------------------------------------------------------ the reference's own algorithm
+@pytest.mark.parametrize("case", ["golden", "random_dense", "random_b5"])
+def test_class_agnostic_mode_is_the_references_nms_per_scene(O, golden, case):
+    """class_nms off, per_class off, conf_thresh 0.5 (T = 0: d > 0 is o1 > o0), scores := d: the kept sequence of every scene is the
+    scene's subsequence of the rows tf_nms3d.cpp:202-273 returns (oracle.nms3d)."""
+    c = dict(golden=cases.nms_random(), random_dense=cases.nms_random(b=3, n=96, seed=41, room=2.5),
+             random_b5=cases.nms_random(b=5, n=40, seed=43, room=3.0))[case]
+    iou = tables(O, c["bboxes"])
+    if case == "golden":  # the boxes of tests/golden/nms_random.npz: the stored table is this one
+        assert np.allclose(iou, golden("nms_random")["iou"], rtol=0, atol=1e-5, equal_nan=True)
+    d = R.margins(c["objectiveness"])
+    assert all(len(np.unique(d[s])) == d.shape[1] for s in range(d.shape[0]))  # no ties: the reference's heap leaves their order open
+    rng = np.random.default_rng(1)
+    cls = rng.normal(size=d.shape + (10,)).astype(np.float32)
+    for thr in (0.1, 0.25, 0.5):
+        exp = O.nms3d(c["bboxes"], d, c["objectiveness"], thr)
+        got = R.class_nms3d(iou, c["objectiveness"], cls, thr, 0.5, class_nms=False, per_class=False, d=d)
+        cand = (c["objectiveness"][..., 1] > c["objectiveness"][..., 0]) & (d > 0)
+        for s in range(d.shape[0]):
+            assert got["kept"][s] == exp[exp[:, 0] == s][:, 1].tolist(), (case, thr, s)
+        assert 0 < len(exp) < int(cand.sum()) or thr > 0.1  # at 0.1 something was suppressed
+        assert got["rows"].shape == (len(exp), 3) and got["det_offset"][-1] == len(exp)
+
+
+# ------------------------------------------------------------------ hand-built cases
+def unit(x, size=1.0):
+    return cases.corner_box(size, size, size, None, (x, 0, 0)).astype(np.float32)
+
+
+def obj_of(d):
+    d = np.asarray(d, np.float32)
+    return np.stack([np.zeros_like(d), d], -1)
+
+
+def onehot(cls, nc=3, hi=4.0):
+    out = np.zeros((len(cls), nc), np.float32)
+    out[np.arange(len(cls)), cls] = hi
+    return out
+
+
+def test_class_wise_keeps_overlapping_boxes_of_different_classes(O):
+    boxes = np.stack([unit(0.0), unit(0.2), unit(5.0)])[None]  # IoU(0, 1) = 0.8 / 1.2
+    iou = tables(O, boxes)
+    assert iou[0, 1, 0] > 0.6 and iou[0, 2, 0] == 0
+    obj, cls = obj_of([[3.0, 2.0, 1.0]]), onehot([0, 1, 0])[None]
+    assert R.class_nms3d(iou, obj, cls, 0.25, 0.05, class_nms=True, per_class=False)["kept"] == [[0, 1, 2]]
+    assert R.class_nms3d(iou, obj, cls, 0.25, 0.05, class_nms=False, per_class=False)["kept"] == [[0, 2]]
+    same = onehot([1, 1, 0])[None]
+    assert R.class_nms3d(iou, obj, same, 0.25, 0.05, class_nms=True, per_class=False)["kept"] == [[0, 2]]
+    # the comparison is strict: at the pair's own overlap as threshold nothing falls
+    assert R.class_nms3d(iou, obj, same, float(iou[0, 1, 0]), 0.05)["kept"] == [[0, 1, 2]]
+
+
+def test_equal_margins_break_by_index_and_nan_is_never_kept(O):
+    boxes = np.stack([unit(0.0), unit(0.2), unit(0.4), unit(9.0)])[None]
+    iou = tables(O, boxes)
+    cls = onehot([0, 0, 0, 0])[None]
+    got = R.class_nms3d(iou, obj_of([[1.0, 2.0, 2.0, 2.0]]), cls, 0.25, 0.05, per_class=False)
+    assert got["kept"] == [[1, 3]]  # visit order 1, 2, 3, 0: box 1 removes 2 (0.8 / 1.2) and 0
+    obj = obj_of([[np.nan, 2.0, 1.0, np.nan]])
+    for c in (0.0, 0.05, 0.5):
+        assert R.class_nms3d(iou, obj, cls, 1.0, c, per_class=False)["kept"] == [[1, 2]]
+    inf = np.array([[[np.inf, np.inf], [0.0, np.inf], [-np.inf, 0.0], [0.0, -np.inf]]], np.float32)  # d = NaN, inf, inf, -inf
+    assert R.class_nms3d(iou, inf, cls, 1.0, 0.0, per_class=False)["kept"] == [[1, 2]]  # -inf > -inf is false
+
+
+def test_a_degenerate_box_neither_falls_nor_suppresses(O):
+    flat = np.zeros((8, 3), np.float32)  # no volume: every overlap with it is 0 or NaN
+    boxes = np.stack([flat, unit(0.0), flat, unit(0.1)])[None]
+    iou = tables(O, boxes)
+    assert not (iou[0, [0, 2]] > 0).any() and not (iou[0, :, [0, 2]] > 0).any()
+    cls = onehot([0, 0, 0, 0])[None]
+    got = R.class_nms3d(iou, obj_of([[4.0, 3.0, 2.0, 1.0]]), cls, 0.0, 0.05, per_class=False)  # threshold 0: any overlap removes
+    assert got["kept"] == [[0, 1, 2]]
+
+
+def test_conf_thresh_zero_keeps_a_box_far_below_and_the_default_drops_it(O):
+    boxes = np.stack([unit(0.0), unit(3.0)])[None]
+    iou = tables(O, boxes)
+    obj, cls = obj_of([[-50.0, 1.0]]), onehot([0, 1])[None]
+    got = R.class_nms3d(iou, obj, cls, 0.25, 0.0, per_class=False)
+    assert got["kept"] == [[1, 0]] and 0 < got["score"][1] < 1e-20
+    assert R.class_nms3d(iou, obj, cls, 0.25, 0.05, per_class=False)["kept"] == [[1]]
+    # P(object) = 0.05 sits at d = -2.944...: one box either side
+    obj = obj_of([[-2.95, -2.94]])
+    assert R.class_nms3d(iou, obj, cls, 0.25, 0.05, per_class=False)["kept"] == [[1]]
+
+
+def test_emission_order_offsets_and_scores_with_empty_scenes(O):
+    """Scenes 0, 2 and 4 have no candidate (first, middle, last).  Rows: scene, then visit order, then class."""
+    boxes = np.stack([np.stack([unit(0.0), unit(0.2), unit(4.0)])] * 5)
+    iou = tables(O, boxes)
+    obj = obj_of([[-9.0, -9.0, -9.0], [1.0, 2.0, 3.0], [np.nan, -9.0, -8.0], [0.5, -0.5, 0.25], [-7.0, -7.0, -7.0]])
+    rng = np.random.default_rng(3)
+    cls = rng.normal(size=(5, 3, 4)).astype(np.float32)
+    got = R.class_nms3d(iou, obj, cls, 0.25, 0.05, class_nms=False, per_class=True)
+    # scene 1: box 1 removes box 0; scene 3: d = -0.5 is a candidate at 0.05 (T = -2.94) and falls to box 0
+    assert got["kept"] == [[], [2, 1], [], [0, 2], []]
+    assert got["det_offset"].tolist() == [0, 0, 8, 8, 16, 16]
+    assert got["rows"].tolist() == [[s, b, c] for s, bs in ((1, (2, 1)), (3, (0, 2))) for b in bs for c in range(4)]
+    for k, (s, b, c) in enumerate(got["rows"]):
+        l = cls[s, b].astype(np.float64)
+        p = np.exp(l[c]) / np.exp(l).sum() / (1.0 + np.exp(-np.float64(np.float32(obj[s, b, 1]))))
+        assert abs(got["score"][k] - p) < 1e-12 * p
+    one = R.class_nms3d(iou, obj, cls, 0.25, 0.05, class_nms=False, per_class=False)
+    assert one["det_offset"].tolist() == [0, 0, 2, 2, 4, 4]
+    assert one["rows"].tolist() == [[1, 2, cls[1, 2].argmax()], [1, 1, cls[1, 1].argmax()], [3, 0, cls[3, 0].argmax()], [3, 2, cls[3, 2].argmax()]]
+    assert np.allclose(one["score"], 1.0 / (1.0 + np.exp(-np.array([3.0, 2.0, 0.5, 0.25]))), rtol=1e-12, atol=0)
+
+
+def test_argmax_ignores_nan_and_an_all_nan_row_is_class_zero():
+    nan = np.float32(np.nan)
+    assert R.argmax_first(np.array([nan, 1.0, 3.0, 3.0], np.float32)) == (2, 3.0)
+    assert R.argmax_first(np.array([2.0, nan, 2.0], np.float32)) == (0, 2.0)
+    a, best = R.argmax_first(np.array([nan, nan], np.float32))
+    assert a == 0 and best != best
+
+
+# ------------------------------------------------------------------ conf_logit
+def test_conf_logit():
+    for f in (D.conf_logit, R.conf_logit):
+        assert f(0) == -np.inf and f(0.5) == 0.0
+        grid = [f(c) for c in np.linspace(0.0, 0.999, 200)]
+        assert all(a < b for a, b in zip(grid, grid[1:]))  # monotone
+        assert abs(f(0.05) - np.log(0.05 / 0.95)) < 1e-6
+        assert np.float32(f(0.3)) == f(0.3)  # a float32 value
+    assert all(D.conf_logit(c) == float(R.conf_logit(c)) for c in (0.0, 0.01, 0.05, 0.25, 0.5, 0.9))
+    for bad in (-0.1, 1.0, 1.5, float("nan")):
+        with pytest.raises(L.InvalidArgumentError, match="conf_thresh"):
+            D.conf_logit(bad)
+
+
+def test_protocol_params():
+    assert D.protocol_params("reference") is None
+    assert D.protocol_params("per_class") == dict(iou_threshold=0.25, conf_thresh=0.05, class_nms=True, per_class=True)
+    assert D.protocol_params("per_class", 0.4)["iou_threshold"] == 0.4
+    assert D.protocol_params(dict(conf_thresh=0.0, per_class=False), 0.3) == dict(iou_threshold=0.3, conf_thresh=0.0, class_nms=True, per_class=False)
+    for bad in ("paper", None, dict(conf=0.1)):
+        with pytest.raises(L.InvalidArgumentError, match="protocol"):
+            D.protocol_params(bad)
+
+
+# ------------------------------------------------------------------ the matcher
+@pytest.mark.parametrize("seed,round_scores", [(0, False), (1, True)])
+def test_restated_matcher_equals_eval_det(O, monkeypatch, seed, round_scores):
+    """One row per kept box, class = arg-max, score = max logit: the restated evaluation over rows is the repository's eval_det
+    (votenet_amd/evaluator.py), fed the same overlap table.  Rounded scores: ties, broken by arrival on both sides."""
+    from votenet_amd import evaluator as E
+    rng = np.random.default_rng(seed)
+    B, N, G, NC = 3, 24, 6, 10
+    mk = lambda n: E.box_corners(rng.random((B, n, 3)) * [2.5, 1, 2.5], rng.random((B, n, 3)) * 0.6 + 0.4, rng.random((B, n)) * 6.28)
+    det, gtb = mk(N), mk(G)
+    src = rng.integers(0, G, (B, 12))  # half the detections sit on a ground-truth box, several on the same one, its class on top
+    det[:, :12] = gtb[np.arange(B)[:, None], src] + rng.normal(size=(B, 12, 1, 3)).astype(np.float32) * 0.03
+    count = np.array([G, 3, 0])
+    labels = rng.integers(0, 3, (B, G)).astype(np.int32)
+    logits = rng.normal(size=(B, N, NC)).astype(np.float32)
+    logits[np.arange(B)[:, None], np.arange(12)[None], labels[np.arange(B)[:, None], src]] += 3.0
+    if round_scores:
+        logits = np.round(logits, 0).astype(np.float32)
+    table = np.stack([O.iou3d_matrix(np.concatenate([det[s], gtb[s]]))[:N, N:] for s in range(B)])
+    monkeypatch.setattr(E.tf_nms3d, "iou3d_cross", lambda a, b: torch.from_numpy(table))
+    keep = np.array([[s, i] for s in range(B) for i in np.nonzero(rng.random(N) < 0.7)[0]], np.int32)
+    keep = keep[rng.permutation(len(keep))]
+    pred = dict(bboxes=torch.from_numpy(det), nms_idx=torch.from_numpy(keep), class_scores=torch.from_numpy(logits))
+    gt = dict(boxes=gtb, labels=labels, count=count)
+    cls = logits[keep[:, 0], keep[:, 1]].argmax(-1)
+    score = logits[keep[:, 0], keep[:, 1]].max(-1)
+    for thr in (0.25, 0.5):
+        ap, m = E.eval_det(pred, gt, thr)
+        got = R.eval_rows(keep[:, 0], keep[:, 1], cls, score, table, labels, count, NC, thr)
+        assert sorted(got["ap"]) == sorted(ap) and len(ap) >= 2
+        assert all(abs(got["ap"][c] - ap[c]) <= 1e-12 for c in ap) and abs(got["mAP"] - m) <= 1e-12
+        assert got["tp"].any() and not got["tp"].all()
+        assert got["npos"].tolist() == [sum(int((labels[s, :count[s]] == c).sum()) for s in range(B)) for c in range(NC)]
+
+
+# ------------------------------------------------------------------ the C ABI
+NAMES = ["votenet_class_nms3d", "votenet_class_nms3d_workspace_bytes", "votenet_detections_last_error", "votenet_eval_match_rows"]
+
+
+def test_header_declares_the_entries_and_the_binding_follows_it():
+    inc = os.path.join(os.path.dirname(L.__file__), os.pardir, "include")
+    with open(os.path.join(inc, "votenet_detections.h")) as f:
+        protos = L.parse_header(f.read(), {})
+    assert sorted(protos) == NAMES
+    ret, args = protos["votenet_class_nms3d"]
+    assert ret is ctypes.c_int and args == [ctypes.c_int] * 3 + [ctypes.c_void_p] * 3 + [ctypes.c_float] * 2 + [ctypes.c_int] * 2 + \
+        [ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    assert protos["votenet_class_nms3d_workspace_bytes"] == (ctypes.c_size_t, [ctypes.c_int] * 3)
+    base = L._abi()[0]["votenet_eval_match"][1]  # the sibling entry: the same accumulator arguments from nthr on
+    assert protos["votenet_eval_match_rows"][1][-11:] == base[-11:] and len(protos["votenet_eval_match_rows"][1]) == 21
+
+
+def test_library_exports_exactly_its_header_and_checks_its_arguments(hiplib):
+    """Every invalid-argument case returns before anything is launched, with the limit in the text: no device is needed."""
+    lib = L.detect_lib()
+    out = subprocess.run(["nm", "-D", "--defined-only", L._DETECT_PATH], capture_output=True, text=True, check=True).stdout
+    assert sorted(line.split()[-1] for line in out.splitlines()) == NAMES
+    main = subprocess.run(["nm", "-D", "--defined-only", L.lib_path()], capture_output=True, text=True, check=True).stdout
+    assert not any(n in main for n in NAMES)  # the drop-in library's export list is what it was
+    buf = np.zeros(4096, np.float32)
+    p = buf.ctypes.data
+    err = lambda: lib.votenet_detections_last_error().decode()
+
+    def nms(b=2, n=16, nc=10, thr=0.25, t=0.0, cn=1, pc=1, cap=None, rows=p, off=p, ws=p, wsb=1 << 20):
+        return lib.votenet_class_nms3d(b, n, nc, p, p, p, thr, t, cn, pc, rows, b * n * nc if cap is None else cap, off, ws, wsb, None)
+    for kw, text in ((dict(n=513), "at most 512 boxes"), (dict(nc=65), "[1, 64]"), (dict(nc=0), "[1, 64]"), (dict(thr=1.5), "[0, 1]"),
+                     (dict(thr=-0.1), "[0, 1]"), (dict(thr=float("nan")), "[0, 1]"), (dict(t=float("nan")), "conf_logit"),
+                     (dict(t=float("inf")), "conf_logit"), (dict(cn=2), "0 or 1"), (dict(cap=2 * 16 * 10 - 1), "320 rows"),
+                     (dict(pc=0, cap=31), "32 rows"), (dict(off=None), "det_offset"), (dict(rows=None), "null"),
+                     (dict(rows=p + 4), "16-byte"), (dict(b=-1), "batch")):
+        assert nms(**kw) == 1, kw
+        assert text in err(), (kw, err())
+    need = lib.votenet_class_nms3d_workspace_bytes(2, 16, 10)
+    assert need >= 2 * 16 * 4 + 2 * 4 and lib.votenet_class_nms3d_workspace_bytes(0, 0, 1) > 0
+    assert nms(wsb=need - 1) == 3 and "workspace of %d bytes required" % need in err()
+    assert nms(ws=None) == 3 and "workspace of %d bytes required" % need in err()
+    with pytest.raises(L.VotenetError, match="workspace of %d bytes" % need):
+        L.check_detect(nms(wsb=0))
+    with pytest.raises(L.InvalidArgumentError, match="at most 512 boxes per scene, got n = 513"):
+        L.check_detect(nms(n=513))
+
+    thr2 = (ctypes.c_float * 2)(0.25, 0.5)
+
+    def match(b=2, n=16, g=4, nc=10, nthr=2, thr=thr2, nrows=320, scene0=0, arrival0=0, cap=64, rec=p, rows=p):
+        return lib.votenet_eval_match_rows(b, n, g, nc, p, rows, nrows, p, p, p, p, nthr, thr, scene0, arrival0, rec, cap, p, p, p, None)
+    for kw, text in ((dict(n=1025), "1 to 1024 boxes"), (dict(n=0), "1 to 1024 boxes"), (dict(g=4097), "4096"), (dict(nc=257), "[1, 256]"),
+                     (dict(nthr=9), "1 to 8"), (dict(thr=None), "thresholds"), (dict(nrows=-1), "negative"), (dict(cap=-1), "negative"),
+                     (dict(scene0=2 ** 31 - 2), "31 bits"), (dict(arrival0=2 ** 32 - 1), "32 bits"), (dict(rec=None), "null accumulator"),
+                     (dict(rows=None), "null detection rows"), (dict(rows=p + 8), "16-byte"), (dict(b=65536), "batch")):
+        assert match(**kw) == 1, kw
+        assert text in err(), (kw, err())
+    assert match(b=0) == 0
+
+
+def test_build_force_also_removes_the_detect_library_and_its_objects(monkeypatch, tmp_path):
+    from votenet_amd import _lib
+    here = tmp_path / "votenet_amd"
+    (here / "csrc" / "detect" / "obj").mkdir(parents=True)
+    (here / "lib").mkdir()
+    for f in (here / "csrc" / "detect" / "obj" / "detections.o", here / "lib" / "libvotenet_detect.so", here / "lib" / "libvotenet_hip.so"):
+        f.write_bytes(b"stale")
+    seen = {}
+
+    def fake_run(cmd, **kw):
+        seen["left"] = sorted(p.name for d in ("csrc/detect/obj", "lib") for p in (here / d).iterdir())
+        return subprocess.CompletedProcess(cmd, 0, "", "")
+    monkeypatch.setattr(_lib, "_HERE", str(here))
+    monkeypatch.setattr(_lib, "_LIB_PATH", str(here / "lib" / "libvotenet_hip.so"))
+    monkeypatch.setattr(_lib.subprocess, "run", fake_run)
+    _lib.build(force=True)
+    assert seen["left"] == []

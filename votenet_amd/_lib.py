@@ -20,6 +20,8 @@ _lib = None
 _mon = None
 _guard = None
 _feat = None
+_DETECT_PATH = os.path.join(_HERE, "lib", "libvotenet_detect.so")  # per-class detections (include/votenet_detections.h): likewise
+_detect = None
 
 
 class VotenetError(RuntimeError):
@@ -41,7 +43,9 @@ def build(force=False):
         mon = os.path.join(os.path.dirname(_LIB_PATH), os.path.basename(_MON_PATH))
         guard = os.path.join(os.path.dirname(_LIB_PATH), os.path.basename(_GUARD_PATH))
         feat = os.path.join(os.path.dirname(_LIB_PATH), os.path.basename(_FEAT_PATH))
-        for f in [_LIB_PATH, mon, guard, feat] + [o for d in ("obj", os.path.join("monitors", "obj"), os.path.join("guard", "obj"), os.path.join("features", "obj"))
+        detect = os.path.join(os.path.dirname(_LIB_PATH), os.path.basename(_DETECT_PATH))
+        for f in [_LIB_PATH, mon, guard, feat, detect] + [o for d in ("obj", os.path.join("monitors", "obj"), os.path.join("guard", "obj"), os.path.join("features", "obj"),
+                                                                 os.path.join("detect", "obj"))
                                             for o in glob.glob(os.path.join(_HERE, "csrc", d, "*.o"))]:
             if os.path.exists(f):
                 os.remove(f)
@@ -217,6 +221,34 @@ def features_lib():
             fn.restype, fn.argtypes = restype, argtypes
         _feat = F
     return _feat
+
+
+def detect_lib():
+    """libvotenet_detect.so, loaded when per-class detections are first asked for; every function of include/votenet_detections.h gets
+    its header's prototype (parse_header, as for the main library).  No fallback: a missing library is an error."""
+    global _detect
+    if _detect is None:
+        if not os.path.exists(_DETECT_PATH):
+            raise VotenetError("libvotenet_detect.so not found at %s -- run `python -c 'import __graft_entry__ as g; g.build()'` "
+                               "(there is no CPU fallback)" % _DETECT_PATH)
+        with open(os.path.join(_HERE, os.pardir, "include", "votenet_detections.h")) as f:
+            protos = parse_header(f.read(), {})
+        D = ctypes.CDLL(_DETECT_PATH)
+        for name, (restype, argtypes) in protos.items():
+            fn = getattr(D, name)
+            fn.restype, fn.argtypes = restype, argtypes
+        _detect = D
+    return _detect
+
+
+def check_detect(rc):
+    """check() for a status libvotenet_detect.so returned (it keeps its own error text)."""
+    if rc == 0:
+        return
+    msg = detect_lib().votenet_detections_last_error().decode()
+    if rc == 1:
+        raise InvalidArgumentError(msg)
+    raise VotenetError("libvotenet_detect error %d: %s" % (rc, msg))
 
 
 def check_features(rc):

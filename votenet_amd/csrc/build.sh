@@ -83,3 +83,20 @@ $HIPCC --offload-arch=gfx950 -shared -fPIC -Wl,--version-script="$HERE/features/
 python3 "$HERE/../../tools/check_isa_hazards.py" "$FTMP"
 mv -f "$FTMP" "$OUT/libvotenet_features.so"
 echo "built $OUT/libvotenet_features.so"
+# libvotenet_detect.so (include/votenet_detections.h): class-wise 3D NMS, per-class detections and their matching, a library of its own
+# for the same reason.  Same flags, same gate; iou3d.h is the text of votenet_iou3d_matrix's overlaps, so both libraries decide on the
+# same bits.
+DOBJ="$HERE/detect/obj/detections.o"
+mkdir -p "$HERE/detect/obj"
+if [ ! -f "$DOBJ" ] || [ "$HERE/detect/detections.hip" -nt "$DOBJ" ] || [ "$HERE/iou3d.h" -nt "$DOBJ" ] \
+   || [ "$HERE/common.h" -nt "$DOBJ" ] || [ "$HERE/../../include/votenet_detections.h" -nt "$DOBJ" ] \
+   || [ "$HERE/../../include/votenet_hip.h" -nt "$DOBJ" ] || [ "$HERE/../../include/votenet_hip_debug.h" -nt "$DOBJ" ] \
+   || [ "${BASH_SOURCE[0]}" -nt "$DOBJ" ]; then
+  $HIPCC $FLAGS -c "$HERE/detect/detections.hip" -o "$DOBJ"
+fi
+DTMP="$OUT/.libvotenet_detect.so.tmp.$$"
+trap 'rm -f "$TMP" "$MTMP" "$GTMP" "$FTMP" "$DTMP"' EXIT
+$HIPCC --offload-arch=gfx950 -shared -fPIC -Wl,--version-script="$HERE/detect/exports.map" "$DOBJ" -o "$DTMP"
+python3 "$HERE/../../tools/check_isa_hazards.py" "$DTMP"
+mv -f "$DTMP" "$OUT/libvotenet_detect.so"
+echo "built $OUT/libvotenet_detect.so"

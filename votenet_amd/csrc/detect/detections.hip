@@ -1,0 +1,423 @@
+// detections.hip -- libvotenet_detect.so (include/votenet_detections.h), a library of its own beside libvotenet_hip.so (whose export
+// list is the drop-in ABI of the reference's ops and stays what it was): the VoteNet paper's detection protocol on the device.
+//   votenet_class_nms3d       class-wise greedy NMS ordered by objectness, a confidence threshold, one detection per class and kept
+//                             box, scored P(object) * P(class).  class_nms_kernel (one workgroup per scene), det_emit_kernel.
+//   votenet_eval_match_rows   votenet_eval_match (../eval_match.hip) on those rows: one workgroup per (scene, class).
+// The overlaps are iou3d_pair of ../iou3d.h, the one text nms3d.hip and eval_match.hip compile, under the same flags: a decision here
+// is the decision votenet_iou3d_matrix / votenet_iou3d_cross would tabulate.
+#include "../common.h"
+#include "../iou3d.h"
+
+#include <climits>
+#pragma GCC visibility push(default)
+#include "../../../include/votenet_detections.h"
+#pragma GCC visibility pop
+
+namespace votenet {
+
+// ---- error plumbing of this library (thread-local text behind votenet_detections_last_error()) ----
+static thread_local char g_det_err[512] = "";
+static int det_set_error(int code, const char *fmt, ...)
+{
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_det_err, sizeof(g_det_err), fmt, ap);
+    va_end(ap);
+    return code;
+}
+static int det_check_launch(const char *what)
+{
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return det_set_error(VOTENET_E_HIP, "%s: %s", what, hipGetErrorString(e));
+    return VOTENET_OK;
+}
+#define DET_REQUIRE(cond, ...)                                                              \
+    do {                                                                                    \
+        if (!(cond)) return ::votenet::det_set_error(VOTENET_E_INVALID_ARGUMENT, __VA_ARGS__); \
+    } while (0)
+
+// ---- votenet_class_nms3d ----
+constexpr int DET_MAX_N = 512;       // boxes of one scene: one thread each, the suppression rows fit LDS (512 x 8 words = 32 KiB)
+constexpr int DET_MAX_NC = 64;
+constexpr int DET_NMS_THREADS = 512; // >= DET_MAX_N
+constexpr int DET_MAX_W = DET_MAX_N / 64;
+
+// the first largest logit; a NaN never wins over a number (eval_match.hip's rule).  All NaN: class 0, best = NaN.
+__device__ __forceinline__ int argmax_first(const float *__restrict__ cs, int nc, float &best)
+{
+    best = cs[0];
+    int arg = 0;
+    for (int c = 1; c < nc; c++) {
+        const float v = cs[c];
+        if (v > best || (best != best && v == v)) best = v, arg = c;
+    }
+    return arg;
+}
+
+// One workgroup per scene, thread t owns box t.
+//   (a) d = o1 - o0, cls, candidate = d > conf_logit;
+//   (b) visit order: rank by counting over the scene's d in LDS (d descending, equal d by box index): every candidate its own rank;
+//   (c) suppression rows as nms_greedy_mask_kernel builds them -- bit j of row i = candidate j comes later, (has i's class,) and
+//       iou3d_pair(box_j, box_i) > thr -- a wave per row, a lane per later candidate, the word is the ballot of the comparisons.  The
+//       polygon clip runs for the pairs the class rule leaves, inside the ballot: no table;
+//   (d) wave 0 passes over the rows once: a candidate is kept iff no kept candidate has removed it.  The kept boxes go to
+//       kept[scene * n ..] in visit order, their number to count[scene].
+__global__ __launch_bounds__(DET_NMS_THREADS) void class_nms_kernel(int n, int nc, const float *__restrict__ bboxes,
+                                                                    const float *__restrict__ obj,
+                                                                    const float *__restrict__ class_scores, float thr,
+                                                                    float conf_logit, int class_nms, int *__restrict__ kept,
+                                                                    int *__restrict__ count)
+{
+    __shared__ unsigned long long s_mask[DET_MAX_N * DET_MAX_W]; // L rows x W words
+    __shared__ float s_d[DET_MAX_N];
+    __shared__ int s_cand[DET_MAX_N];
+    __shared__ int s_list[DET_MAX_N]; // box of the r-th candidate in visit order
+    __shared__ int s_lcls[DET_MAX_N]; // ... and its class
+    __shared__ int s_len;
+    const int scene = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    if (tid == 0) s_len = 0;
+    float d = 0.0f;
+    bool cand = false;
+    int cls = 0;
+    if (tid < n) {
+        const float *__restrict__ o = obj + ((size_t)scene * n + tid) * 2;
+        d = o[1] - o[0];
+        cand = d > conf_logit; // false for a NaN d
+        float best;
+        cls = argmax_first(class_scores + ((size_t)scene * n + tid) * nc, nc, best);
+        s_d[tid] = d;
+        s_cand[tid] = cand ? 1 : 0;
+    }
+    __syncthreads();
+    if (cand) {
+        int rank = 0;
+        for (int e = 0; e < n; e++) {
+            const float de = s_d[e];
+            if (s_cand[e] && (de > d || (de == d && e < tid))) rank++;
+        }
+        s_list[rank] = tid;
+        s_lcls[rank] = cls;
+        atomicAdd(&s_len, 1);
+    }
+    __syncthreads();
+    const int L = s_len, W = (L + 63) / 64;
+    const float *__restrict__ base = bboxes + (size_t)scene * n * 24;
+    for (int i = w; i < L; i += DET_NMS_THREADS / 64) {
+        const int ci = s_lcls[i];
+        const float *__restrict__ pe = base + (size_t)s_list[i] * 24;
+        const int w0 = i >> 6; // the words before it hold earlier candidates only
+        if (lane < w0) s_mask[(size_t)i * W + lane] = 0ull;
+        for (int wd = w0; wd < W; wd++) {
+            const int j = wd * 64 + lane;
+            const bool need = j > i && j < L && (!class_nms || s_lcls[j] == ci);
+            bool hit = false;
+            if (need) {
+                const float *__restrict__ pl = base + (size_t)s_list[j] * 24;
+                float bl[24], be[24];
+#pragma unroll
+                for (int t = 0; t < 24; t++) {
+                    bl[t] = pl[t];
+                    be[t] = pe[t];
+                }
+                hit = iou3d_pair(bl, be) > thr; // the later box first (nms3d.hip:130-134); strict; a NaN overlap is no hit
+            }
+            const unsigned long long m = __ballot(hit);
+            if (lane == 0) s_mask[(size_t)i * W + wd] = m;
+        }
+    }
+    __syncthreads();
+    if (w == 0) { // lane wd owns word wd of the removed set
+        unsigned long long removed = 0ull;
+        int nk = 0;
+        for (int i = 0; i < L; i++) {
+            const unsigned long long cur = __shfl(removed, i >> 6);
+            if (!((cur >> (i & 63)) & 1ull)) { // uniform
+                if (lane < W) removed |= s_mask[(size_t)i * W + lane];
+                if (lane == 0) kept[(size_t)scene * n + nk] = s_list[i];
+                nk++;
+            }
+        }
+        if (lane == 0) count[scene] = nk;
+    }
+}
+
+// One workgroup per scene: its first row = (kept boxes of the scenes before it) x rows per box, then the scores and the rows.
+__global__ __launch_bounds__(256) void det_emit_kernel(int b, int n, int nc, const float *__restrict__ obj,
+                                                       const float *__restrict__ class_scores, int per_class,
+                                                       const int *__restrict__ kept, const int *__restrict__ count,
+                                                       uint4 *__restrict__ rows, int *__restrict__ det_offset)
+{
+    __shared__ float s_pobj[DET_MAX_N], s_max[DET_MAX_N], s_sum[DET_MAX_N];
+    __shared__ int s_cls[DET_MAX_N], s_box[DET_MAX_N];
+    __shared__ int s_before;
+    const int scene = blockIdx.x, tid = threadIdx.x;
+    const int R = per_class ? nc : 1;
+    if (tid == 0) s_before = 0;
+    __syncthreads();
+    int part = 0;
+    for (int s = tid; s < scene; s += 256) part += count[s];
+    if (part) atomicAdd(&s_before, part); // an integer sum: the order does not matter
+    __syncthreads();
+    const int K = count[scene];
+    const int off = s_before * R;
+    if (tid == 0) {
+        det_offset[scene] = off;
+        if (scene == b - 1) det_offset[b] = off + K * R;
+    }
+    for (int k = tid; k < K; k += 256) {
+        const int box = kept[(size_t)scene * n + k];
+        const float *__restrict__ o = obj + ((size_t)scene * n + box) * 2;
+        const float d = o[1] - o[0];
+        const float *__restrict__ cs = class_scores + ((size_t)scene * n + box) * nc;
+        float best;
+        s_cls[k] = argmax_first(cs, nc, best);
+        float sum = 0.0f;
+        if (per_class)
+            for (int c = 0; c < nc; c++) sum += expf(cs[c] - best);
+        s_box[k] = box;
+        s_pobj[k] = 1.0f / (1.0f + expf(-d));
+        s_max[k] = best;
+        s_sum[k] = sum;
+    }
+    __syncthreads();
+    const int total = K * R;
+    for (int r = tid; r < total; r += 256) {
+        const int k = r / R, c = r - k * R;
+        int cls = s_cls[k];
+        float score = s_pobj[k];
+        if (per_class) {
+            cls = c;
+            score = score * (expf(class_scores[((size_t)scene * n + s_box[k]) * nc + c] - s_max[k]) / s_sum[k]);
+        }
+        rows[(size_t)off + r] = make_uint4((unsigned)scene, (unsigned)s_box[k], (unsigned)cls, __float_as_uint(score));
+    }
+}
+
+static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// ---- votenet_eval_match_rows: eval_match.hip's steps (b)-(f) for one (scene, class) ----
+constexpr int EVAL_MAX_DET = 1024; // rows of one scene and class: one per box
+constexpr int EVAL_MAX_GT = 4096;
+constexpr int EVAL_MAX_NC = 256; // the class travels in 8 bits of the record
+constexpr int EVAL_MAX_THR = 8;
+struct EvalThr {
+    float t[EVAL_MAX_THR];
+};
+constexpr int EVAL_F_OVERFLOW = 1, EVAL_F_BAD_ROW = 2, EVAL_F_SCENE = 4; // eval_match.hip's flags word
+
+// float bits -> unsigned that orders like the float (no NaN reaches this); eval_match.hip's key
+__device__ __forceinline__ unsigned ordered_bits(float v)
+{
+    const unsigned u = __float_as_uint(v);
+    return (u >> 31) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float from_ordered_bits(unsigned o) { return __uint_as_float((o >> 31) ? (o & 0x7fffffffu) : ~o); }
+
+__global__ __launch_bounds__(256) void eval_match_rows_kernel(int n, int g, int nc, const float *__restrict__ bboxes,
+                                                              const int4 *__restrict__ rows, long nrows,
+                                                              const int *__restrict__ det_offset,
+                                                              const float *__restrict__ gt_boxes, const int *__restrict__ gt_labels,
+                                                              const int *__restrict__ gt_count, EvalThr thr, int nthr, int scene0,
+                                                              unsigned arrival0, uint4 *__restrict__ records, int capacity,
+                                                              int *__restrict__ rec_count, int *__restrict__ npos,
+                                                              int *__restrict__ flags)
+{
+    __shared__ int s_box[EVAL_MAX_DET];                // box of the d-th row of this scene and class
+    __shared__ unsigned s_row[EVAL_MAX_DET];           // ... and its row index in the call
+    __shared__ float s_score[EVAL_MAX_DET];            // its score (NaN -> -inf: a total order)
+    __shared__ unsigned long long s_key[EVAL_MAX_DET]; // (ordered ovmax, ~jmax); 0 = no overlap seen
+    __shared__ int s_nan[EVAL_MAX_DET];
+    __shared__ int s_jmax[EVAL_MAX_DET];
+    __shared__ int s_qmask[EVAL_MAX_DET]; // {t : ovmax > thr[t]}
+    __shared__ int s_gtlist[EVAL_MAX_GT]; // the scene's valid ground-truth rows of this class
+    __shared__ int s_wcnt[4], s_len, s_ngc, s_base;
+    const int cls = blockIdx.x, scene = blockIdx.y, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    int flag = 0;
+    long lo = det_offset[scene], hi = det_offset[scene + 1];
+    if (lo < 0 || hi < lo || hi > nrows) { // offsets that do not ascend inside the buffer: the scene is skipped
+        flag |= EVAL_F_BAD_ROW;
+        lo = hi = 0;
+    }
+    if (tid == 0) s_len = 0, s_ngc = 0;
+    __syncthreads();
+    // (a) this scene's rows of this class, in row order
+    for (long start = lo; start < hi; start += 256) {
+        const long p = start + tid;
+        bool mine = false;
+        int box = 0;
+        float score = 0.0f;
+        if (p < hi) {
+            const int4 r = rows[p];
+            if (r.x != scene || r.y < 0 || r.y >= n || r.z < 0 || r.z >= nc)
+                flag |= EVAL_F_BAD_ROW;
+            else if (r.z == cls)
+                mine = true, box = r.y, score = __int_as_float(r.w);
+        }
+        const unsigned long long bal = __ballot(mine);
+        if (lane == 0) s_wcnt[w] = __popcll(bal);
+        __syncthreads();
+        int woff = 0, tot = 0;
+        for (int i = 0; i < 4; i++) {
+            if (i < w) woff += s_wcnt[i];
+            tot += s_wcnt[i];
+        }
+        const int base = s_len;
+        if (mine) {
+            const int q = base + woff + __popcll(bal & ((1ull << lane) - 1ull));
+            if (q < EVAL_MAX_DET) {
+                s_box[q] = box, s_row[q] = (unsigned)p;
+                s_score[q] = score != score ? -__builtin_inff() : score;
+                s_key[q] = 0ull;
+                s_nan[q] = 0;
+            }
+        }
+        __syncthreads();
+        if (tid == 0) s_len = base + tot;
+        __syncthreads();
+    }
+    int L = s_len;
+    if (L > EVAL_MAX_DET) {
+        L = EVAL_MAX_DET;
+        flag |= EVAL_F_SCENE;
+    }
+    if (flag) atomicOr(flags, flag);
+    // (b) ground truth of this class: rows beyond count are padding.  Any order: the key carries j
+    int ngt = g > 0 ? gt_count[scene] : 0;
+    ngt = ngt < 0 ? 0 : (ngt > g ? g : ngt);
+    for (int j = tid; j < ngt; j += 256)
+        if (gt_labels[(size_t)scene * g + j] == cls) s_gtlist[atomicAdd(&s_ngc, 1)] = j;
+    __syncthreads();
+    const int ngc = s_ngc;
+    if (tid == 0) {
+        if (ngc) atomicAdd(&npos[cls], ngc);
+        s_base = L ? atomicAdd(rec_count, L) : 0; // every record offered is counted, also the ones a full buffer drops
+    }
+    // (d) one overlap per (detection, ground truth of its class and scene)
+    const int npair = L * ngc;
+    for (int p = tid; p < npair; p += 256) {
+        const int d = p / ngc;
+        const int j = s_gtlist[p - d * ngc];
+        const float *__restrict__ pb = bboxes + ((size_t)scene * n + s_box[d]) * 24;
+        const float *__restrict__ pg = gt_boxes + ((size_t)scene * g + j) * 24;
+        float bi[24], bj[24];
+#pragma unroll
+        for (int t = 0; t < 24; t++) {
+            bi[t] = pb[t];
+            bj[t] = pg[t];
+        }
+        const float ov = iou3d_pair(bi, bj); // detection first, as votenet_iou3d_cross
+        if (ov != ov)
+            atomicOr(&s_nan[d], 1);
+        else
+            atomicMax(&s_key[d], ((unsigned long long)ordered_bits(ov + 0.0f) << 32) | (unsigned)(~j)); // -0 == +0 in a '>' scan
+    }
+    __syncthreads();
+    // (e) ovmax, jmax and the thresholds they pass
+    for (int d = tid; d < L; d += 256) {
+        const unsigned long long k = s_key[d];
+        int q = 0, jm = -1;
+        if (k != 0ull && !s_nan[d]) {
+            const float ovmax = from_ordered_bits((unsigned)(k >> 32));
+            jm = (int)~(unsigned)k;
+            for (int t = 0; t < nthr; t++)
+                if (ovmax > thr.t[t]) q |= 1 << t;
+        }
+        s_jmax[d] = jm;
+        s_qmask[d] = q;
+    }
+    __syncthreads();
+    // (f) the box is taken at threshold t iff an earlier detection with the same jmax passes t
+    const int base = s_base;
+    for (int d = tid; d < L; d += 256) {
+        const int jm = s_jmax[d];
+        const float sd = s_score[d];
+        int taken = 0;
+        if (s_qmask[d])
+            for (int e = 0; e < L; e++) {
+                const float se = s_score[e];
+                if (s_jmax[e] == jm && (se > sd || (se == sd && e < d))) taken |= s_qmask[e];
+            }
+        const int tp = s_qmask[d] & ~taken;
+        const long pos = (long)base + d;
+        if (pos < (long)capacity)
+            records[pos] = make_uint4(__float_as_uint(sd), (unsigned)cls | ((unsigned)tp << 8), (unsigned)(scene0 + scene),
+                                      arrival0 + s_row[d]);
+        else
+            atomicOr(flags, EVAL_F_OVERFLOW);
+    }
+}
+
+} // namespace votenet
+
+using namespace votenet;
+
+extern "C" const char *votenet_detections_last_error(void) { return g_det_err; }
+
+extern "C" size_t votenet_class_nms3d_workspace_bytes(int b, int n, int nc)
+{
+    (void)nc;
+    if (b <= 0 || n <= 0) return 256;
+    return align256((size_t)b * n * sizeof(int)) + align256((size_t)b * sizeof(int)); // kept boxes per scene, their counts
+}
+
+extern "C" int votenet_class_nms3d(int b, int n, int nc, const float *bboxes, const float *objectness, const float *class_scores,
+                                   float iou_threshold, float conf_logit, int class_nms, int per_class, void *det_rows,
+                                   long det_capacity, int *det_offset, void *workspace, size_t workspace_bytes, void *stream)
+{
+    DET_REQUIRE(b >= 0 && b <= 65535, "class_nms3d: batch must be in [0, 65535], got %d", b);
+    DET_REQUIRE(n >= 0 && n <= DET_MAX_N, "class_nms3d: at most %d boxes per scene, got n = %d", DET_MAX_N, n);
+    DET_REQUIRE(nc >= 1 && nc <= DET_MAX_NC, "class_nms3d: the number of classes must be in [1, %d], got %d", DET_MAX_NC, nc);
+    DET_REQUIRE(iou_threshold >= 0 && iou_threshold <= 1, "class_nms3d: iou_threshold must be in [0, 1], got %g", (double)iou_threshold);
+    DET_REQUIRE(conf_logit == conf_logit && conf_logit < __builtin_inff(),
+                "class_nms3d: conf_logit must be the logit of a confidence threshold in [0, 1): -inf <= T < +inf, got %g", (double)conf_logit);
+    DET_REQUIRE((class_nms == 0 || class_nms == 1) && (per_class == 0 || per_class == 1), "class_nms3d: class_nms and per_class are 0 or 1");
+    DET_REQUIRE(det_offset != nullptr, "class_nms3d: det_offset is required");
+    const long need = (long)b * n * (per_class ? nc : 1);
+    DET_REQUIRE((long)b * n * nc <= (long)INT_MAX, "class_nms3d: b * n * nc must fit 31 bits");
+    DET_REQUIRE(det_capacity >= need, "class_nms3d: det_rows must hold b * n * %d = %ld rows, got %ld", per_class ? nc : 1, need, det_capacity);
+    hipStream_t st = as_stream(stream);
+    if (b == 0 || n == 0) {
+        (void)hipMemsetAsync(det_offset, 0, ((size_t)b + 1) * sizeof(int), st);
+        return det_check_launch("class_nms3d");
+    }
+    DET_REQUIRE(bboxes && objectness && class_scores && det_rows, "class_nms3d: null buffer");
+    DET_REQUIRE(((uintptr_t)det_rows & 15) == 0, "class_nms3d: det_rows must be 16-byte aligned");
+    const size_t wbytes = votenet_class_nms3d_workspace_bytes(b, n, nc);
+    if (workspace == nullptr || workspace_bytes < wbytes)
+        return det_set_error(VOTENET_E_WORKSPACE, "class_nms3d: workspace of %zu bytes required, got %zu", wbytes, workspace ? workspace_bytes : (size_t)0);
+    int *kept = (int *)workspace;
+    int *count = (int *)((char *)workspace + align256((size_t)b * n * sizeof(int)));
+    hipLaunchKernelGGL(class_nms_kernel, dim3(b), dim3(DET_NMS_THREADS), 0, st, n, nc, bboxes, objectness, class_scores, iou_threshold,
+                       conf_logit, class_nms, kept, count);
+    hipLaunchKernelGGL(det_emit_kernel, dim3(b), dim3(256), 0, st, b, n, nc, objectness, class_scores, per_class, kept, count,
+                       (uint4 *)det_rows, det_offset);
+    return det_check_launch("class_nms3d");
+}
+
+extern "C" int votenet_eval_match_rows(int b, int n, int g, int nc, const float *bboxes, const void *det_rows, long nrows,
+                                       const int *det_offset, const float *gt_boxes, const int *gt_labels, const int *gt_count,
+                                       int nthr, const float *thresholds, long scene0, unsigned arrival0, void *records,
+                                       int capacity, int *rec_count, int *npos, int *flags, void *stream)
+{
+    DET_REQUIRE(b >= 0 && b <= 65535, "eval_match_rows: batch must be in [0, 65535], got %d", b);
+    DET_REQUIRE(n >= 1 && n <= EVAL_MAX_DET, "eval_match_rows: 1 to %d boxes per scene, got n = %d", EVAL_MAX_DET, n);
+    DET_REQUIRE(g >= 0 && g <= EVAL_MAX_GT, "eval_match_rows: at most %d ground-truth rows per scene, got %d", EVAL_MAX_GT, g);
+    DET_REQUIRE(nc >= 1 && nc <= EVAL_MAX_NC, "eval_match_rows: the number of classes must be in [1, %d], got %d", EVAL_MAX_NC, nc);
+    DET_REQUIRE(nthr >= 1 && nthr <= EVAL_MAX_THR, "eval_match_rows: 1 to %d IoU thresholds, got %d", EVAL_MAX_THR, nthr);
+    DET_REQUIRE(thresholds != nullptr, "eval_match_rows: null thresholds");
+    DET_REQUIRE(nrows >= 0 && capacity >= 0, "eval_match_rows: negative row count or capacity");
+    DET_REQUIRE(scene0 >= 0 && scene0 + b <= (long)INT_MAX, "eval_match_rows: scene numbers must fit 31 bits, got %ld + %d", scene0, b);
+    DET_REQUIRE((unsigned long long)arrival0 + (unsigned long long)nrows <= 0xffffffffull, "eval_match_rows: arrival numbers must fit 32 bits");
+    DET_REQUIRE(records && rec_count && npos && flags, "eval_match_rows: null accumulator buffer");
+    if (b == 0) return VOTENET_OK;
+    DET_REQUIRE(bboxes && det_offset, "eval_match_rows: null prediction buffer");
+    DET_REQUIRE(nrows == 0 || det_rows, "eval_match_rows: null detection rows");
+    DET_REQUIRE(((uintptr_t)det_rows & 15) == 0 && ((uintptr_t)records & 15) == 0, "eval_match_rows: det_rows and records must be 16-byte aligned");
+    DET_REQUIRE(g == 0 || (gt_boxes && gt_labels && gt_count), "eval_match_rows: null ground-truth buffer");
+    EvalThr thr = {};
+    for (int t = 0; t < nthr; t++) thr.t[t] = thresholds[t];
+    hipLaunchKernelGGL(eval_match_rows_kernel, dim3(nc, b), dim3(256), 0, as_stream(stream), n, g, nc, bboxes, (const int4 *)det_rows,
+                       nrows, det_offset, gt_boxes, gt_labels, gt_count, thr, nthr, (int)scene0, arrival0, (uint4 *)records, capacity,
+                       rec_count, npos, flags);
+    return det_check_launch("eval_match_rows");
+}

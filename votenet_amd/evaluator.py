@@ -190,11 +190,15 @@ class DetectionAccumulator:
 
     def add(self, pred, gt):
         """pred: what VoteNetHotPath.predict returns (sync=True: nms_idx (K,2); sync=False: padded nms_idx + nms_count on the
-        device).  gt: gt_for_eval's dict, numpy (uploaded here) or device tensors (gt_to_device: used in place)."""
+        device; protocol="per_class": det_rows (R,4) + det_offset (B+1,), matched row by row through votenet_eval_match_rows -- the
+        arrival number then advances by R, the rows offered room for).  gt: gt_for_eval's dict, numpy (uploaded here) or device
+        tensors (gt_to_device: used in place)."""
         boxes = L.dev_f32(pred["bboxes"].detach(), "DetectionAccumulator.add: bboxes (B,N,8,3)", 4, 3)
         b, n = boxes.shape[:2]
         if boxes.shape[2] != 8:
             raise L.InvalidArgumentError("DetectionAccumulator.add expects (B, N, 8, 3) boxes")
+        if "det_rows" in pred:
+            return self._add_rows(boxes, pred, gt)
         cls = L.dev_f32(pred["class_scores"].detach(), "DetectionAccumulator.add: class_scores (B,N,NC)", 3, NC)
         if tuple(cls.shape[:2]) != (b, n):
             raise L.InvalidArgumentError("DetectionAccumulator.add: class_scores %s do not match boxes %s" % (tuple(cls.shape), tuple(boxes.shape)))
@@ -204,12 +208,7 @@ class DetectionAccumulator:
         count = pred.get("nms_count")
         if count is not None:
             count = L.dev_i32(count, "DetectionAccumulator.add: nms_count")
-        g = gt_to_device(gt, self.device)
-        if g["boxes"].dim() != 4 or tuple(g["boxes"].shape[2:]) != (8, 3) or g["boxes"].shape[0] != b:
-            raise L.InvalidArgumentError("DetectionAccumulator.add expects (B, G, 8, 3) ground-truth boxes, got %s" % (tuple(g["boxes"].shape),))
-        ng = g["boxes"].shape[1]
-        if tuple(g["labels"].shape) != (b, ng) or tuple(g["count"].shape) != (b,):
-            raise L.InvalidArgumentError("DetectionAccumulator.add: labels must be (B, G) and count (B,)")
+        g, ng = self._gt(gt, b)
         k = rows.shape[0]
         if self._arrival + k > 0xffffffff:
             raise L.VotenetError("DetectionAccumulator: more than 2^32 kept rows offered")
@@ -219,6 +218,37 @@ class DetectionAccumulator:
                                                L.ptr(g["boxes"]), L.ptr(g["labels"]), L.ptr(g["count"]), len(self.thresholds), self._thr,
                                                self._scene, self._arrival, L.ptr(self._records), self.capacity, st.data_ptr(),
                                                st.data_ptr() + 8, st.data_ptr() + 4, L.stream_ptr()))
+        self._scene += b
+        self._arrival += k
+
+    def _gt(self, gt, b):
+        g = gt_to_device(gt, self.device)
+        if g["boxes"].dim() != 4 or tuple(g["boxes"].shape[2:]) != (8, 3) or g["boxes"].shape[0] != b:
+            raise L.InvalidArgumentError("DetectionAccumulator.add expects (B, G, 8, 3) ground-truth boxes, got %s" % (tuple(g["boxes"].shape),))
+        ng = g["boxes"].shape[1]
+        if tuple(g["labels"].shape) != (b, ng) or tuple(g["count"].shape) != (b,):
+            raise L.InvalidArgumentError("DetectionAccumulator.add: labels must be (B, G) and count (B,)")
+        return g, ng
+
+    def _add_rows(self, boxes, pred, gt):
+        """add() for explicit detection rows (detections.class_nms3d): the same records, flags and capacity rule."""
+        b, n = boxes.shape[:2]
+        rows = L.dev_i32(pred["det_rows"], "DetectionAccumulator.add: det_rows (R,4)", 2)
+        if rows.shape[1] != 4:
+            raise L.InvalidArgumentError("DetectionAccumulator.add: det_rows must be (R, 4)")
+        offset = L.dev_i32(pred["det_offset"], "DetectionAccumulator.add: det_offset (B+1,)", 1)
+        if offset.shape[0] != b + 1:
+            raise L.InvalidArgumentError("DetectionAccumulator.add: det_offset must be (B + 1,), got %s" % (tuple(offset.shape),))
+        g, ng = self._gt(gt, b)
+        k = rows.shape[0]
+        if self._arrival + k > 0xffffffff:
+            raise L.VotenetError("DetectionAccumulator: more than 2^32 detection rows offered")
+        st = self._state
+        with L.device_guard(self.device):
+            L.check_detect(L.detect_lib().votenet_eval_match_rows(
+                b, n, ng, NC, L.ptr(boxes), L.ptr(rows) if k else None, k, L.ptr(offset), L.ptr(g["boxes"]), L.ptr(g["labels"]),
+                L.ptr(g["count"]), len(self.thresholds), self._thr, self._scene, self._arrival, L.ptr(self._records), self.capacity,
+                st.data_ptr(), st.data_ptr() + 8, st.data_ptr() + 4, L.stream_ptr()))
         self._scene += b
         self._arrival += k
 
@@ -234,21 +264,24 @@ class DetectionAccumulator:
         return finalize_records(self._records[:offered].cpu().numpy(), npos, self.thresholds, use_07_metric)
 
 
-def evaluate(net, batches, gts, thresholds=(0.25, 0.5), iou_threshold=0.25):
+def evaluate(net, batches, gts, thresholds=(0.25, 0.5), iou_threshold=0.25, protocol="reference"):
     """mAP of `net` over a validation set: batches[i] (B,n,3) device clouds -- or (cloud, feats (B,n,c)) pairs for a network built with
     point features --, gts[i] gt_for_eval's dict (numpy or device).  Every predict call is asynchronous with the next batch's
-    geometry underneath it; one synchronisation at the end.
+    geometry underneath it; one synchronisation at the end.  protocol: predict's ("reference", "per_class" or a dict of
+    detections.class_nms3d's parameters); per class, every box offers a detection of every class.
     -> {threshold: dict(ap, mAP, rec, prec, npos)}."""
     acc = None
+    kw = {} if protocol == "reference" else dict(protocol=protocol)  # (the call of the reference's protocol, as it was)
     pairs = [tuple(v) if isinstance(v, (tuple, list)) else (v, None) for v in batches]
     for i, ((x, f), g) in enumerate(zip(pairs, gts)):
         nx, nf = pairs[i + 1] if i + 1 < len(pairs) else (None, None)
         if f is None:  # (the call of every network without point features, as it was)
-            pred = net.predict(x, iou_threshold, next_x=nx, sync=False)
+            pred = net.predict(x, iou_threshold, next_x=nx, sync=False, **kw)
         else:
-            pred = net.predict(x, iou_threshold, next_x=nx, sync=False, feats=f, next_feats=nf)
-        if acc is None:  # every proposal of every scene kept: the most the set can offer
-            acc = DetectionAccumulator(x.device, thresholds, capacity=sum(int(v.shape[0]) for v, _ in pairs) * int(pred["bboxes"].shape[1]))
+            pred = net.predict(x, iou_threshold, next_x=nx, sync=False, feats=f, next_feats=nf, **kw)
+        if acc is None:  # every proposal of every scene kept (per class: offering every class): the most the set can offer
+            per_box = NC if "det_rows" in pred else 1
+            acc = DetectionAccumulator(x.device, thresholds, capacity=sum(int(v.shape[0]) for v, _ in pairs) * int(pred["bboxes"].shape[1]) * per_box)
         acc.add(pred, g)
     if acc is None:
         raise L.InvalidArgumentError("evaluate: no batches")

@@ -687,14 +687,19 @@ class VoteNetHotPath:
             self._frozen_key = key
         return self._frozen
 
-    def predict(self, x, iou_threshold=0.25, next_x=None, sync=True, batch_statistics=False, feats=None, next_feats=None):
+    def predict(self, x, iou_threshold=0.25, next_x=None, sync=True, batch_statistics=False, feats=None, next_feats=None,
+                protocol="reference"):
         """Predict tower of model.py:98-139: forward -> decode -> NMS3D(bboxes, max class logit, objectness, 0.25), every
         BatchNorm in inference mode (moving averages, as the reference's BNReLU under `not is_training`): a scene's
         detections do not depend on its batch-mates.  batch_statistics=True normalises with the current batch instead
         (what a model without trained moving averages needs, e.g. random-init benchmarks).
         next_x: the batch(es) of the next call(s), as in forward().  sync=False: nms_idx stays padded on the device with its
-        length in nms_count (no host synchronisation: calls pipeline).  feats / next_feats: as in forward()."""
-        from . import tf_nms3d
+        length in nms_count (no host synchronisation: calls pipeline).  feats / next_feats: as in forward().
+        protocol: "reference" is the above.  "per_class" (the VoteNet paper's protocol: detections.PAPER with this call's
+        iou_threshold) or a dict of any of iou_threshold / conf_thresh / class_nms / per_class runs detections.class_nms3d in NMS3D's
+        place: det_rows / det_offset instead of nms_idx, on the device; that mode never synchronises, whatever `sync` says."""
+        from . import detections, tf_nms3d
+        params = detections.protocol_params(protocol, iou_threshold)
         self._sa1_points(x, feats, "predict")
         if not batch_statistics and self._ema_state() is not None and self._ema_version == 0 and not getattr(self, "_warned_ema", False):
             import warnings
@@ -704,6 +709,10 @@ class VoteNetHotPath:
         with P.frozen_bn(None if batch_statistics else self.inference_bn()):
             out = self.forward(x, next_x=next_x, **self._feats_kw(feats, next_feats))
         boxes, score = self.decode_boxes(out["proposals_xyz"], out["proposals_output"])
+        if params is not None:
+            cls = out["proposals_output"][..., -NC:].contiguous()
+            det = detections.class_nms3d(boxes, out["proposals_output"][..., :2].contiguous(), cls, **params)
+            return dict(bboxes=boxes, scores=score, class_scores=cls, **det, **out)
         keep = tf_nms3d.NMS3D(boxes, score, out["proposals_output"][..., :2].contiguous(), iou_threshold, padded=not sync)
         extra = {} if sync else dict(nms_count=keep[1])
         return dict(bboxes=boxes, scores=score, nms_idx=keep if sync else keep[0], class_scores=out["proposals_output"][..., -NC:].contiguous(),
