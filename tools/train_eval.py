@@ -2,7 +2,7 @@
 tower (decode -> 3D NMS) on held-out scenes and report mAP@0.25 / @0.5 with the reference's evaluator logic: "mAP" is the mean
 of the per-batch mAPs (the figure of every earlier log), "set mAP" the reference's own metric, detections ranked over the whole
 validation set (evaluator.evaluate).
-    python tools/train_eval.py [steps] [train_batches] [--save PATH] [--resume PATH] [--monitor K] [--guard] [--height] [--per-class]
+    python tools/train_eval.py [steps] [train_batches] [--save PATH] [--resume PATH] [--monitor K] [--guard] [--height] [--per-class] [--min-points K]
 --save PATH: a checkpoint (VoteNetHotPath.save) at every evaluation and at the end.  --resume PATH: continue the run a checkpoint
 holds -- parameters, moving averages, Adam state and step count -- up to `steps` steps in all, on the batches it would have seen.  --monitor K: the reference's training summaries from the device
 (VoteNetHotPath.enable_monitors): every K steps the moving averages of obj_accuracy / sem_accuracy / total_cost over the last 100 steps
@@ -13,7 +13,9 @@ and the restores of the moving averages are printed at the end (with --monitor K
 the device by input_pipeline.subsample_augment_features from the same clouds (already in the camera frame; the rooms have no colour).
 --per-class: at the end, the set-level mAP under both protocols: the reference's (class-agnostic NMS by the largest class logit, one
 detection per kept box) and the VoteNet paper's (detections.class_nms3d: class-wise NMS by objectness, confidence threshold 0.05, one
-detection per class and kept box scored P(object) P(class))."""
+detection per class and kept box scored P(object) P(class)).
+--min-points K: a predicted box that holds fewer than K points of its scene's cloud is dropped before the NMS (box_points; the count runs on
+the device) in the set-level evaluations.  With --per-class, K = 5 is the paper's protocol apart from its axis-aligned NMS overlap."""
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import importlib.util
@@ -33,6 +35,7 @@ ap.add_argument("--monitor", metavar="K", type=int, default=0, help="print the m
 ap.add_argument("--guard", action="store_true", help="skip steps whose gradient is not finite (on the device); print how many were")
 ap.add_argument("--height", action="store_true", help="feed the height above the floor as a point feature (point_features=1)")
 ap.add_argument("--per-class", action="store_true", help="print the set-level mAP under the reference's and the paper's protocol at the end")
+ap.add_argument("--min-points", metavar="K", type=int, default=0, help="drop predicted boxes that hold fewer than K points of the cloud (the paper: 5)")
 args = ap.parse_args()
 steps, nb = args.steps, args.train_batches
 dev = torch.device("cuda:0")
@@ -84,7 +87,7 @@ def save():
 
 def report(step):
     """The line of every earlier log (mean of the per-batch mAPs), and beside it the reference's metric: mAP over the whole set."""
-    res = E.evaluate(net, list(zip(val_x, val_f)) if args.height else val_x, val_gt, (0.25, 0.5))
+    res = E.evaluate(net, list(zip(val_x, val_f)) if args.height else val_x, val_gt, (0.25, 0.5), min_points=args.min_points)
     print("step %d: mAP" % step, evaluate(), " set mAP", {thr: res[thr]["mAP"] for thr in (0.25, 0.5)})
 
 
@@ -126,5 +129,5 @@ if args.guard:
 if args.per_class:
     val = list(zip(val_x, val_f)) if args.height else val_x
     for name, proto in (("reference protocol", "reference"), ("per-class protocol", "per_class")):
-        res = E.evaluate(net, val, val_gt, (0.25, 0.5), protocol=proto)
+        res = E.evaluate(net, val, val_gt, (0.25, 0.5), protocol=proto, min_points=args.min_points)
         print("step %d: set mAP, %s" % (net._step, name), {thr: res[thr]["mAP"] for thr in (0.25, 0.5)})

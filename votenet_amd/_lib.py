@@ -22,6 +22,8 @@ _guard = None
 _feat = None
 _DETECT_PATH = os.path.join(_HERE, "lib", "libvotenet_detect.so")  # per-class detections (include/votenet_detections.h): likewise
 _detect = None
+_BOXPTS_PATH = os.path.join(_HERE, "lib", "libvotenet_boxpts.so")  # points inside predicted boxes (include/votenet_box_points.h): likewise
+_boxpts = None
 
 
 class VotenetError(RuntimeError):
@@ -44,8 +46,9 @@ def build(force=False):
         guard = os.path.join(os.path.dirname(_LIB_PATH), os.path.basename(_GUARD_PATH))
         feat = os.path.join(os.path.dirname(_LIB_PATH), os.path.basename(_FEAT_PATH))
         detect = os.path.join(os.path.dirname(_LIB_PATH), os.path.basename(_DETECT_PATH))
-        for f in [_LIB_PATH, mon, guard, feat, detect] + [o for d in ("obj", os.path.join("monitors", "obj"), os.path.join("guard", "obj"), os.path.join("features", "obj"),
-                                                                 os.path.join("detect", "obj"))
+        boxpts = os.path.join(os.path.dirname(_LIB_PATH), os.path.basename(_BOXPTS_PATH))
+        for f in [_LIB_PATH, mon, guard, feat, detect, boxpts] + [o for d in ("obj", os.path.join("monitors", "obj"), os.path.join("guard", "obj"), os.path.join("features", "obj"),
+                                                                         os.path.join("detect", "obj"), os.path.join("boxpts", "obj"))
                                             for o in glob.glob(os.path.join(_HERE, "csrc", d, "*.o"))]:
             if os.path.exists(f):
                 os.remove(f)
@@ -239,6 +242,35 @@ def detect_lib():
             fn.restype, fn.argtypes = restype, argtypes
         _detect = D
     return _detect
+
+
+def boxpts_lib():
+    """libvotenet_boxpts.so, loaded when the points inside predicted boxes are first asked for; every function of
+    include/votenet_box_points.h gets its header's prototype (parse_header, as for the main library).  No fallback: a missing library
+    is an error."""
+    global _boxpts
+    if _boxpts is None:
+        if not os.path.exists(_BOXPTS_PATH):
+            raise VotenetError("libvotenet_boxpts.so not found at %s -- run `python -c 'import __graft_entry__ as g; g.build()'` "
+                               "(there is no CPU fallback)" % _BOXPTS_PATH)
+        with open(os.path.join(_HERE, os.pardir, "include", "votenet_box_points.h")) as f:
+            protos = parse_header(f.read(), {})
+        B = ctypes.CDLL(_BOXPTS_PATH)
+        for name, (restype, argtypes) in protos.items():
+            fn = getattr(B, name)
+            fn.restype, fn.argtypes = restype, argtypes
+        _boxpts = B
+    return _boxpts
+
+
+def check_boxpts(rc):
+    """check() for a status libvotenet_boxpts.so returned (it keeps its own error text)."""
+    if rc == 0:
+        return
+    msg = boxpts_lib().votenet_box_points_last_error().decode()
+    if rc == 1:
+        raise InvalidArgumentError(msg)
+    raise VotenetError("libvotenet_boxpts error %d: %s" % (rc, msg))
 
 
 def check_detect(rc):

@@ -100,3 +100,20 @@ $HIPCC --offload-arch=gfx950 -shared -fPIC -Wl,--version-script="$HERE/detect/ex
 python3 "$HERE/../../tools/check_isa_hazards.py" "$DTMP"
 mv -f "$DTMP" "$OUT/libvotenet_detect.so"
 echo "built $OUT/libvotenet_detect.so"
+# libvotenet_boxpts.so (include/votenet_box_points.h): the points inside each predicted box and the gate that keeps empty boxes out of
+# the NMS, a library of its own for the same reason.  Same flags (no floating-point contraction: tests/box_points_ref.py restates the
+# rule operation for operation), same gate; -fno-slp-vectorize as loss.hip: the point slots' dot products pack into the v_pk_*_f32 forms
+# the gate refuses.
+BOBJ="$HERE/boxpts/obj/box_points.o"
+mkdir -p "$HERE/boxpts/obj"
+if [ ! -f "$BOBJ" ] || [ "$HERE/boxpts/box_points.hip" -nt "$BOBJ" ] || [ "$HERE/common.h" -nt "$BOBJ" ] \
+   || [ "$HERE/../../include/votenet_box_points.h" -nt "$BOBJ" ] || [ "$HERE/../../include/votenet_hip.h" -nt "$BOBJ" ] \
+   || [ "$HERE/../../include/votenet_hip_debug.h" -nt "$BOBJ" ] || [ "${BASH_SOURCE[0]}" -nt "$BOBJ" ]; then
+  $HIPCC $FLAGS -fno-slp-vectorize -c "$HERE/boxpts/box_points.hip" -o "$BOBJ"
+fi
+BTMP="$OUT/.libvotenet_boxpts.so.tmp.$$"
+trap 'rm -f "$TMP" "$MTMP" "$GTMP" "$FTMP" "$DTMP" "$BTMP"' EXIT
+$HIPCC --offload-arch=gfx950 -shared -fPIC -Wl,--version-script="$HERE/boxpts/exports.map" "$BOBJ" -o "$BTMP"
+python3 "$HERE/../../tools/check_isa_hazards.py" "$BTMP"
+mv -f "$BTMP" "$OUT/libvotenet_boxpts.so"
+echo "built $OUT/libvotenet_boxpts.so"

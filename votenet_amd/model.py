@@ -688,7 +688,7 @@ class VoteNetHotPath:
         return self._frozen
 
     def predict(self, x, iou_threshold=0.25, next_x=None, sync=True, batch_statistics=False, feats=None, next_feats=None,
-                protocol="reference"):
+                protocol="reference", min_points=0):
         """Predict tower of model.py:98-139: forward -> decode -> NMS3D(bboxes, max class logit, objectness, 0.25), every
         BatchNorm in inference mode (moving averages, as the reference's BNReLU under `not is_training`): a scene's
         detections do not depend on its batch-mates.  batch_statistics=True normalises with the current batch instead
@@ -697,9 +697,15 @@ class VoteNetHotPath:
         length in nms_count (no host synchronisation: calls pipeline).  feats / next_feats: as in forward().
         protocol: "reference" is the above.  "per_class" (the VoteNet paper's protocol: detections.PAPER with this call's
         iou_threshold) or a dict of any of iou_threshold / conf_thresh / class_nms / per_class runs detections.class_nms3d in NMS3D's
-        place: det_rows / det_offset instead of nms_idx, on the device; that mode never synchronises, whatever `sync` says."""
+        place: det_rows / det_offset instead of nms_idx, on the device; that mode never synchronises, whatever `sync` says.
+        min_points > 0 (box_points.PAPER_MIN_POINTS = 5 is the paper's remove_empty_box): the points of x inside every decoded box are
+        counted on the device (point_counts (B,N) int32 in the result) and a box with fewer is no candidate of the NMS of either
+        protocol, which sees a gated copy of the objectness logits; proposals_output stays the network's own.  0: the launches and the
+        keys of a call without it."""
         from . import detections, tf_nms3d
         params = detections.protocol_params(protocol, iou_threshold)
+        if isinstance(min_points, bool) or not isinstance(min_points, int) or min_points < 0:
+            raise M.L.InvalidArgumentError("predict: min_points must be an int >= 0, got %r" % (min_points,))
         self._sa1_points(x, feats, "predict")
         if not batch_statistics and self._ema_state() is not None and self._ema_version == 0 and not getattr(self, "_warned_ema", False):
             import warnings
@@ -709,12 +715,19 @@ class VoteNetHotPath:
         with P.frozen_bn(None if batch_statistics else self.inference_bn()):
             out = self.forward(x, next_x=next_x, **self._feats_kw(feats, next_feats))
         boxes, score = self.decode_boxes(out["proposals_xyz"], out["proposals_output"])
+        objectness = lambda: out["proposals_output"][..., :2].contiguous()
+        gate = {}
+        if min_points > 0:  # (the only place that loads libvotenet_boxpts.so)
+            from . import box_points
+            gate = dict(point_counts=box_points.box_point_counts(boxes, x))
+            gated = box_points.gate_objectness(objectness(), gate["point_counts"], min_points)
+            objectness = lambda: gated
         if params is not None:
             cls = out["proposals_output"][..., -NC:].contiguous()
-            det = detections.class_nms3d(boxes, out["proposals_output"][..., :2].contiguous(), cls, **params)
-            return dict(bboxes=boxes, scores=score, class_scores=cls, **det, **out)
-        keep = tf_nms3d.NMS3D(boxes, score, out["proposals_output"][..., :2].contiguous(), iou_threshold, padded=not sync)
-        extra = {} if sync else dict(nms_count=keep[1])
+            det = detections.class_nms3d(boxes, objectness(), cls, **params)
+            return dict(bboxes=boxes, scores=score, class_scores=cls, **gate, **det, **out)
+        keep = tf_nms3d.NMS3D(boxes, score, objectness(), iou_threshold, padded=not sync)
+        extra = dict(gate) if sync else dict(nms_count=keep[1], **gate)
         return dict(bboxes=boxes, scores=score, nms_idx=keep if sync else keep[0], class_scores=out["proposals_output"][..., -NC:].contiguous(),
                     **extra, **out)
 
