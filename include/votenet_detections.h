@@ -42,7 +42,8 @@ const char *votenet_detections_last_error(void);
  * det_rows: 16-byte aligned, det_capacity >= b * n * (per_class ? nc : 1) rows.
  * Filtering by the confidence threshold BEFORE the NMS keeps the same boxes as the paper's filter after it: a box below the threshold
  * comes later in the visit order than every box above it, so it can only suppress boxes that the filter drops anyway.
- * The paper's NMS uses axis-aligned overlaps; this one uses the rotated-box IoU of the rest of the project.
+ * This entry suppresses by the rotated-box IoU of the rest of the project; the paper's NMS uses the overlap of the boxes' axis-aligned
+ * hulls, which is votenet_class_nms_aabb (votenet_aabb_nms.h, libvotenet_aabb.so): this entry rule for rule, that overlap in iou3d's place.
  * Launches on `stream`: one workgroup per scene (order, suppression masks by ballots, one wave's pass over them), then one
  * workgroup per scene for the offsets, scores and rows.  workspace: votenet_class_nms3d_workspace_bytes(b, n, nc) bytes. */
 size_t votenet_class_nms3d_workspace_bytes(int b, int n, int nc);

@@ -3,6 +3,7 @@ tower (decode -> 3D NMS) on held-out scenes and report mAP@0.25 / @0.5 with the 
 of the per-batch mAPs (the figure of every earlier log), "set mAP" the reference's own metric, detections ranked over the whole
 validation set (evaluator.evaluate).
     python tools/train_eval.py [steps] [train_batches] [--save PATH] [--resume PATH] [--monitor K] [--guard] [--height] [--per-class] [--min-points K]
+                                                      [--nms-overlap {rotated,aabb3d,bev}] [--nms-old-type]
 --save PATH: a checkpoint (VoteNetHotPath.save) at every evaluation and at the end.  --resume PATH: continue the run a checkpoint
 holds -- parameters, moving averages, Adam state and step count -- up to `steps` steps in all, on the batches it would have seen.  --monitor K: the reference's training summaries from the device
 (VoteNetHotPath.enable_monitors): every K steps the moving averages of obj_accuracy / sem_accuracy / total_cost over the last 100 steps
@@ -15,7 +16,11 @@ the device by input_pipeline.subsample_augment_features from the same clouds (al
 detection per kept box) and the VoteNet paper's (detections.class_nms3d: class-wise NMS by objectness, confidence threshold 0.05, one
 detection per class and kept box scored P(object) P(class)).
 --min-points K: a predicted box that holds fewer than K points of its scene's cloud is dropped before the NMS (box_points; the count runs on
-the device) in the set-level evaluations.  With --per-class, K = 5 is the paper's protocol apart from its axis-aligned NMS overlap."""
+the device) in the set-level evaluations.
+--nms-overlap: the overlap the per-class protocol's NMS suppresses by (aabb_nms; --per-class only): rotated, the rotated-box IoU of the
+rest of the project (the default); aabb3d, the overlap of the boxes' axis-aligned hulls, the paper's; bev, the same on the ground plane.
+--nms-old-type: with aabb3d or bev, the paper's use_old_type_nms: intersection over the later box instead of IoU.
+--per-class --min-points 5 --nms-overlap aabb3d is the paper's protocol."""
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import importlib.util
@@ -36,7 +41,13 @@ ap.add_argument("--guard", action="store_true", help="skip steps whose gradient 
 ap.add_argument("--height", action="store_true", help="feed the height above the floor as a point feature (point_features=1)")
 ap.add_argument("--per-class", action="store_true", help="print the set-level mAP under the reference's and the paper's protocol at the end")
 ap.add_argument("--min-points", metavar="K", type=int, default=0, help="drop predicted boxes that hold fewer than K points of the cloud (the paper: 5)")
+ap.add_argument("--nms-overlap", choices=("rotated", "aabb3d", "bev"), default="rotated", help="the overlap of the per-class protocol's NMS (the paper: aabb3d)")
+ap.add_argument("--nms-old-type", action="store_true", help="with aabb3d / bev: intersection over the later box instead of IoU (the paper's use_old_type_nms)")
 args = ap.parse_args()
+if (args.nms_overlap != "rotated" or args.nms_old_type) and not args.per_class:
+    ap.error("--nms-overlap / --nms-old-type need --per-class: the reference's protocol suppresses by the rotated-box IoU")
+if args.nms_old_type and args.nms_overlap == "rotated":
+    ap.error("--nms-old-type needs --nms-overlap aabb3d or bev")
 steps, nb = args.steps, args.train_batches
 dev = torch.device("cuda:0")
 B, n = 8, 20480
@@ -129,5 +140,8 @@ if args.guard:
 if args.per_class:
     val = list(zip(val_x, val_f)) if args.height else val_x
     for name, proto in (("reference protocol", "reference"), ("per-class protocol", "per_class")):
-        res = E.evaluate(net, val, val_gt, (0.25, 0.5), protocol=proto, min_points=args.min_points)
+        kw = dict(nms_overlap=args.nms_overlap, nms_measure="over_later" if args.nms_old_type else "iou") if proto == "per_class" else {}
+        res = E.evaluate(net, val, val_gt, (0.25, 0.5), protocol=proto, min_points=args.min_points, **kw)
+        if kw and args.nms_overlap != "rotated":
+            name += ", NMS overlap %s / %s" % (kw["nms_overlap"], kw["nms_measure"])
         print("step %d: set mAP, %s" % (net._step, name), {thr: res[thr]["mAP"] for thr in (0.25, 0.5)})

@@ -24,6 +24,8 @@ _DETECT_PATH = os.path.join(_HERE, "lib", "libvotenet_detect.so")  # per-class d
 _detect = None
 _BOXPTS_PATH = os.path.join(_HERE, "lib", "libvotenet_boxpts.so")  # points inside predicted boxes (include/votenet_box_points.h): likewise
 _boxpts = None
+_AABB_PATH = os.path.join(_HERE, "lib", "libvotenet_aabb.so")  # axis-aligned NMS overlaps (include/votenet_aabb_nms.h): likewise
+_aabb = None
 
 
 class VotenetError(RuntimeError):
@@ -47,8 +49,9 @@ def build(force=False):
         feat = os.path.join(os.path.dirname(_LIB_PATH), os.path.basename(_FEAT_PATH))
         detect = os.path.join(os.path.dirname(_LIB_PATH), os.path.basename(_DETECT_PATH))
         boxpts = os.path.join(os.path.dirname(_LIB_PATH), os.path.basename(_BOXPTS_PATH))
-        for f in [_LIB_PATH, mon, guard, feat, detect, boxpts] + [o for d in ("obj", os.path.join("monitors", "obj"), os.path.join("guard", "obj"), os.path.join("features", "obj"),
-                                                                         os.path.join("detect", "obj"), os.path.join("boxpts", "obj"))
+        aabb = os.path.join(os.path.dirname(_LIB_PATH), os.path.basename(_AABB_PATH))
+        for f in [_LIB_PATH, mon, guard, feat, detect, boxpts, aabb] + [o for d in ("obj", os.path.join("monitors", "obj"), os.path.join("guard", "obj"), os.path.join("features", "obj"),
+                                                                               os.path.join("detect", "obj"), os.path.join("boxpts", "obj"), os.path.join("aabb", "obj"))
                                             for o in glob.glob(os.path.join(_HERE, "csrc", d, "*.o"))]:
             if os.path.exists(f):
                 os.remove(f)
@@ -261,6 +264,34 @@ def boxpts_lib():
             fn.restype, fn.argtypes = restype, argtypes
         _boxpts = B
     return _boxpts
+
+
+def aabb_lib():
+    """libvotenet_aabb.so, loaded when an axis-aligned NMS overlap is first asked for; every function of include/votenet_aabb_nms.h
+    gets its header's prototype (parse_header, as for the main library).  No fallback: a missing library is an error."""
+    global _aabb
+    if _aabb is None:
+        if not os.path.exists(_AABB_PATH):
+            raise VotenetError("libvotenet_aabb.so not found at %s -- run `python -c 'import __graft_entry__ as g; g.build()'` "
+                               "(there is no CPU fallback)" % _AABB_PATH)
+        with open(os.path.join(_HERE, os.pardir, "include", "votenet_aabb_nms.h")) as f:
+            protos = parse_header(f.read(), {})
+        A = ctypes.CDLL(_AABB_PATH)
+        for name, (restype, argtypes) in protos.items():
+            fn = getattr(A, name)
+            fn.restype, fn.argtypes = restype, argtypes
+        _aabb = A
+    return _aabb
+
+
+def check_aabb(rc):
+    """check() for a status libvotenet_aabb.so returned (it keeps its own error text)."""
+    if rc == 0:
+        return
+    msg = aabb_lib().votenet_aabb_last_error().decode()
+    if rc == 1:
+        raise InvalidArgumentError(msg)
+    raise VotenetError("libvotenet_aabb error %d: %s" % (rc, msg))
 
 
 def check_boxpts(rc):

@@ -89,6 +89,7 @@ echo "built $OUT/libvotenet_features.so"
 DOBJ="$HERE/detect/obj/detections.o"
 mkdir -p "$HERE/detect/obj"
 if [ ! -f "$DOBJ" ] || [ "$HERE/detect/detections.hip" -nt "$DOBJ" ] || [ "$HERE/iou3d.h" -nt "$DOBJ" ] \
+   || [ "$HERE/detect/det_emit.h" -nt "$DOBJ" ] \
    || [ "$HERE/common.h" -nt "$DOBJ" ] || [ "$HERE/../../include/votenet_detections.h" -nt "$DOBJ" ] \
    || [ "$HERE/../../include/votenet_hip.h" -nt "$DOBJ" ] || [ "$HERE/../../include/votenet_hip_debug.h" -nt "$DOBJ" ] \
    || [ "${BASH_SOURCE[0]}" -nt "$DOBJ" ]; then
@@ -117,3 +118,21 @@ $HIPCC --offload-arch=gfx950 -shared -fPIC -Wl,--version-script="$HERE/boxpts/ex
 python3 "$HERE/../../tools/check_isa_hazards.py" "$BTMP"
 mv -f "$BTMP" "$OUT/libvotenet_boxpts.so"
 echo "built $OUT/libvotenet_boxpts.so"
+# libvotenet_aabb.so (include/votenet_aabb_nms.h): the axis-aligned overlaps of the paper's NMS and the class-wise NMS that decides on
+# them, a library of its own for the same reason.  Same flags (no floating-point contraction: tests/aabb_nms_ref.py restates the rules
+# operation for operation), same gate; -fno-slp-vectorize as box_points.hip: the three axes' products would pack into the v_pk_*_f32
+# forms the gate refuses.  detect/det_emit.h is the text of votenet_class_nms3d's rows, so both libraries write the same bytes.
+AOBJ="$HERE/aabb/obj/aabb_nms.o"
+mkdir -p "$HERE/aabb/obj"
+if [ ! -f "$AOBJ" ] || [ "$HERE/aabb/aabb_nms.hip" -nt "$AOBJ" ] || [ "$HERE/detect/det_emit.h" -nt "$AOBJ" ] \
+   || [ "$HERE/common.h" -nt "$AOBJ" ] || [ "$HERE/../../include/votenet_aabb_nms.h" -nt "$AOBJ" ] \
+   || [ "$HERE/../../include/votenet_hip.h" -nt "$AOBJ" ] || [ "$HERE/../../include/votenet_hip_debug.h" -nt "$AOBJ" ] \
+   || [ "${BASH_SOURCE[0]}" -nt "$AOBJ" ]; then
+  $HIPCC $FLAGS -fno-slp-vectorize -c "$HERE/aabb/aabb_nms.hip" -o "$AOBJ"
+fi
+ATMP="$OUT/.libvotenet_aabb.so.tmp.$$"
+trap 'rm -f "$TMP" "$MTMP" "$GTMP" "$FTMP" "$DTMP" "$BTMP" "$ATMP"' EXIT
+$HIPCC --offload-arch=gfx950 -shared -fPIC -Wl,--version-script="$HERE/aabb/exports.map" "$AOBJ" -o "$ATMP"
+python3 "$HERE/../../tools/check_isa_hazards.py" "$ATMP"
+mv -f "$ATMP" "$OUT/libvotenet_aabb.so"
+echo "built $OUT/libvotenet_aabb.so"

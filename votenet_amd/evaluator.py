@@ -264,17 +264,24 @@ class DetectionAccumulator:
         return finalize_records(self._records[:offered].cpu().numpy(), npos, self.thresholds, use_07_metric)
 
 
-def evaluate(net, batches, gts, thresholds=(0.25, 0.5), iou_threshold=0.25, protocol="reference", min_points=0):
+def evaluate(net, batches, gts, thresholds=(0.25, 0.5), iou_threshold=0.25, protocol="reference", min_points=0, nms_overlap="rotated",
+             nms_measure="iou"):
     """mAP of `net` over a validation set: batches[i] (B,n,3) device clouds -- or (cloud, feats (B,n,c)) pairs for a network built with
     point features --, gts[i] gt_for_eval's dict (numpy or device).  Every predict call is asynchronous with the next batch's
     geometry underneath it; one synchronisation at the end.  protocol: predict's ("reference", "per_class" or a dict of
     detections.class_nms3d's parameters); per class, every box offers a detection of every class.  min_points: predict's (5,
-    box_points.PAPER_MIN_POINTS, with "per_class" is the paper's protocol: boxes that hold fewer points of the cloud are dropped).
+    box_points.PAPER_MIN_POINTS, with "per_class": boxes that hold fewer points of the cloud are dropped).  nms_overlap, nms_measure:
+    predict's ("aabb3d", aabb_nms.PAPER_OVERLAP, with "per_class" and min_points=5 is the paper's protocol: the NMS suppresses by the
+    overlap of the boxes' axis-aligned hulls; the matching below stays on the rotated-box IoU, as the paper's does).
     -> {threshold: dict(ap, mAP, rec, prec, npos)}."""
+    from . import aabb_nms
+    aabb_nms.check_overlap(protocol, nms_overlap, nms_measure, "evaluate")
     acc = None
     kw = {} if protocol == "reference" else dict(protocol=protocol)  # (the call of the reference's protocol, as it was)
     if min_points:
         kw["min_points"] = min_points
+    if nms_overlap != "rotated":  # (the rotated overlap: predict is called without the arguments, as it was)
+        kw.update(nms_overlap=nms_overlap, nms_measure=nms_measure)
     pairs = [tuple(v) if isinstance(v, (tuple, list)) else (v, None) for v in batches]
     for i, ((x, f), g) in enumerate(zip(pairs, gts)):
         nx, nf = pairs[i + 1] if i + 1 < len(pairs) else (None, None)

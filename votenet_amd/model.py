@@ -688,7 +688,7 @@ class VoteNetHotPath:
         return self._frozen
 
     def predict(self, x, iou_threshold=0.25, next_x=None, sync=True, batch_statistics=False, feats=None, next_feats=None,
-                protocol="reference", min_points=0):
+                protocol="reference", min_points=0, nms_overlap="rotated", nms_measure="iou"):
         """Predict tower of model.py:98-139: forward -> decode -> NMS3D(bboxes, max class logit, objectness, 0.25), every
         BatchNorm in inference mode (moving averages, as the reference's BNReLU under `not is_training`): a scene's
         detections do not depend on its batch-mates.  batch_statistics=True normalises with the current batch instead
@@ -701,9 +701,15 @@ class VoteNetHotPath:
         min_points > 0 (box_points.PAPER_MIN_POINTS = 5 is the paper's remove_empty_box): the points of x inside every decoded box are
         counted on the device (point_counts (B,N) int32 in the result) and a box with fewer is no candidate of the NMS of either
         protocol, which sees a gated copy of the objectness logits; proposals_output stays the network's own.  0: the launches and the
-        keys of a call without it."""
-        from . import detections, tf_nms3d
+        keys of a call without it.
+        nms_overlap: the overlap the per-class NMS suppresses by.  "rotated" is detections.class_nms3d, the rotated-box IoU.  "aabb3d"
+        (aabb_nms.PAPER_OVERLAP, the paper's) and "bev" run aabb_nms.class_nms_aabb in its place, on the same boxes and the same,
+        possibly gated, objectness: the overlap of the boxes' axis-aligned hulls, in 3D or on the ground plane; the same keys.
+        nms_measure: "iou", or "over_later" (the paper's use_old_type_nms: intersection over the later box) with those two.  The
+        reference's protocol has the rotated-box IoU only."""
+        from . import aabb_nms, detections, tf_nms3d
         params = detections.protocol_params(protocol, iou_threshold)
+        aabb_nms.check_overlap(protocol, nms_overlap, nms_measure, "predict")
         if isinstance(min_points, bool) or not isinstance(min_points, int) or min_points < 0:
             raise M.L.InvalidArgumentError("predict: min_points must be an int >= 0, got %r" % (min_points,))
         self._sa1_points(x, feats, "predict")
@@ -724,7 +730,10 @@ class VoteNetHotPath:
             objectness = lambda: gated
         if params is not None:
             cls = out["proposals_output"][..., -NC:].contiguous()
-            det = detections.class_nms3d(boxes, objectness(), cls, **params)
+            if nms_overlap == "rotated":
+                det = detections.class_nms3d(boxes, objectness(), cls, **params)
+            else:  # (the only place that loads libvotenet_aabb.so)
+                det = aabb_nms.class_nms_aabb(boxes, objectness(), cls, overlap=nms_overlap, measure=nms_measure, **params)
             return dict(bboxes=boxes, scores=score, class_scores=cls, **gate, **det, **out)
         keep = tf_nms3d.NMS3D(boxes, score, objectness(), iou_threshold, padded=not sync)
         extra = dict(gate) if sync else dict(nms_count=keep[1], **gate)
