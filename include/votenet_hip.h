@@ -624,7 +624,16 @@ int votenet_clip_adam(int ntensors, const long *seg, float *sumsq_scratch, float
  * losses (12 floats): total_cost, vote_reg_loss, obj_cls_loss, center_loss (incl. the dual term),
  * heading_cls_loss, heading_residual_loss, size_cls_loss, size_residual_loss, sem_cls_loss, box_loss,
  * #positive, #negative proposals.  No positive (or no negative) proposal: the affected means are NaN, as
- * tf.reduce_mean of an empty tensor. */
+ * tf.reduce_mean of an empty tensor.
+ * Labels outside their range (heading_labels outside [0, nh), size_labels outside [0, ns), semantic_labels outside [0, nc);
+ * they are device data, so no caller can screen them): nothing is clamped and no label becomes an address outside the class
+ * block it selects in.  For every positive proposal assigned to such a box, as TensorFlow documents the reference's ops on a GPU:
+ * the class term (tf.nn.sparse_softmax_cross_entropy_with_logits, model.py:187,198,213) is NaN, so that class loss, box_loss (heading,
+ * size) and total_cost are NaN, and the nh / ns / nc cotangents of that proposal's class block are NaN; the residual prediction is
+ * the sum over an all-zero tf.one_hot row (model.py:189-193, 200-205), i.e. 0: the residual loss takes Huber(0 - label residual)
+ * for that proposal -- not zero: the reference's own graph, where the one-hot row multiplies the prediction, not the error -- and
+ * the residual columns get no cotangent.  Every other proposal, scene, loss term and cotangent keeps the bits it has with a valid
+ * label on that box.  The guarded optimizer step (votenet_step_guard.h) sees the NaN gradient and skips the step. */
 int votenet_loss(int b, int n_seeds, int n_prop, int n_box, int nh, int ns, int nc, const float *seeds_xyz,
                  const float *votes_xyz, const float *proposals_xyz, const float *proposals_output,
                  const float *bboxes_xyz, const float *bboxes_lwh, const float *bboxes_roty,
@@ -697,11 +706,14 @@ int votenet_subsample_augment(int b, int n_out, const void *raw, int raw_f64, in
 /* Ground truth: scene s owns boxes [box_offset[s], box_offset[s+1]) of center (nbox,3), size (nbox,3; full l,w,h as
  * dataset.py:258), heading (nbox), cls (nbox), all device memory, doubles / ints.  Applies dataset.py:262-276 (flip_x:
  * x = -x, heading = pi - heading; flip_z: z = -z, heading = -heading; rotation of the centre, heading += angle[s]; centre
- * and size times scale[s]), size2class (dataset.py:80-84), angle2class (dataset.py:52-67, python float modulo), the
+ * and size times scale[s]), size2class (dataset.py:80-84), angle2class (dataset.py:52-67, python float modulo; one deviation: a
+ * heading within an ulp of a bin edge at 2 pi - pi/nh, where dataset.py's quotient rounds to class nh, is class 0 with the
+ * residual as computed, about -pi/nh before normalisation -- heading_labels lie in [0, nh)), the
  * residual normalisations of dataset.py:294-298, and pads every scene to n_box_out rows by repeating its last box
  * (run.py:14-24, np.pad mode='edge').  mean_size: HOST (nc,3) doubles (dataset.py:36-45), nc <= 32.  A scene without
  * boxes is an error (the reference skips such scenes, dataset.py:300).  Outputs are the eight model inputs of
- * model.py:22-32, float / int. */
+ * model.py:22-32, float / int.  cls is written to semantic_labels and size_labels as given (a class outside [0, nc) takes the
+ * nearest mean-size row for its residual); what votenet_loss does with such a label is stated there. */
 int votenet_augment_boxes(int b, int n_box_out, const long *box_offset, const double *center, const double *size,
                           const double *heading, const int *cls, const int *flip, const double *angle, const double *rot_cos,
                           const double *rot_sin, const double *scale, const double *mean_size, int nc, int nh,

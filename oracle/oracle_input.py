@@ -27,12 +27,16 @@ def flip_axis_to_camera(pc):
 
 
 def angle2class(angle, num_class):
-    """dataset.py:52-67."""
+    """dataset.py:52-67, with the bin edge at 2 pi wrapped to class 0 (see below)."""
     angle = angle % TWO_PI
     per = TWO_PI / float(num_class)
     shifted = (angle + per / 2) % TWO_PI
     cid = int(shifted / per)
-    return cid, shifted - (cid * per + per / 2)
+    res = shifted - (cid * per + per / 2)
+    # Deviates from dataset.py: shifted < 2 pi, but within an ulp of it the quotient rounds to num_class exactly and dataset.py emits
+    # that class, one past the last bin.  The bin wraps to class 0; the residual stays as computed (about -per / 2), which is class 0's
+    # residual for an angle of 2 pi - per / 2.  votenet_augment_boxes and synth.angle2class do the same.
+    return (0 if cid >= num_class else cid), res
 
 
 def augment_points(raw, choice, flip_x, flip_z, angle, scale, train=True, depth_to_camera=True, literal=False):

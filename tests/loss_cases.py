@@ -39,11 +39,27 @@ def case_ids():
     return ["shape-" + k for k in SHAPES] + ["hand-" + k for k in sorted(loss_ref.HAND_CASES)]
 
 
+def label_case_ids():
+    """The cases with one label at or past its range (loss_ref.LABEL_CASES); "labelbase-<base>" is the same case with every label valid."""
+    return ["label-" + k for k in loss_ref.LABEL_CASES]
+
+
+@functools.lru_cache(maxsize=None)
+def label_box(cid):
+    """-> (scene, box, field, the valid label the bad one replaced) of a "label-" case."""
+    name = cid.split("-", 1)[1]
+    _, (s, j), valid = loss_ref.label_case(name)
+    return s, j, loss_ref.LABEL_CASES[name][0], valid
+
+
 @functools.lru_cache(maxsize=None)
 def load_case(cid):
     """-> seeds, votes, prop, out, gt, kw (nh / ns / nc / pos_thr / neg_thr as the reference and the kernel take them).  Shared: read-only."""
     kind, name = cid.split("-", 1)
-    if kind == "shape":
+    if kind in ("label", "labelbase"):
+        case = loss_ref.label_case(name)[0] if kind == "label" else loss_ref.label_base(name)[0]
+        kw = dict(nh=12, ns=10, nc=10)
+    elif kind == "shape":
         s = SHAPES[name]
         case = loss_ref.shape_case(100 + list(SHAPES).index(name), **s)
         kw = dict(nh=s["nh"], ns=s["ns"], nc=s["nc"])

@@ -16,7 +16,28 @@ def huber(labels, predictions):
     return Fn.huber_loss(predictions, labels, reduction="none", delta=1.0)
 
 
+def sparse_ce(logits, labels):
+    """Mean of tf.nn.sparse_softmax_cross_entropy_with_logits as a GPU computes it: a label outside [0, classes) makes that row's loss
+    NaN and, through the product with a NaN constant, the gradient of every logit of the row NaN.  All labels in range: the same
+    cross_entropy call as ever."""
+    labels = labels.long()
+    valid = (labels >= 0) & (labels < logits.shape[1])
+    if bool(valid.all()):
+        return Fn.cross_entropy(logits, labels, reduction="mean")
+    rows = Fn.cross_entropy(logits, labels.clamp(0, logits.shape[1] - 1), reduction="none")
+    nan = torch.full_like(rows, float("nan"))
+    return (rows * torch.where(valid, torch.ones_like(rows), nan)).mean()
+
+
+def one_hot(labels, depth, dtype):
+    """tf.one_hot: a label outside [0, depth) gives an all-zero row."""
+    return (labels.long()[:, None] == torch.arange(depth, device=labels.device)[None, :]).to(dtype)
+
+
 def votenet_loss(seeds_xyz, votes_xyz, proposals_xyz, out, gt, nh=12, ns=10, nc=10, pos_thr=0.3, neg_thr=0.6):
+    """Labels outside their range are defined as TensorFlow defines them for the reference's ops on a GPU: the class term of a proposal
+    assigned to such a box is NaN with a NaN cotangent over its class block (sparse_ce); its residual prediction is selected by an
+    all-zero one-hot row (model.py:189-193, 200-205), so it is 0 -- Huber of (0 - label residual), no cotangent."""
     bx, lwh, roty = gt["bboxes_xyz"], gt["bboxes_lwh"], gt["bboxes_roty"]
     d2c = (seeds_xyz[:, :, None] - bx[:, None]).abs()
     d2c = rotate_pc_along_y(d2c, -roty)
@@ -31,7 +52,7 @@ def votenet_loss(seeds_xyz, votes_xyz, proposals_xyz, out, gt, nh=12, ns=10, nc=
     pb, pp = torch.nonzero(mind < pos_thr, as_tuple=True)
     nb, npp = torch.nonzero(mind > neg_thr, as_tuple=True)
     pg = passign[pb, pp]
-    ce = lambda lg, lab: Fn.cross_entropy(lg, lab.long(), reduction="mean")
+    ce = sparse_ce
     obj = ce(out[pb, pp, :2], torch.ones_like(pb)) + ce(out[nb, npp, :2], torch.zeros_like(nb))
     center = huber(bx[pb, pg] - proposals_xyz[pb, pp], out[pb, pp, 2:5]).sum(-1).mean()
     dual = dist.argmin(1)
@@ -39,11 +60,11 @@ def votenet_loss(seeds_xyz, votes_xyz, proposals_xyz, out, gt, nh=12, ns=10, nc=
     center = center + huber(bx - proposals_xyz[bi, dual], out[bi, dual, 2:5]).sum(-1).mean()
     hl = gt["heading_labels"][pb, pg].long()
     hcls = ce(out[pb, pp, 5:5 + nh], hl)
-    hres = huber(gt["heading_residuals"][pb, pg], out[pb, pp, 5 + nh:5 + 2 * nh].gather(1, hl[:, None])[:, 0]).mean()
+    hres = huber(gt["heading_residuals"][pb, pg], (out[pb, pp, 5 + nh:5 + 2 * nh] * one_hot(hl, nh, out.dtype)).sum(1)).mean()
     sl = gt["size_labels"][pb, pg].long()
     o = 5 + 2 * nh
     scls = ce(out[pb, pp, o:o + ns], sl)
-    sres_pred = out[pb, pp, o + ns:o + 4 * ns].reshape(-1, ns, 3)[torch.arange(len(pb), device=bx.device), sl]
+    sres_pred = (out[pb, pp, o + ns:o + 4 * ns].reshape(-1, ns, 3) * one_hot(sl, ns, out.dtype)[:, :, None]).sum(1)
     sres = huber(gt["size_residuals"][pb, pg], sres_pred).sum(-1).mean()
     sem = ce(out[pb, pp, -nc:], gt["semantic_labels"][pb, pg])
     box = center + 0.1 * hcls + hres + 0.1 * scls + sres
@@ -117,6 +138,66 @@ def shape_case(seed, b, n, p, bb, nh, ns, nc, pos_thr=0.3, neg_thr=0.6):
     mind, _ = _dec64(seeds, prop, gt)
     assert (mind < pos_thr).any() and (mind > neg_thr).any()
     return seeds, votes, prop, out, gt
+
+
+# ---- labels at or past their range.  LABEL_BASES[base] -> shape of a shape_case whose LAST proposal of the LAST scene (the last row of
+# proposals_output and of its cotangent) is moved next to the box of that scene that already holds the most positives: label_box(base).
+# LABEL_CASES[name] = (ground-truth field, bad value, base): the base with that one label of that one box replaced.  nh, ns, nc = 12, 10, 10.
+LABEL_BASES = {"p64": dict(seed=301, b=2, n=70, p=64, bb=5), "p256": dict(seed=302, b=2, n=70, p=256, bb=5)}
+LABEL_CASES = {
+    "heading-nh": ("heading_labels", 12, "p64"),          # what the box encoder used to emit at a bin edge
+    "heading-minus1": ("heading_labels", -1, "p64"),
+    "size-ns": ("size_labels", 10, "p64"),
+    "size-minus1": ("size_labels", -1, "p64"),
+    "size-ns-plus-1000": ("size_labels", 1010, "p64"),    # an index far outside the row: past the buffer for the last rows
+    "size-ns-plus-1000-p256": ("size_labels", 1010, "p256"),
+    "sem-nc": ("semantic_labels", 10, "p64"),
+    "sem-minus1": ("semantic_labels", -1, "p64"),
+}
+# the entries of the loss vector (loss_cases.NAMES) a bad label of each field makes NaN or changes; every other entry keeps its bits
+LABEL_AFFECTS = {"heading_labels": ("total_cost", "heading_cls_loss", "heading_residual_loss", "box_loss"),
+                 "size_labels": ("total_cost", "size_cls_loss", "size_residual_loss", "box_loss"),
+                 "semantic_labels": ("total_cost", "sem_cls_loss")}
+LABEL_NAN = {"heading_labels": ("total_cost", "heading_cls_loss", "box_loss"), "size_labels": ("total_cost", "size_cls_loss", "box_loss"),
+             "semantic_labels": ("total_cost", "sem_cls_loss")}
+
+
+def label_blocks(field, valid_label, nh=12, ns=10, nc=10):
+    """-> (columns of the class block, columns of the residual slot the VALID label selects) of proposals_output for that field."""
+    so = 5 + 2 * nh
+    if field == "heading_labels":
+        return range(5, 5 + nh), [5 + nh + valid_label]
+    if field == "size_labels":
+        return range(so, so + ns), [so + ns + 3 * valid_label + k for k in range(3)]
+    return range(so + 4 * ns, so + 4 * ns + nc), []
+
+
+def label_base(base):
+    """-> (five-tuple of random_case, (scene, box)).  Decisions keep the margins of shape_case; the moved proposal is positive on its box
+    with the second nearest centre at least 1e-3 further away."""
+    import numpy as np
+    kw = dict(LABEL_BASES[base])
+    seeds, votes, prop, out, gt = shape_case(kw.pop("seed"), nh=12, ns=10, nc=10, **kw)
+    bx = gt["bboxes_xyz"].astype(np.float64)
+    s = prop.shape[0] - 1
+    d = np.linalg.norm(prop.astype(np.float64)[s, :, None] - bx[s][None], axis=-1)
+    j = int(np.bincount(d.argmin(-1)[d.min(-1) < 0.3], minlength=bx.shape[1]).argmax())
+    prop[s, -1] = gt["bboxes_xyz"][s, j] + np.array([0.05, -0.02, 0.03], np.float32)
+    mind, _ = _dec64(seeds, prop, gt)
+    assert not ((np.abs(mind - 0.3) < 1e-3) | (np.abs(mind - 0.6) < 1e-3)).any()
+    dl = np.sort(np.linalg.norm(prop.astype(np.float64)[s, -1] - bx[s], axis=-1))
+    assert dl[0] < 0.3 - 1e-3 and dl[1] - dl[0] >= 1e-3
+    return (seeds, votes, prop, out, gt), (s, j)
+
+
+def label_case(name):
+    """-> (five-tuple with the bad label, (scene, box), the valid label it replaced)."""
+    field, value, base = LABEL_CASES[name]
+    (seeds, votes, prop, out, gt), (s, j) = label_base(base)
+    gt = {k: v.copy() for k, v in gt.items()}
+    valid = int(gt[field][s, j])
+    gt[field][s, j] = value
+    return (seeds, votes, prop, out, gt), (s, j), valid
 
 
 # ---- hand-made cases of the loss kernel's decisions.  Every coordinate, extent, residual and hand-written logit is a multiple of 1/64 and

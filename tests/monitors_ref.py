@@ -145,4 +145,19 @@ def case_no_positive():
     return prop, out, gt, dict(n_obj_correct=6, n_sem_correct=0, n_pos=0, n_neg=7, obj_accuracy=6 / 7, sem_accuracy=float("nan"))
 
 
-HAND_CASES = dict(tie=case_tie, nan_target=case_nan_target, no_positive=case_no_positive)
+def case_label_out_of_range():
+    """A semantic label of nc or -1 is in nobody's top 1 (tf.nn.in_top_k: a target out of range is false) and is not turned into an
+    index: the floats such an index would reach (the next row's first logit; the last size-residual slot) hold scores that would win."""
+    prop, out, gt = _blank(2, 4, 2)
+    gt["semantic_labels"][0] = (10, -1)
+    gt["semantic_labels"][1] = (7, 4)
+    for s, i, j in ((0, 0, 0), (0, 2, 1), (1, 1, 1)):
+        prop[s, i] = gt["bboxes_xyz"][s, j]
+        out[s, i, :2] = (0.0, 1.0)        # positive and says so: obj-correct
+    out[0, 1, 0] = 5.0                    # what column 69 + 10 of row (0, 0) would be: the next row's first float
+    out[0, 2, 68] = 5.0                   # what column 69 - 1 of row (0, 2) is
+    out[1, 1, 69 + 4] = 2.0               # a valid label beside them: correct
+    return prop, out, gt, dict(n_obj_correct=8, n_sem_correct=1, n_pos=3, n_neg=5, obj_accuracy=1.0, sem_accuracy=1 / 3)
+
+
+HAND_CASES = dict(tie=case_tie, nan_target=case_nan_target, no_positive=case_no_positive, label_out_of_range=case_label_out_of_range)

@@ -154,3 +154,80 @@ def test_pipeline_output_feeds_the_train_step(hiplib, dev):
     net.train_step(x, gt=gt)
     assert bool(torch.isfinite(net.last_losses[:10]).all()) and float(net.last_losses[10]) > 0  # positives were assigned
     assert bool(torch.isfinite(net.store.flat).all())
+
+
+# ---------------------------------------------------------------- heading-bin edges
+@pytest.mark.parametrize("nh", [12, 7, 24])
+def test_boxes_heading_bin_edges(hiplib, dev, nh):
+    """votenet_augment_boxes on headings at and one / two floats beside every bin edge and bin centre (test_oracle_input.edge_headings),
+    through all four flip combinations with augmentation angles that are multiples of pi / nh, and once without augmentation; class ids
+    0 .. nc - 1.  For nh = 12 and 24 the list holds, for every flip combination, boxes for which the letter of dataset.py gives class nh
+    (asserted); the kernel and the oracle give class 0 there.  Every output bit for bit, every heading label in [0, nh)."""
+    from test_oracle_input import EDGE_NH_WITH_HITS, edge_box_scenes, edge_oracle
+    from votenet_amd import input_pipeline as IP, synth
+    cen, siz, hed, cls, fx, fz, angle, scale = edge_box_scenes(nh)
+    assert {0, len(synth.MEAN_SIZES) - 1} <= set(np.concatenate(cls).tolist())
+    dc, off = IP.pack_ragged(cen, dev)
+    ds, dh, dk = IP.pack_ragged(siz, dev)[0], IP.pack_ragged(hed, dev)[0], IP.pack_ragged(cls, dev)[0]
+    for train in (True, False):
+        per, hits = edge_oracle(nh, synth.MEAN_SIZES, train=train)
+        print("nh = %d train = %s: boxes whose unwrapped class is nh, per scene: %s" % (nh, train, [int(h.sum()) for h in hits]))
+        if train and nh in EDGE_NH_WITH_HITS:
+            assert all(h.sum() >= 1 for h in hits), "the case list misses the edge for a flip combination"
+        exp = OI.batch_boxes(per)
+        got = IP.augment_boxes(dc, ds, dh, dk, off, IP.Augmentation(fx, fz, angle, scale) if train else None, nh=nh)
+        assert set(got) == set(exp)
+        for k in exp:
+            g = got[k].cpu().numpy()
+            assert g.dtype == exp[k].dtype and g.shape == exp[k].shape, k
+            assert np.array_equal(g, exp[k]), (k, train, np.argwhere(g != exp[k])[:4].tolist())
+        hl = got["heading_labels"].cpu().numpy()
+        assert hl.min() >= 0 and hl.max() < nh
+        for s, h in enumerate(hits):
+            assert (hl[s, :len(h)][h] == 0).all()
+
+
+# ---------------------------------------------------------------- the device draw at the width boundaries of feistel_perm
+DRAW_BATCHES = {                                    # name -> (scene sizes, n_out): ragged inside one launch; n_out <= the smallest scene
+    "tiny-n1": ([1, 2, 3, 4, 5], 1),
+    "whole-1": ([1] * 3, 1), "whole-2": ([2] * 3, 2), "whole-3": ([3] * 2, 3), "whole-4": ([4] * 2, 4), "whole-5": ([5] * 2, 5),
+    "n15": ([15, 16, 17, 255, 256, 257, 15, 4095, 4096, 4097, 16, 16384, 16385, 17, 65536, 65537, 15, 16, 17, 255], 15),
+    "n255": ([255, 256, 257, 4095, 4096, 4097, 16384, 16385, 65536, 65537, 255, 256, 257, 4095, 4096, 4097, 65537, 256], 255),
+    "n256": ([256, 257, 4095, 4096, 4097, 16384, 16385, 65536, 65537, 256, 257, 4096, 4097, 16385, 65536, 65537, 256, 257], 256),
+}
+for _n in (15, 16, 17, 257):                       # n == n_out beside the widths 16 and 256 too
+    DRAW_BATCHES["whole-%d" % _n] = ([_n] * 2, _n)
+DRAW_SEEDS = (0x1234567890AB, 7)                    # one above 2^32 (both halves of the key), one below
+DRAW_SCENE0 = 2 ** 32 - 3                           # scene0 + s + 1 crosses 2^32 inside the batch: the 32-bit wrap of scene_key
+
+
+def draw_scenes(sizes):
+    """Raw clouds whose x column is the row number (exact in float32 up to 2^24): the drawn row can be read off the output."""
+    return [np.stack([np.arange(n), np.full(n, float(i)), np.zeros(n)], 1).astype(np.float32) for i, n in enumerate(sizes)]
+
+
+def check_draw(rows, sizes, n_out, seed, scene0, what):
+    """rows (b, n_out): the raw row numbers an entry drew -> equal to oracle_input.feistel_choice row for row; inside [0, n), distinct,
+    and a whole permutation where n == n_out."""
+    for s, n in enumerate(sizes):
+        want = OI.feistel_choice(n, n_out, seed, scene0 + s)
+        assert np.array_equal(rows[s], want), (what, s, n, rows[s][:8].tolist(), want[:8].tolist())
+        assert rows[s].min() >= 0 and rows[s].max() < n and len(set(rows[s].tolist())) == n_out, (what, s, n)
+        if n == n_out:
+            assert sorted(rows[s].tolist()) == list(range(n)), (what, s, n)
+
+
+@pytest.mark.parametrize("name", sorted(DRAW_BATCHES))
+def test_device_draw_equals_its_restatement_at_the_width_boundaries(hiplib, dev, name):
+    """subsample_augment with choice=None, aug=None against oracle_input.feistel_choice at scene sizes on both sides of every width of
+    feistel_perm's loop `while ((1 << bits) < n) bits += 2` (4, 16, 256, 4096, 65536; 16384 is no boundary and must not be one), sizes
+    1 .. 5, and n == n_out (the draw is then a whole permutation); scenes of different sizes in one launch and across the 16-scene
+    chunk; two seeds; scene numbers that cross 2^32."""
+    from votenet_amd import input_pipeline as IP
+    sizes, n_out = DRAW_BATCHES[name]
+    assert n_out <= min(sizes)
+    raw, off = IP.pack_ragged(draw_scenes(sizes), dev)
+    for seed in DRAW_SEEDS:
+        got = IP.subsample_augment(raw, off, n_out, None, None, seed=seed, scene0=DRAW_SCENE0, depth_to_camera=False).cpu().numpy()
+        assert np.array_equal(got[:, :, 1], np.repeat(np.arange(len(sizes), dtype=np.float32)[:, None], n_out, 1))  # rows of its own scene
+        check_draw(got[:, :, 0].astype(np.int64), sizes, n_out, seed, DRAW_SCENE0, (name, seed))

@@ -297,3 +297,117 @@ def test_decode_boxes_hand_cases(hiplib, dev, b, p, nh):
     assert extent(5)[1] > 0.1 and np.hypot(extent(5)[0], extent(5)[2]) < 1e-5    # l and w on the floor, h untouched
     # the first of a tie, told by its residuals: class 4 of the last row has h on the floor, class 8 would not
     assert extent(-1)[1] < 1e-5 and extent(4)[1] == pytest.approx(synth.MEAN_SIZES[3][2] * 1.125, rel=1e-5)
+
+
+# ---------------------------------------------------------------- labels at or past their range (loss_ref.LABEL_CASES)
+import functools  # noqa: E402
+
+from loss_cases import label_box, label_case_ids  # noqa: E402
+
+LABEL_GUARD = 4096          # elements of sentinel on both sides of every buffer: more than the widest index a label of these cases could make (column 3071)
+F_SENTINEL, I_SENTINEL = -7777.0, 0x5A5A5A5A
+
+
+def _inside_sentinels(a, dev, zero=False):
+    """A buffer with the contents of `a` (or zeros of its shape) in the middle of a sentinel-filled tensor -> (whole tensor, view)."""
+    t = torch.from_numpy(np.array(a))  # (a copy: the shared cases are read-only)
+    big = torch.full((LABEL_GUARD + t.numel() + LABEL_GUARD,), I_SENTINEL if t.dtype == torch.int32 else F_SENTINEL, dtype=t.dtype, device=dev)
+    view = big[LABEL_GUARD:LABEL_GUARD + t.numel()].view(t.shape)
+    if zero:
+        view.zero_()
+    else:
+        view.copy_(t.to(dev))
+    return big, view
+
+
+def _margins_intact(big, n):
+    fill = I_SENTINEL if big.dtype == torch.int32 else F_SENTINEL
+    return bool((big[:LABEL_GUARD] == fill).all()) and bool((big[LABEL_GUARD + n:] == fill).all())
+
+
+def run_case_inside_sentinels(dev, cid):
+    """The case through the C ABI with every input and every output carved out of a sentinel-filled tensor of its own.  Asserts that no
+    margin was written and no input changed; -> (losses, cotangents) as CPU tensors."""
+    from votenet_amd import _lib as L
+    seeds, votes, prop, out, gt, kw = load_case(cid)
+    b, n, p, bb = seeds.shape[0], seeds.shape[1], prop.shape[1], gt["bboxes_xyz"].shape[1]
+    GT = ("bboxes_xyz", "bboxes_lwh", "bboxes_roty", "semantic_labels", "heading_labels", "heading_residuals", "size_labels", "size_residuals")
+    host = dict(seeds=seeds, votes=votes, prop=prop, out=out, **{k: gt[k] for k in GT})
+    ins = {k: _inside_sentinels(a, dev) for k, a in host.items()}
+    nws = int(L.lib().votenet_loss_workspace_floats(b))
+    outs = dict(losses=_inside_sentinels(np.zeros(12, np.float32), dev, zero=True), d_votes=_inside_sentinels(votes, dev, zero=True),
+                d_prop=_inside_sentinels(prop, dev, zero=True), d_out=_inside_sentinels(out, dev, zero=True),
+                ws=_inside_sentinels(np.zeros(nws, np.float32), dev, zero=True))
+    P = lambda k: L.ptr((ins[k] if k in ins else outs[k])[1])
+    L.check(L.lib().votenet_loss(b, n, p, bb, kw["nh"], kw["ns"], kw["nc"], P("seeds"), P("votes"), P("prop"), P("out"), P("bboxes_xyz"),
+                                 P("bboxes_lwh"), P("bboxes_roty"), P("semantic_labels"), P("heading_labels"), P("heading_residuals"),
+                                 P("size_labels"), P("size_residuals"), 0.3, 0.6, P("losses"), P("d_votes"), P("d_prop"), P("d_out"),
+                                 P("ws"), L.stream_ptr()))
+    torch.cuda.synchronize()
+    for k, (big, view) in list(ins.items()) + list(outs.items()):
+        assert _margins_intact(big, view.numel()), "the margin of %s was written" % k
+    for k, (big, view) in ins.items():
+        assert np.array_equal(view.cpu().numpy(), host[k]), "input %s was written" % k
+    return outs["losses"][1].cpu(), dict(votes_xyz=outs["d_votes"][1].cpu(), proposals_xyz=outs["d_prop"][1].cpu(),
+                                         proposals_output=outs["d_out"][1].cpu())
+
+
+@functools.lru_cache(maxsize=None)
+def _valid_label_run(dev, base):
+    return run_case_inside_sentinels(dev, "labelbase-" + base)
+
+
+def _i32(t):
+    return t.contiguous().view(torch.int32)
+
+
+@pytest.mark.parametrize("cid", label_case_ids())
+def test_loss_label_outside_its_range(hiplib, dev, cid):
+    """One ground-truth box carries one label at or past its range (heading nh / -1, size ns / -1 / ns + 1000, semantic nc / -1); positives
+    are assigned to it, the last row of the buffers among them.  Defined behaviour (include/votenet_hip.h, tests/loss_ref.py): the class
+    term is NaN and the class block of those proposals' cotangent rows is NaN; the residual prediction is 0 (an all-zero one-hot row):
+    Huber(0 - label residual) in the loss, no cotangent.  Checked here:
+    - every input and output lies between 4096-element sentinel margins, none of which changes, and no input changes;
+    - NaN exactly where the float64 reference has NaN; everything finite at the bar of the other tests (1e-5 relative, floors 1.0 and
+      1e-3), bit-zero where the reference is exactly zero;
+    - against the device's own run with the valid label: the loss terms the label does not enter, the votes' and proposal centres'
+      cotangents, and every entry of proposals_output's cotangent outside the class block and the valid label's residual slot of the
+      mislabelled box's positives keep every bit."""
+    losses, cot = run_case_inside_sentinels(dev, cid)
+    s, j, field, valid = label_box(cid)
+    base = loss_ref.LABEL_CASES[cid.split("-", 1)[1]][2]
+    losses0, cot0 = _valid_label_run(dev, base)
+    r, g = reference(cid)
+    r0, g0 = reference("labelbase-" + base)
+    got, got0 = dict(zip(NAMES + ["n_pos", "n_neg"], losses.tolist())), dict(zip(NAMES + ["n_pos", "n_neg"], losses0.tolist()))
+    print("label_case %s box (%d, %d) valid label %d losses %s" % (cid, s, j, valid, got))
+    assert int(got["n_pos"]) == r["n_pos"] > 0 and int(got["n_neg"]) == r["n_neg"] > 0
+    for i, k in enumerate(NAMES):
+        want = float(r[k])
+        if np.isnan(want):
+            assert k in loss_ref.LABEL_NAN[field] and np.isnan(got[k]), (k, got[k])
+        else:
+            assert abs(got[k] - want) <= 1e-5 * max(1.0, abs(want)), (k, got[k], want)
+        if k not in loss_ref.LABEL_AFFECTS[field]:
+            assert torch.equal(_i32(losses[i:i + 1]), _i32(losses0[i:i + 1])), (k, got[k], got0[k])
+        assert abs(got0[k] - float(r0[k])) <= 1e-5 * max(1.0, abs(float(r0[k]))), (k, got0[k], float(r0[k]))  # the valid run is a valid run
+    for name, ref in g.items():
+        d = cot[name]
+        nan = torch.isnan(ref)
+        assert torch.equal(torch.isnan(d), nan), name
+        fin = ~nan
+        err = float((d.double()[fin] - ref[fin]).abs().max()) / max(1e-3, float(ref[fin].abs().max()))
+        print("label_case %s %s error %.2e NaN entries %d" % (cid, name, err, int(nan.sum())))
+        assert err <= 1e-5, (name, err)
+        assert int((_i32(d)[ref == 0] != 0).sum()) == 0, name
+    assert torch.equal(_i32(cot["votes_xyz"]), _i32(cot0["votes_xyz"])) and torch.equal(_i32(cot["proposals_xyz"]), _i32(cot0["proposals_xyz"]))
+    mine = (r["positive"][s] & (r["bboxes_assignment"][s] == j)).numpy()
+    cls_cols, res_cols = loss_ref.label_blocks(field, valid)
+    may_differ = np.zeros(cot["proposals_output"].shape, bool)
+    may_differ[s][np.ix_(mine, list(cls_cols) + list(res_cols))] = True
+    a, a0 = _i32(cot["proposals_output"]).numpy(), _i32(cot0["proposals_output"]).numpy()
+    assert mine.sum() >= 2 and mine[-1] and s == a.shape[0] - 1
+    assert np.array_equal(a[~may_differ], a0[~may_differ])
+    assert np.isnan(cot["proposals_output"].numpy()[s][np.ix_(mine, list(cls_cols))]).all()
+    if res_cols:
+        assert (a[s][np.ix_(mine, res_cols)] == 0).all() and (a0[s][np.ix_(mine, res_cols)] != 0).all()

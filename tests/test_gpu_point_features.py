@@ -250,3 +250,20 @@ def test_build_batch_carries_the_features(hiplib, dev, golden):
     assert set(gt) == set(plain_gt) | {"features"} and all(torch.equal(gt[k], plain_gt[k]) for k in plain_gt)
     _, feats, _ = IP.subsample_augment_features(raw, off, n_out, aug, choice, height=True, extra_cols=extra)
     assert torch.equal(gt["features"], feats[torch.from_numpy(scene_index).to(dev)]) and gt["features"].shape == (len(scene_index), n_out, 1 + extra)
+
+
+def test_device_draw_at_the_width_boundaries(hiplib, dev):
+    """The features entry draws through the same feistel_perm: scene sizes on both sides of every width of its loop, in one ragged batch
+    across the 16-scene chunk, against oracle_input.feistel_choice row for row (test_gpu_input.check_draw), and the points of
+    subsample_augment bit for bit."""
+    from test_gpu_input import DRAW_BATCHES, DRAW_SCENE0, DRAW_SEEDS, check_draw, draw_scenes
+    from votenet_amd import input_pipeline as IP
+    sizes, n_out = DRAW_BATCHES["n256"]
+    raw, off = pack(draw_scenes(sizes), dev)
+    for seed in DRAW_SEEDS:
+        points, feats, floor = IP.subsample_augment_features(raw, off, n_out, None, None, seed=seed, scene0=DRAW_SCENE0,
+                                                             depth_to_camera=False, height=True, extra_cols=0)
+        assert torch.equal(points, IP.subsample_augment(raw, off, n_out, None, None, seed=seed, scene0=DRAW_SCENE0, depth_to_camera=False))
+        got = points.cpu().numpy()
+        assert np.array_equal(got[:, :, 1], np.repeat(np.arange(len(sizes), dtype=np.float32)[:, None], n_out, 1))
+        check_draw(got[:, :, 0].astype(np.int64), sizes, n_out, seed, DRAW_SCENE0, ("features", seed))

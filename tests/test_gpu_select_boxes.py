@@ -252,3 +252,26 @@ def test_invalid_arguments_raise_and_leave_no_sticky_error(hiplib, dev, golden):
     assert out["box_offset"].tolist() == [0, 0, 0] and out["center"].shape == (0, 3)
     assert set(out["status"].cpu().numpy().tolist()) <= {1, 2, 3}
     torch.cuda.synchronize()
+
+
+def test_device_draw_at_the_width_boundaries(hiplib, dev):
+    """select_boxes tests the rows feistel_perm draws: scene sizes on both sides of every width of its loop, in one ragged batch across
+    the 8-scene chunks.  Every scene has one object whose box holds exactly the even raw rows (z = 0; the odd ones lie at z = 100), so
+    the `inside` mask of output row j is the parity of the drawn row: against oracle_input.feistel_choice row for row."""
+    from test_gpu_input import DRAW_BATCHES, DRAW_SCENE0, DRAW_SEEDS
+    from votenet_amd import input_pipeline as IP, sunrgbd
+    sizes, n_out = DRAW_BATCHES["n256"]
+    clouds = [np.stack([np.arange(n), np.ones(n), 100.0 * (np.arange(n) % 2)], 1).astype(np.float32) for n in sizes]
+    raw, off = IP.pack_ragged(clouds, dev)
+    calib = [(np.eye(3), np.eye(3))] * len(sizes)   # pixel (x / y, -z / y) with y = 1: every point in front of the camera
+    one = {"cls": np.array([3], np.int32), "box2d": np.array([[-1e9, -1e9, 1e9, 1e9]]), "centroid": np.array([[0.0, 1.0, 0.0]]),
+           "half_extent": np.array([[1e9, 1e9, 1.0]]), "heading": np.array([0.0])}
+    objects = sunrgbd.pack_objects([one] * len(sizes))
+    for seed in DRAW_SEEDS:
+        out = IP.select_boxes(raw, off, calib, objects, n_out, None, seed, DRAW_SCENE0, want_inside=True)
+        inside, n_inside = out["inside"].cpu().numpy().astype(bool), out["n_inside"].cpu().numpy()
+        for s, n in enumerate(sizes):
+            want = OI.feistel_choice(n, n_out, seed, DRAW_SCENE0 + s) % 2 == 0
+            assert np.array_equal(inside[s], want), (seed, s, n)
+            assert n_inside[s] == want.sum() >= 5
+        assert (out["status"].cpu().numpy() == 0).all() and out["box_offset"].tolist() == list(range(len(sizes) + 1))

@@ -254,6 +254,34 @@ def test_guarded_steps_train_bit_identically_and_a_poisoned_step_does_no_harm(hi
     assert on.step_guard.read()["consecutive"] == 0 and on.step_guard.read()["seen"] == 6
 
 
+def test_a_label_outside_its_range_is_a_skipped_step(hiplib, dev):
+    """Ground truth whose semantic labels are all nc (one past the last class): votenet_loss makes the class term and the class block's
+    cotangents of every positive proposal NaN (include/votenet_hip.h), the gradient is not finite, and the guard skips the step: the
+    four buffers keep every bit.  The nets, batches and steps are those of the test above, whose fourth step has positive proposals."""
+    from votenet_amd import mlp as M
+    from votenet_amd import synth
+    batches = _batches(dev, (500, 502, 504, 506))
+    prev = M.set_deterministic(True)
+    try:
+        on = _net(dev, 9, True)
+        for x, gt in batches[:3]:
+            on.train_step(x, gt=gt)
+        before = _four(on)
+        x, gt = batches[3]
+        gt_bad = dict(gt)
+        gt_bad["semantic_labels"] = torch.full_like(gt["semantic_labels"], synth.NC)
+        on.train_step(x, gt=gt_bad)
+        l = on.last_losses.cpu().numpy()
+        assert l[10] > 0, "no positive proposal: the label was never used"
+        assert np.isnan(l[0]) and np.isnan(l[8]) and np.isfinite(l[[1, 2, 3, 4, 5, 6, 7, 9]]).all()
+        assert not torch.isfinite(on.store.grad).all()
+        assert _same(_four(on), before), "a skipped step changed parameters, moments or moving averages"
+        r = on.step_guard.read()
+        assert (r["seen"], r["skipped"], r["consecutive"], r["last_skip_step"]) == (4, 1, 1, 4)
+    finally:
+        M.set_deterministic(prev)
+
+
 def test_guarded_steps_through_the_captured_stretch(hiplib, dev, monkeypatch):
     """The default mode: the first step of a shape runs launch by launch, the following ones replay the captured stretch.  Two nets
     cannot be compared there (atomics), so every guarded optimizer call is checked against votenet_clip_adam on copies of exactly

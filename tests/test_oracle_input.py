@@ -1,6 +1,7 @@
 """CPU: the input-pipeline oracle (oracle/oracle_input.py) against the reference's own formulas written literally, and the
 host draws of votenet_amd/input_pipeline.py against the reference's draw order (dataset.py:185-186,219-231)."""
 import numpy as np
+import pytest
 
 from oracle import oracle_input as OI
 
@@ -96,3 +97,103 @@ def test_host_draws_follow_the_reference_order():
     ch = IP.draw_choice(r1, [5000, 3000], 2048)
     assert ch.dtype == np.int32 and np.array_equal(ch[0], r2.choice(5000, 2048, replace=False))
     assert np.array_equal(ch[1], r2.choice(3000, 2048, replace=False))
+
+
+# ---------------------------------------------------------------- heading-bin edges (shared with tests/test_gpu_input.py)
+EDGE_FLIPS = ((0, 0), (1, 0), (0, 1), (1, 1))
+EDGE_ANGLE_STEPS = (0, 1, -2, 3)  # the scene's augmentation angle in units of pi / nh: itself a bin edge or a bin centre
+# 2 pi / nh times nh rounds below 2 pi only for nh = 3, 6, 12, 24 (of 1..32): only there can int(shifted / per) come out as nh
+EDGE_NH_WITH_HITS = (12, 24)
+
+
+def angle2class_unwrapped(angle, num_class):
+    """dataset.py:52-67 to the letter: what oracle_input.angle2class was before the bin edge at 2 pi wrapped to class 0."""
+    angle = angle % (2 * np.pi)
+    per = 2 * np.pi / float(num_class)
+    shifted = (angle + per / 2) % (2 * np.pi)
+    cid = int(shifted / per)
+    return cid, shifted - (cid * per + per / 2)
+
+
+def edge_headings(nh):
+    """Every multiple of pi / nh in [-2 pi, 2 pi] (bin edges and bin centres) with its neighbours up to two floats on each side, and
+    +-0, +-2 pi, the float below 2 pi, +-1e6, +-1e-320."""
+    out = []
+    for k in range(-2 * nh, 2 * nh + 1):
+        lo = hi = h = k * (np.pi / nh)
+        out.append(h)
+        for _ in range(2):
+            lo, hi = np.nextafter(lo, -np.inf), np.nextafter(hi, np.inf)
+            out += [lo, hi]
+    return np.array(out + [0.0, -0.0, 2 * np.pi, -2 * np.pi, np.nextafter(2 * np.pi, 0.0), 1e6, -1e6, 1e-320, -1e-320])
+
+
+def edge_box_scenes(nh, nc=10):
+    """Four scenes, one per flip combination, each holding every edge heading (scene s drops its first s boxes: ragged, so the padding
+    runs too); class ids cycle through 0 .. nc - 1.  -> (centres, sizes, headings, classes: lists of per-scene arrays; flip_x, flip_z,
+    angle, scale: per-scene arrays)."""
+    rng = np.random.default_rng(100 + nh)
+    H = edge_headings(nh)
+    cen, siz, hed, cls = [], [], [], []
+    for s in range(4):
+        h = H[s:]
+        cen.append(rng.normal(size=(len(h), 3)) * 2)
+        siz.append(np.abs(rng.normal(size=(len(h), 3))) + 0.3)
+        hed.append(h.copy())
+        cls.append(((np.arange(len(h)) + s) % nc).astype(np.int32))
+    fx, fz = np.array([f[0] for f in EDGE_FLIPS], bool), np.array([f[1] for f in EDGE_FLIPS], bool)
+    angle = np.array(EDGE_ANGLE_STEPS, np.float64) * (np.pi / nh)
+    return cen, siz, hed, cls, fx, fz, angle, np.array([1.0, 0.93, 1.07, 1.1])
+
+
+def edge_oracle(nh, mean_size, train=True):
+    """The oracle on edge_box_scenes(nh) -> (per-scene tuples of oracle_input.augment_boxes, per-scene bool arrays: the letter of
+    dataset.py gives class nh for that box)."""
+    cen, siz, hed, cls, fx, fz, angle, scale = edge_box_scenes(nh)
+    per = [OI.augment_boxes(cen[s], siz[s], hed[s], cls[s], train and fx[s], train and fz[s], angle[s] if train else 0.0,
+                            scale[s] if train else 1.0, mean_size, nh, train=train) for s in range(4)]
+    hits = [np.array([angle2class_unwrapped(a, nh)[0] == nh for a in p[2]]) for p in per]
+    return per, hits
+
+
+@pytest.mark.parametrize("nh", [12, 7, 24])
+def test_heading_bin_edge_wraps_to_class_zero(nh):
+    """At the edge the letter of dataset.py gives class nh; the oracle gives class 0 with the residual as computed, which decodes
+    (class2angle, dataset.py:70-78) to the angle; everywhere else the oracle is the letter of dataset.py."""
+    from votenet_amd import synth
+    per, hits = edge_oracle(nh, np.asarray(synth.MEAN_SIZES, np.float64))
+    print("nh = %d: boxes whose unwrapped class is nh, per flip combination: %s" % (nh, [int(h.sum()) for h in hits]))
+    if nh in EDGE_NH_WITH_HITS:
+        assert all(h.sum() >= 1 for h in hits), "the case list misses the edge for a flip combination"
+    else:
+        assert not any(h.any() for h in hits)
+    for p, hit in zip(per, hits):
+        rot, hl, hr = p[2], p[4], p[5]
+        assert hl.min() >= 0 and hl.max() < nh
+        for a, c, r, e in zip(rot, hl, hr, hit):
+            uc, ur = angle2class_unwrapped(a, nh)
+            assert r == ur / (np.pi / nh)
+            assert (c == 0 and uc == nh and abs(r + 1.0) < 1e-9) if e else c == uc
+            assert abs(r) <= 1.0 + 1e-9
+            back = c * (2 * np.pi / nh) + r * (np.pi / nh)
+            assert abs(((back - a + np.pi) % (2 * np.pi)) - np.pi) < 1e-9 * max(1.0, abs(a))
+            assert synth.angle2class(a, nh) == OI.angle2class(a, nh)  # the package's own mirror (synth.room_gt) encodes alike
+
+
+def test_committed_fixtures_are_unchanged_by_the_wrap(golden):
+    """No heading of the committed ground-truth fixture sits on the wrapped edge, under any flip combination, at the angles of the edge
+    cases and at drawn ones: what the GPU tests expect of these fixtures is what it was."""
+    from votenet_amd import input_pipeline as IP, synth
+    g = golden("select_boxes")
+    heads = np.concatenate([g["obj_heading"]] + [g["heading_f64_%d" % s] for s in range(int(g["b"]))])
+    angles = [m * np.pi / synth.NH for m in EDGE_ANGLE_STEPS] + list(IP.draw_augmentation(8, np.random.RandomState(4)).angle) \
+        + list(IP.draw_augmentation(1, np.random.RandomState(8)).angle)
+    n = 0
+    for h in heads:
+        for fx, fz in EDGE_FLIPS:
+            for ang in angles:
+                a = (np.pi - h) if fx else h
+                a = (-a if fz else a) + ang
+                assert OI.angle2class(a, synth.NH) == angle2class_unwrapped(a, synth.NH)
+                n += 1
+    assert n > 1000

@@ -67,6 +67,9 @@ __global__ void augment_boxes_kernel(AugScenes P, int bb, const double *__restri
         const double shifted = py_mod(a + per / 2, two_pi);
         const int cid = (int)(shifted / per);
         const double res = shifted - (cid * per + per / 2);
+        // shifted < 2 pi, but within an ulp of it the quotient rounds to nh exactly.  dataset.py would emit class nh; here the bin wraps to
+        // class 0 and the residual stays as computed: the angle is 2 pi - per / 2 to an ulp, whose residual in class 0 is that -per / 2.
+        const int hcls = cid >= nh ? 0 : cid;
         const long o = (long)sc * bb + slot;
         O.xyz[o * 3] = (float)cx;
         O.xyz[o * 3 + 1] = (float)cy;
@@ -76,7 +79,7 @@ __global__ void augment_boxes_kernel(AugScenes P, int bb, const double *__restri
         O.lwh[o * 3 + 2] = (float)h;
         O.roty[o] = (float)ang;
         O.sem[o] = k;
-        O.hlab[o] = cid;
+        O.hlab[o] = hcls;
         O.hres[o] = (float)(res / (pi / nh)); // dataset.py:296
         O.slab[o] = k;
         O.sres[o * 3] = (float)((l - M.v[km][0]) / M.v[km][0]); // dataset.py:83,298

@@ -35,7 +35,8 @@ __device__ __forceinline__ float huber(float e, float &grad) // tf.losses.huber_
     return a <= 1.0f ? 0.5f * e * e : a - 0.5f;
 }
 
-// softmax cross entropy of `c` logits (stride 1) against `label`; probs[] receives softmax - onehot
+// softmax cross entropy of `c` logits (stride 1) against `label`; probs[] receives softmax - onehot.  A label outside [0, c) indexes
+// nothing: the loss and all c entries of probs[] are NaN (tf.nn.sparse_softmax_cross_entropy_with_logits on a GPU).
 __device__ __forceinline__ float softmax_ce(const float *lg, int c, int label, float *probs)
 {
     float m = lg[0];
@@ -44,6 +45,11 @@ __device__ __forceinline__ float softmax_ce(const float *lg, int c, int label, f
     for (int i = 0; i < c; i++) {
         probs[i] = expf(lg[i] - m);
         s += probs[i];
+    }
+    if ((unsigned)label >= (unsigned)c) {
+        const float nan = __uint_as_float(0x7FC00000u);
+        for (int i = 0; i < c; i++) probs[i] = nan;
+        return nan;
     }
     const float inv = 1.0f / s;
     for (int i = 0; i < c; i++) probs[i] = probs[i] * inv - (i == label ? 1.0f : 0.0f);
@@ -175,23 +181,28 @@ __global__ __launch_bounds__(LOSS_T) void votenet_loss_kernel(LossArgs A, int *c
                 go[2 + k] += gr * inv_np;                  // this thread owns the proposal here; the dual term adds below, behind a barrier
                 A.d_pxyz[q * 3 + k] += gr * inv_np;        // d(error)/d(proposal centre) = +1
             }
+            // The labels are device data nobody has screened.  One outside its range selects no column of this row: the class term is NaN
+            // (softmax_ce), and the residual prediction is the sum over an all-zero tf.one_hot row (model.py:189-193, 200-205), 0 --
+            // Huber of (0 - label residual), no cotangent.  No label is ever turned into an address outside its own block.
             // heading class (0.1) and residual (1)
             const int hl = A.hlab[gi];
+            const bool hok = (unsigned)hl < (unsigned)NH;
             acc[5] += softmax_ce(o + 5, NH, hl, pr);
             for (int i = 0; i < NH; i++) go[5 + i] = pr[i] * (0.1f * inv_np);
             {
                 float gr;
-                acc[6] += huber(o[5 + NH + hl] - A.hres[gi], gr);
-                go[5 + NH + hl] = gr * inv_np;
+                acc[6] += huber((hok ? o[5 + NH + hl] : 0.0f) - A.hres[gi], gr);
+                if (hok) go[5 + NH + hl] = gr * inv_np;
             }
             // size class (0.1) and residual (1)
             const int sl = A.slab[gi], so = 5 + 2 * NH;
+            const bool sok = (unsigned)sl < (unsigned)NS;
             acc[7] += softmax_ce(o + so, NS, sl, pr);
             for (int i = 0; i < NS; i++) go[so + i] = pr[i] * (0.1f * inv_np);
             for (int k = 0; k < 3; k++) {
                 float gr;
-                acc[8] += huber(o[so + NS + sl * 3 + k] - A.sres[gi * 3 + k], gr);
-                go[so + NS + sl * 3 + k] = gr * inv_np;
+                acc[8] += huber((sok ? o[so + NS + sl * 3 + k] : 0.0f) - A.sres[gi * 3 + k], gr);
+                if (sok) go[so + NS + sl * 3 + k] = gr * inv_np;
             }
             // semantic class (0.1)
             const int co = W - NC;

@@ -74,7 +74,9 @@ def angle2class(angle, num_class=NH):
     per = 2 * np.pi / float(num_class)
     shifted = (angle + per / 2) % (2 * np.pi)
     cid = int(shifted / per)
-    return cid, shifted - (cid * per + per / 2)
+    res = shifted - (cid * per + per / 2)
+    # deviates from dataset.py: within an ulp of 2 pi the quotient rounds to num_class; that bin is class 0 with the residual as computed
+    return (0 if cid >= num_class else cid), res
 
 
 def room_gt(b, n, seed0=1000, **kw):
