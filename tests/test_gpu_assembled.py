@@ -14,7 +14,14 @@ def relerr(a, b):
 @pytest.mark.parametrize("b,n,m,k,cf,c0,c1,radius", [(2, 600, 64, 64, 128, 128, 128, 0.5), (1, 400, 32, 64, 16, 64, 64, 0.3),
                                                      (2, 300, 16, 32, 32, 128, 256, 0.25), (1, 500, 8, 16, 8, 64, 320, 2.0)])
 def test_assembled_first_layer_matches_the_materialised_layer(hiplib, dev, gemm_form, b, n, m, k, cf, c0, c1, radius):
+    assembled_first_layer(dev, gemm_form, b, n, m, k, cf, c0, c1, radius)
+
+
+def assembled_first_layer(dev, gemm_form, b, n, m, k, cf, c0, c1, radius, run=None):
+    """The body of the test above.  run(tag, fn) -> fn(): how the two fused GEMMs are launched (tests/test_gpu_tile_walk.py launches them
+    under its workgroup caps and hands back the walked launch's results); -> the rows of the GEMMs."""
     from votenet_amd import mlp as M
+    run = run or (lambda tag, fn: fn())
     from votenet_amd import tf_grouping, tf_sampling
     g = torch.Generator().manual_seed(3 * n + cf)
     rnd = lambda *s: torch.randn(*s, generator=g).to(dev)
@@ -59,7 +66,7 @@ def test_assembled_first_layer_matches_the_materialised_layer(hiplib, dev, gemm_
     gamma0, beta0 = rnd(c0) * 0.2 + 1.0, rnd(c0) * 0.1
     bn0 = M.PendingBN(st, gamma0, beta0, rows)
     # second layer forward: the assembled loader against the ordinary GEMM on the materialised z0 with the same BatchNorm
-    z1, st1 = M.assembled_linear(geo, P, wx, w1, None, bn0)
+    z1, st1 = run("assembled", lambda: M.assembled_linear(geo, P, wx, w1, None, bn0))
     z1m, st1m = M.linear_dense(z0, w1, None, bn0.scale, bn0.shift, True)
     assert relerr(z1, z1m) < 1e-6 and relerr(st1, st1m) < 1e-6
     a0 = torch.relu(z0.double() * bn0.scale.double() + bn0.shift.double())
@@ -71,7 +78,7 @@ def test_assembled_first_layer_matches_the_materialised_layer(hiplib, dev, gemm_
     M.wgrad_dense_bn(z0, z1, coef1, True, dwm, da=da1, in_scale=bn0.scale, in_shift=bn0.shift, in_relu=True)
     assert relerr(dw, dwm) < 1e-5
     below = (bn0.scale, bn0.shift, bn0.mean, bn0.var, True)
-    da0, sums = M.assembled_dgrad_bn_reduce(z1, coef1, True, wT, da1, geo, P, wx, below)
+    da0, sums = run("assembled", lambda: M.assembled_dgrad_bn_reduce(z1, coef1, True, wT, da1, geo, P, wx, below))
     split_k, M.SPLIT_K = M.SPLIT_K, False  # bit for bit against the UNSPLIT stored-layer kernel (split-K adds the same products in another order)
     try:
         da0m, sumsm = M.dgrad_bn(z1, coef1, True, wT, da=da1, below=(z0,) + below)
@@ -88,6 +95,7 @@ def test_assembled_first_layer_matches_the_materialised_layer(hiplib, dev, gemm_
     assert relerr(S, Sm) < 1e-5 and relerr(dwx, dwxm) < 1e-4
     img.close()
     img_f.close()
+    return rows
 
 
 def test_model_with_and_without_the_assembled_first_layers(hiplib, dev):

@@ -74,9 +74,17 @@ def _totals(t_full, half, dev):
 
 @pytest.mark.parametrize("b,n,m,cf,c2,radius", [(2, 600, 64, 128, 256, 0.5), (1, 500, 48, 32, 128, 0.42), (2, 400, 32, 64, 256, 0.62)])
 def test_stage_kernels_on_compact_rows_match_the_full_layout(hiplib, dev, gemm_form, b, n, m, cf, c2, radius):
+    stage_kernels_on_compact_rows(dev, gemm_form, b, n, m, cf, c2, radius)
+
+
+def stage_kernels_on_compact_rows(dev, gemm_form, b, n, m, cf, c2, radius, c0=128, c1=128, run=None):
+    """The body of the test above (c0, c1: the widths of the first two layers).  run(tag, fn) -> fn(): how the fused GEMMs of the piece
+    layout are launched (tests/test_gpu_tile_walk.py launches them under its workgroup caps and hands back the walked launch's
+    results); -> the compact rows."""
     from votenet_amd import mlp as M
     from votenet_amd import tf_grouping, tf_sampling
-    k, c0, c1 = 64, 128, 128
+    run = run or (lambda tag, fn: fn())
+    k = 64
     g = torch.Generator().manual_seed(7 * n + cf)
     rnd = lambda *s: torch.randn(*s, generator=g).to(dev)
     xyz = (torch.rand(b, n, 3, generator=g) * 2.0).to(dev)
@@ -106,7 +114,7 @@ def test_stage_kernels_on_compact_rows_match_the_full_layout(hiplib, dev, gemm_f
     gamma0 = rnd(c0) * 0.2 + 1.0
     bn0 = M.PendingBN(st0, gamma0, rnd(c0) * 0.1, rows)
     z1, st1 = M.assembled_linear(geo, P, wx, w1, None, bn0)
-    z1h, st1h = M.assembled_linear(half.geo, P, wx, w1, None, bn0, half=half)
+    z1h, st1h = run("assembled_half", lambda: M.assembled_linear(half.geo, P, wx, w1, None, bn0, half=half))
     assert torch.equal(z1h, z1[full])
     assert relerr(st1h[:c1], st1[:c1]) < 1e-6 and relerr(st1h[c1:], st1[c1:]) < 1e-6
     bn1 = M.PendingBN(st1, rnd(c1) * 0.2 + 1.0, rnd(c1) * 0.1, rows)
@@ -158,7 +166,7 @@ def test_stage_kernels_on_compact_rows_match_the_full_layout(hiplib, dev, gemm_f
     bn0.finalize()
     below0 = (bn0.scale, bn0.shift, bn0.mean, bn0.var, True)
     da0, sums0 = M.assembled_dgrad_bn_reduce(z1, coef1, True, w1T, da1, geo, P, wx, below0)
-    da0h, sums0h = M.assembled_dgrad_bn_reduce(z1h, coef1, True, w1T, da1h, half.geo, P, wx, below0, half=half)
+    da0h, sums0h = run("assembled_half", lambda: M.assembled_dgrad_bn_reduce(z1h, coef1, True, w1T, da1h, half.geo, P, wx, below0, half=half))
     assert relerr(da0h, _totals(da0, half, dev)) < 1e-5
     z0 = M.assemble_z0(geo, P, wx)
     scale0 = torch.cat([da0.double().abs().sum(0), (da0.double() * ((z0.double() - bn0.mean.double()) / torch.sqrt(bn0.var.double() + M.BN_EPS))).abs().sum(0)])
@@ -180,11 +188,20 @@ def test_stage_kernels_on_compact_rows_match_the_full_layout(hiplib, dev, gemm_f
     # ---- the same backward of layer 0 DECOMPOSED over the points (round 4): a plain input-gradient GEMM, the masked scatter that
     # reduces the BatchNorm backward itself, a pass over the points -- against the epilogue reduce + the sorted scatter with the
     # coefficient vector those sums give (the chain the model ran before)
-    da0p = M.dgrad_bn_half(z1h, coef1, True, w1T, da1h, half)
+    da0p = run("assembled_half", lambda: M.dgrad_bn_half(z1h, coef1, True, w1T, da1h, half))
     assert relerr(da0p, da0h) < 1e-6  # the same GEMM without the epilogue's reduce
     bn0v = (bn0.scale, bn0.shift, bn0.mean, bn0.var)
     dg_ref, db_ref = torch.zeros(c0, device=dev), torch.zeros(c0, device=dev)
     coef_ref = M.bn_backward_coef(rows, *bn0v, gamma0, sums0h, dg_ref, db_ref)
+
+    def reduce_with_tail():  # the same epilogue reduce with the coefficient vector from its tail (every workgroup takes a ticket)
+        dg, db = torch.zeros(c0, device=dev), torch.zeros(c0, device=dev)
+        da, coef = M.assembled_dgrad_bn_reduce(z1h, coef1, True, w1T, da1h, half.geo, P, wx, below0, below_tail=(rows, gamma0, dg, db), half=half)
+        return da, coef, dg, db
+    da0t_, coef_t, dg_t, db_t = run("assembled_half", reduce_with_tail)
+    assert torch.equal(da0t_, da0h)
+    for got, want in ((coef_t, coef_ref), (dg_t, dg_ref), (db_t, db_ref)):  # as test_coefficient_tails_equal_the_separate_launch
+        assert float((got - want).abs().max()) <= 1e-5 * float(want.abs().max()) + 1e-12
     dwx_ref = torch.zeros(3, c0, device=dev)
     S_ref = M.group_linear_backward_half(half, b, n, P, wx, da0h, coef_ref, True, dwx_ref)
     for tails in (True, False):  # the coefficient vector from the kernel's tail / from the separate launch
@@ -200,6 +217,7 @@ def test_stage_kernels_on_compact_rows_match_the_full_layout(hiplib, dev, gemm_f
         assert relerr(dg, dg_ref) < 2e-5 and relerr(db, db_ref) < 2e-5
         assert relerr(S_dec, S_ref) < 2e-5 and relerr(dwx_dec, dwx_ref) < 1e-4
     img.close()
+    return half.rows
 
 
 def test_model_with_and_without_the_half_group_layout(hiplib, dev):
@@ -250,12 +268,20 @@ def test_model_with_and_without_the_half_group_layout(hiplib, dev):
 
 @pytest.mark.parametrize("b,n,m,c,radius,b0_shift", [(2, 700, 64, 3, 0.5, 0.0), (1, 500, 48, 0, 0.45, 0.0), (2, 700, 64, 3, 0.5, 40.0)])
 def test_narrow_stage_kernels_on_compact_rows_match_the_full_layout(hiplib, dev, gemm_form, b, n, m, c, radius, b0_shift):
-    """sa1's form (csrc/narrow.hip: z0 rebuilt from eight floats per row) on the compact rows.  b0_shift = 40: a first-layer bias that
+    narrow_stage_kernels_on_compact_rows(dev, gemm_form, b, n, m, c, radius, b0_shift)
+
+
+def narrow_stage_kernels_on_compact_rows(dev, gemm_form, b, n, m, c, radius, b0_shift, run=None):
+    """The body of the test above.  run(tag, fn) -> fn(): how the fused GEMMs of the piece layout are launched (tests/test_gpu_tile_walk.py
+    launches them under its workgroup caps and hands back the walked launch's results); -> the compact rows.
+
+    sa1's form (csrc/narrow.hip: z0 rebuilt from eight floats per row) on the compact rows.  b0_shift = 40: a first-layer bias that
     puts |mean| / std of z0 at ~50 (the masked input-gradient tail derives sum g zhat as a DIFFERENCE of two sums of that
     size, (sum_d W0 UG + b0 s1) - mean s1; it does so in double on double totals, so the bias cancels to the last bit of its fp32
     value and what remains is the accuracy of the fp32 per-lane partials of UG and s1 -- the same as the round-3 epilogue's)."""
     from votenet_amd import mlp as M
     from votenet_amd import tf_grouping, tf_sampling
+    run = run or (lambda tag, fn: fn())
     k, c0, c1 = 64, 64, 64
     g = torch.Generator().manual_seed(11 * n + c)
     rnd = lambda *s: torch.randn(*s, generator=g).to(dev)
@@ -279,7 +305,7 @@ def test_narrow_stage_kernels_on_compact_rows_match_the_full_layout(hiplib, dev,
     bn0 = M.PendingBN(st0, rnd(c0) * 0.2 + 1.0, rnd(c0) * 0.1, rows)
     bn0.finalize()
     z1, st1 = M.narrow_linear(u8, w0, b0, w1, None, bn0)
-    z1h, st1h = M.narrow_linear(half.u8, w0, b0, w1, None, bn0, half=half)
+    z1h, st1h = run("narrow", lambda: M.narrow_linear(half.u8, w0, b0, w1, None, bn0, half=half))
     assert torch.equal(z1h, z1[full]) and relerr(st1h[:c1], st1[:c1]) < 1e-6 and relerr(st1h[c1:], st1[c1:]) < 1e-6
     da1 = rnd(rows, c1)
     da1h = _totals(da1, half, dev).float()
@@ -293,7 +319,7 @@ def test_narrow_stage_kernels_on_compact_rows_match_the_full_layout(hiplib, dev,
     assert relerr(dw1h, dw1) < 1e-5
     below0 = (bn0.scale, bn0.shift, bn0.mean, bn0.var, True)
     sums, ug = M.narrow_dgrad_bn_reduce(z1, coef1, True, w1T, da1, u8, w0, b0, below0)
-    sums_h, ug_h = M.narrow_dgrad_bn_reduce(z1h, coef1, True, w1T, da1h, half.u8, w0, b0, below0, half=half)
+    sums_h, ug_h = run("narrow_dgrad", lambda: M.narrow_dgrad_bn_reduce(z1h, coef1, True, w1T, da1h, half.u8, w0, b0, below0, half=half))
     # scale of the sums: the absolute sums of their terms
     dz1 = coef1[:c1] * da1 * (z1 * bn1.scale + bn1.shift > 0) + coef1[c1:2 * c1] + coef1[2 * c1:3 * c1] * z1
     da0 = dz1.double() @ w1T.double()
@@ -305,7 +331,7 @@ def test_narrow_stage_kernels_on_compact_rows_match_the_full_layout(hiplib, dev,
     assert float(((ug_h - ug).abs() / (uscale + 1e-30)).max()) < 1e-5
     # ---- round 4: the first layer's ReLU mask recorded by the forward GEMM and read by the input-gradient epilogue (EPI 7) instead of a
     # rebuild of z0 per accumulator element; the second BatchNorm-backward sum derived in the coefficient tail from ug and the first
-    z1m, st1m, mask = M.narrow_linear(half.u8, w0, b0, w1, None, bn0, half=half, want_mask=True)
+    z1m, st1m, mask = run("narrow", lambda: M.narrow_linear(half.u8, w0, b0, w1, None, bn0, half=half, want_mask=True))
     assert torch.equal(z1m, z1h) and torch.equal(st1m, st1h)
     z0h = M.narrow_z0(half.u8, w0, b0)
     act = (torch.clamp_min(z0h * bn0.scale + bn0.shift, 0.0) > 0)  # the loader's own test: relu(bn0(z0)) > 0
@@ -313,10 +339,13 @@ def test_narrow_stage_kernels_on_compact_rows_match_the_full_layout(hiplib, dev,
     want = (act.view(half.rows, c0 // 16, 16).long() << bits).sum(-1)
     assert torch.equal(mask.long() & 0xffff, want)
     gamma0 = rnd(c0) * 0.2 + 1.0
-    ref_dg, ref_db = torch.zeros(c0, device=dev), torch.zeros(c0, device=dev)
-    coef_ref, ug_ref = M.narrow_dgrad_bn_reduce(z1h, coef1, True, w1T, da1h, half.u8, w0, b0, below0, tail=(rows, gamma0, ref_dg, ref_db), half=half)
-    dg, db = torch.zeros(c0, device=dev), torch.zeros(c0, device=dev)
-    coef_m, ug_m = M.narrow_dgrad_bn_reduce(z1h, coef1, True, w1T, da1h, half.u8, w0, b0, below0, tail=(rows, gamma0, dg, db), half=half, mask=mask)
+
+    def reduce_with_tail(mask):  # (fresh dgamma / dbeta per launch: the tail accumulates into them)
+        dg, db = torch.zeros(c0, device=dev), torch.zeros(c0, device=dev)
+        coef, ug = M.narrow_dgrad_bn_reduce(z1h, coef1, True, w1T, da1h, half.u8, w0, b0, below0, tail=(rows, gamma0, dg, db), half=half, mask=mask)
+        return coef, ug, dg, db
+    coef_ref, ug_ref, ref_dg, ref_db = run("narrow_dgrad", lambda: reduce_with_tail(None))
+    coef_m, ug_m, dg, db = run("narrow_dgrad", lambda: reduce_with_tail(mask))
     assert float(((ug_m - ug_ref).abs() / (uscale + 1e-30)).max()) < 1e-5
     assert torch.equal(coef_m[3 * c0:], coef_ref[3 * c0:])
     # A, B, C follow from the sums: hold them to the sums' own scale (B, C divide differences of large sums)
@@ -324,6 +353,7 @@ def test_narrow_stage_kernels_on_compact_rows_match_the_full_layout(hiplib, dev,
         assert relerr(coef_m[q * c0:(q + 1) * c0], coef_ref[q * c0:(q + 1) * c0]) < 1e-4, q
     assert relerr(dg, ref_dg) < 1e-4 and relerr(db, ref_db) < 1e-4
     img.close()
+    return half.rows
 
 
 @pytest.mark.parametrize("radius", [0.1, 0.25, 0.6])

@@ -32,7 +32,14 @@ def setup(dev, b, n, m, k, c, c0, c1, seed):
 @pytest.mark.parametrize("b,n,m,k,c,c0,c1", [(2, 500, 64, 64, 3, 64, 64), (1, 300, 32, 64, 1, 128, 128), (2, 256, 16, 64, 0, 64, 128),
                                              (1, 400, 8, 16, 5, 64, 64)])
 def test_narrow_first_layer_matches_the_materialised_layer(hiplib, dev, gemm_form, b, n, m, k, c, c0, c1):
+    narrow_first_layer(dev, gemm_form, b, n, m, k, c, c0, c1)
+
+
+def narrow_first_layer(dev, gemm_form, b, n, m, k, c, c0, c1, run=None):
+    """The body of the test above.  run(tag, fn) -> fn(): how the two fused GEMMs are launched (tests/test_gpu_tile_walk.py launches them
+    under its workgroup caps and hands back the walked launch's results); -> the rows of the GEMMs."""
     from votenet_amd import mlp as M
+    run = run or (lambda tag, fn: fn())
     xyz, new_xyz, feat, idx, w0, b0, w1, rows_in, rnd = setup(dev, b, n, m, k, c, c0, c1, 7 * n + c)
     wT = w1.t().contiguous()
     # images for the second layer's forward GEMM (fp16 x 2 when gemm_form == 2, as the model registers its forward matrices) and its
@@ -55,7 +62,7 @@ def test_narrow_first_layer_matches_the_materialised_layer(hiplib, dev, gemm_for
     gamma0, beta0 = rnd(c0) * 0.2 + 1.0, rnd(c0) * 0.1
     bn0 = M.PendingBN(st, gamma0, beta0, rows)
     # second layer forward: z1 and its statistics
-    z1, st1 = M.narrow_linear(u8, w0, b0, w1, None, bn0)
+    z1, st1 = run("narrow", lambda: M.narrow_linear(u8, w0, b0, w1, None, bn0))
     mu, var = z0.mean(0), z0.var(0, unbiased=False)
     assert relerr(bn0.mean, mu) < 1e-6 and relerr(bn0.var, var) < 1e-5
     a0 = torch.relu(gamma0.double() * (z0 - mu) / torch.sqrt(var + M.BN_EPS) + beta0.double())
@@ -73,7 +80,7 @@ def test_narrow_first_layer_matches_the_materialised_layer(hiplib, dev, gemm_for
     M.narrow_wgrad_bn(u8, w0, b0, bn0.scale, bn0.shift, True, z1, coef1, True, da1, dw1)
     a0f = torch.relu((u8[:, :k0].double() @ w0.double() + b0.double()) * bn0.scale.double() + bn0.shift.double())
     assert relerr(dw1, a0f.t() @ dz1) < 2e-5
-    sums, ug = M.narrow_dgrad_bn_reduce(z1, coef1, True, wT, da1, u8, w0, b0, (bn0.scale, bn0.shift, bn0.mean, bn0.var, True))
+    sums, ug = run("narrow_dgrad", lambda: M.narrow_dgrad_bn_reduce(z1, coef1, True, wT, da1, u8, w0, b0, (bn0.scale, bn0.shift, bn0.mean, bn0.var, True)))
     da0 = dz1 @ w1.double().t()
     act = (z0 * bn0.scale.double() + bn0.shift.double()) > 0
     # entries whose pre-activation is within fp32 rounding of zero may take either side: they carry |da0| each, far below the bound
@@ -92,6 +99,7 @@ def test_narrow_first_layer_matches_the_materialised_layer(hiplib, dev, gemm_for
     assert relerr(dw0, ud[:, :k0].t() @ dz0) < 2e-5
     img.close()
     img_f.close()
+    return rows
 
 
 def test_narrow_kernels_reject_unserved_shapes(hiplib, dev):

@@ -606,7 +606,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((EPI == 3 |
     for (int d = 0; d < (NEPI ? 8 : 1); d++)
 #pragma unroll
         for (int j = 0; j < NT; j++) ugs[d][j] = 0.0f;
-    if (my_tiles == 0) { // never with the launchers below (gridDim.x <= row tiles); a workgroup without work still takes its ticket
+    // A workgroup without a tile.  The launchers keep gridDim.x <= rows / 128, and still this is reached: under xcd_chunk an XCD's chunk is
+    // ceil(ntiles / 8) tiles, so the last chunks run short or empty (513 tiles on 512 workgroups; 9 tiles on 8: three workgroups get
+    // nothing), and under nh_dev the grid is sized from the caller's upper bound.  Such a workgroup still takes its ticket: the tail
+    // counts gridDim workgroups.  (EPI 7 is never launched chunked or with nh_dev; its own tail further down is not the one taken here.)
+    if (my_tiles == 0) {
         if (REDUCE_BELOW) coef_tail(A.tail, gridDim.x * gridDim.y * (SK ? gridDim.z : 1u), cout, A.stats, A.e_scale, A.e_shift, A.e_mean, A.e_var, A.e_eps);
         return;
     }
