@@ -221,7 +221,7 @@ def test_header_declares_the_entries_and_the_binding_follows_it():
     for name, table in (("VOTENET_AABB_3D", aabb_nms._MODE["aabb3d"]), ("VOTENET_AABB_BEV", aabb_nms._MODE["bev"]),
                         ("VOTENET_AABB_IOU", aabb_nms._MEASURE["iou"]), ("VOTENET_AABB_OVER_LATER", aabb_nms._MEASURE["over_later"])):
         assert "#define %s %d\n" % (name, table) in text
-    lib = L.aabb_lib()
+    lib = L.side_lib("aabb")
     for name in NAMES:
         fn = getattr(lib, name)
         assert (fn.restype, list(fn.argtypes or [])) == (protos[name][0], protos[name][1])
@@ -230,11 +230,11 @@ def test_header_declares_the_entries_and_the_binding_follows_it():
 
 def test_library_exports_exactly_its_header_and_checks_its_arguments(hiplib):
     """Every invalid-argument case returns before anything is launched, with the limit in the text: no device is needed."""
-    lib = L.aabb_lib()
+    lib = L.side_lib("aabb")
     defined = lambda path: [line.split()[-1] for line in subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True,
                                                                         check=True).stdout.splitlines()]
-    assert sorted(defined(L._AABB_PATH)) == NAMES
-    for other in (L.lib_path(), L._DETECT_PATH, L._BOXPTS_PATH):  # the other libraries export what they did
+    assert sorted(defined(L.side_path("aabb"))) == NAMES
+    for other in (L.lib_path(), L.side_path("detect"), L.side_path("boxpts")):  # the other libraries export what they did
         assert not set(NAMES) & set(defined(other))
     buf = np.zeros(4096, F)
     p = buf.ctypes.data
@@ -252,13 +252,13 @@ def test_library_exports_exactly_its_header_and_checks_its_arguments(hiplib):
         assert nms(**kw) == 1, kw
         assert text in err(), (kw, err())
     need = lib.votenet_class_nms_aabb_workspace_bytes(2, 16, 10)
-    assert need == L.detect_lib().votenet_class_nms3d_workspace_bytes(2, 16, 10) and lib.votenet_class_nms_aabb_workspace_bytes(0, 0, 1) > 0
+    assert need == L.side_lib("detect").votenet_class_nms3d_workspace_bytes(2, 16, 10) and lib.votenet_class_nms_aabb_workspace_bytes(0, 0, 1) > 0
     assert nms(wsb=need - 1) == 3 and "workspace of %d bytes required" % need in err()
     assert nms(ws=None) == 3 and "workspace of %d bytes required" % need in err()
     with pytest.raises(L.VotenetError, match="workspace of %d bytes" % need):
-        L.check_aabb(nms(wsb=0))
+        L.check(nms(wsb=0), side="aabb")
     with pytest.raises(L.InvalidArgumentError, match="at most 512 boxes per scene, got n = 513"):
-        L.check_aabb(nms(n=513))
+        L.check(nms(n=513), side="aabb")
 
     def matrix(b=2, n=16, mode=0, meas=0, boxes=p, out=p):
         return lib.votenet_aabb_overlap_matrix(b, n, boxes, mode, meas, out, None)

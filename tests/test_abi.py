@@ -186,22 +186,25 @@ def test_build_force_is_a_clean_build(monkeypatch, tmp_path):
     from votenet_amd import _lib
     here = tmp_path / "votenet_amd"
     (here / "csrc" / "obj").mkdir(parents=True)
+    (here / "csrc" / "guard" / "obj").mkdir(parents=True)  # a side library's files go with the main library's
     (here / "lib").mkdir()
-    objs = [here / "csrc" / "obj" / n for n in ("fps.o", "mlp_fast.o")]
-    for f in objs + [here / "lib" / "libvotenet_hip.so"]:
+    objs = [here / "csrc" / "obj" / n for n in ("fps.o", "mlp_fast.o")] + [here / "csrc" / "guard" / "obj" / "step_guard.o"]
+    for f in objs + [here / "lib" / "libvotenet_hip.so", here / "lib" / "libvotenet_guard.so"]:
         f.write_bytes(b"stale")
     seen = {}
 
     def fake_run(cmd, **kw):
         seen["left"] = sorted(p.name for p in (here / "csrc" / "obj").iterdir()) + sorted(p.name for p in (here / "lib").iterdir())
+        seen["guard"] = sorted(p.name for p in (here / "csrc" / "guard" / "obj").iterdir()) + sorted(p.name for p in (here / "lib").glob("*guard*"))
         return subprocess.CompletedProcess(cmd, 0, "", "")
     monkeypatch.setattr(_lib, "_HERE", str(here))
     monkeypatch.setattr(_lib, "_LIB_PATH", str(here / "lib" / "libvotenet_hip.so"))
     monkeypatch.setattr(_lib.subprocess, "run", fake_run)
     _lib.build(force=False)
-    assert seen["left"] == ["fps.o", "mlp_fast.o", "libvotenet_hip.so"]   # an incremental build keeps its cache
+    assert seen["left"] == ["fps.o", "mlp_fast.o", "libvotenet_guard.so", "libvotenet_hip.so"]   # an incremental build keeps its cache
+    assert seen["guard"] == ["step_guard.o", "libvotenet_guard.so"]
     _lib.build(force=True)
-    assert seen["left"] == []
+    assert seen["left"] == [] and seen["guard"] == []
 
 
 def test_library_has_no_packed_f32_op_reading_the_high_register_of_src1(hiplib):
@@ -347,3 +350,61 @@ def test_header_reader_has_teeth():
     assert pair._fields_ == [("gamma", V), ("beta", V), ("b", I), ("n", I), ("m", I), ("ticket", V)]
     assert funcs == {"votenet_many": (I, [I, ctypes.POINTER(pair), ctypes.c_ulonglong, ctypes.c_uint, V, ctypes.c_size_t, V]),
                      "votenet_bytes": (ctypes.c_size_t, []), "votenet_set": (None, [I])}
+
+
+# ------------------------------------------------------------------ the side libraries (votenet_amd._lib.SIDE_LIBS), one rule for all
+def _side_names():
+    from votenet_amd import _lib
+    return sorted(_lib.SIDE_LIBS)
+
+
+@pytest.mark.parametrize("name", _side_names())
+def test_side_library_loads_and_exports_exactly_its_header_with_its_prototypes(hiplib, name):
+    """libvotenet_<name>.so loads, exports the functions its header declares and nothing else, each bound with the header's prototype."""
+    from votenet_amd import _lib
+    with open(os.path.join(ROOT, "include", _lib.SIDE_LIBS[name])) as f:
+        protos = _lib.parse_header(f.read(), {})
+    S = _lib.side_lib(name)
+    assert _lib.side_loaded(name) and os.path.basename(_lib.side_path(name)) == "libvotenet_%s.so" % name
+    out = subprocess.run(["nm", "-D", "--defined-only", _lib.side_path(name)], capture_output=True, text=True, check=True).stdout
+    rows = [line.split() for line in out.splitlines()]
+    assert all(r[1] == "T" for r in rows), rows
+    assert sorted(r[2] for r in rows) == sorted(protos) == declared_symbols((_lib.SIDE_LIBS[name],))
+    for fname, (restype, argtypes) in protos.items():
+        fn = getattr(S, fname)
+        assert (fn.restype, list(fn.argtypes or [])) == (restype, argtypes), fname
+    last_error, = [fname for fname in protos if fname.endswith("_last_error")]
+    assert getattr(S, last_error).restype is ctypes.c_char_p and getattr(S, last_error).argtypes == []
+
+
+@pytest.mark.parametrize("name", _side_names())
+def test_check_raises_with_the_side_library_s_name(hiplib, name):
+    from votenet_amd import _lib
+    with pytest.raises(_lib.InvalidArgumentError):
+        _lib.check(1, side=name)
+    with pytest.raises(_lib.VotenetError) as e:
+        _lib.check(2, side=name)
+    assert str(e.value).startswith("libvotenet_%s error 2" % name)
+    _lib.check(0, side=name)
+
+
+def test_error_texts_are_per_library(hiplib):
+    """A failure in one library leaves the text of every other one alone: three libraries fail in turn (status 1, nothing launched), and
+    each *_last_error() still returns its own text afterwards."""
+    from votenet_amd import _lib
+    A, D = _lib.side_lib("aabb"), _lib.side_lib("detect")
+    buf = np.zeros(4096, np.float32)
+    p = buf.ctypes.data
+    assert A.votenet_class_nms_aabb(2, 513, 10, p, p, p, 0.25, 0.0, 1, 1, 0, 0, p, 2 * 513 * 10, p, p, 1 << 20, None) == 1
+    assert D.votenet_class_nms3d(2, 513, 10, p, p, p, 0.25, 0.0, 1, 1, p, 2 * 513 * 10, p, p, 1 << 20, None) == 1
+    assert hiplib.votenet_farthest_point_sample(1, 10, 0, None, None, None, None) == 1
+    aabb, detect, main = A.votenet_aabb_last_error(), D.votenet_detections_last_error(), hiplib.votenet_last_error()
+    assert b"class_nms_aabb" in aabb and b"at most 512 boxes per scene, got n = 513" in aabb
+    assert b"class_nms3d" in detect and b"at most 512 boxes per scene, got n = 513" in detect and detect != aabb
+    assert b"positive npoint" in main and b"512 boxes" not in main
+    with pytest.raises(_lib.InvalidArgumentError, match="class_nms_aabb"):
+        _lib.check(1, side="aabb")
+    with pytest.raises(_lib.InvalidArgumentError, match="class_nms3d"):
+        _lib.check(1, side="detect")
+    with pytest.raises(_lib.InvalidArgumentError, match="positive npoint"):
+        _lib.check(1)

@@ -149,7 +149,7 @@ def test_header_declares_the_entries_and_the_binding_follows_it():
     assert protos["votenet_box_points_last_error"] == (ctypes.c_char_p, [])
     assert protos["votenet_box_point_counts"] == (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_long] + [ctypes.c_void_p] * 4)
     assert protos["votenet_gate_objectness"] == (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 3)
-    lib = L.boxpts_lib()
+    lib = L.side_lib("boxpts")
     for name in NAMES:
         fn = getattr(lib, name)
         assert (fn.restype, list(fn.argtypes or [])) == (protos[name][0], protos[name][1])
@@ -157,11 +157,11 @@ def test_header_declares_the_entries_and_the_binding_follows_it():
 
 def test_library_exports_exactly_its_header_and_checks_its_arguments(hiplib):
     """Every invalid-argument case returns 1 before anything is launched, with the limit in the text: no device is needed."""
-    lib = L.boxpts_lib()
+    lib = L.side_lib("boxpts")
     defined = lambda path: [line.split()[-1] for line in subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True,
                                                                         check=True).stdout.splitlines()]
-    assert sorted(defined(L._BOXPTS_PATH)) == NAMES
-    for other in (L.lib_path(), L._DETECT_PATH):  # the other libraries export what they did
+    assert sorted(defined(L.side_path("boxpts"))) == NAMES
+    for other in (L.lib_path(), L.side_path("detect")):  # the other libraries export what they did
         assert not set(NAMES) & set(defined(other))
     buf = np.zeros(4096, F)
     p = buf.ctypes.data
@@ -185,7 +185,7 @@ def test_library_exports_exactly_its_header_and_checks_its_arguments(hiplib):
         assert text in err(), (kw, err())
     assert gate(b=0) == 0
     with pytest.raises(L.InvalidArgumentError, match=r"1 to 1024 boxes per scene, got n = 1025"):
-        L.check_boxpts(count(n=1025))
+        L.check(count(n=1025), side="boxpts")
 
 
 def test_build_force_also_removes_the_boxpts_library_and_its_objects(monkeypatch, tmp_path):

@@ -218,8 +218,8 @@ def test_header_declares_the_entries_and_the_binding_follows_it():
 
 def test_library_exports_exactly_its_header_and_checks_its_arguments(hiplib):
     """Every invalid-argument case returns before anything is launched, with the limit in the text: no device is needed."""
-    lib = L.detect_lib()
-    out = subprocess.run(["nm", "-D", "--defined-only", L._DETECT_PATH], capture_output=True, text=True, check=True).stdout
+    lib = L.side_lib("detect")
+    out = subprocess.run(["nm", "-D", "--defined-only", L.side_path("detect")], capture_output=True, text=True, check=True).stdout
     assert sorted(line.split()[-1] for line in out.splitlines()) == NAMES
     main = subprocess.run(["nm", "-D", "--defined-only", L.lib_path()], capture_output=True, text=True, check=True).stdout
     assert not any(n in main for n in NAMES)  # the drop-in library's export list is what it was
@@ -241,9 +241,9 @@ def test_library_exports_exactly_its_header_and_checks_its_arguments(hiplib):
     assert nms(wsb=need - 1) == 3 and "workspace of %d bytes required" % need in err()
     assert nms(ws=None) == 3 and "workspace of %d bytes required" % need in err()
     with pytest.raises(L.VotenetError, match="workspace of %d bytes" % need):
-        L.check_detect(nms(wsb=0))
+        L.check(nms(wsb=0), side="detect")
     with pytest.raises(L.InvalidArgumentError, match="at most 512 boxes per scene, got n = 513"):
-        L.check_detect(nms(n=513))
+        L.check(nms(n=513), side="detect")
 
     thr2 = (ctypes.c_float * 2)(0.25, 0.5)
 

@@ -161,7 +161,7 @@ def test_adversarial_inputs_and_nothing_written_beyond_the_total(hiplib, dev):
     ties = [i for i in exp["kept"][1]]
     assert any(d[1, i] == d[1, j] and i < j for i, j in zip(ties, ties[1:]))  # equal margins in index order
     # the raw entry on a prefilled buffer
-    lib = L.aabb_lib()
+    lib = L.side_lib("aabb")
     bb, ob, cs = T(boxes, dev), T(obj, dev), T(cls, dev)
     for pc in (0, 1):
         cap = b * n * (nc if pc else 1)
@@ -169,8 +169,8 @@ def test_adversarial_inputs_and_nothing_written_beyond_the_total(hiplib, dev):
         off = torch.full((b + 2,), 0x5A5A5A5A, dtype=torch.int32, device=dev)
         need = lib.votenet_class_nms_aabb_workspace_bytes(b, n, nc)
         ws = torch.empty(need, dtype=torch.uint8, device=dev)
-        L.check_aabb(lib.votenet_class_nms_aabb(b, n, nc, L.ptr(bb), L.ptr(ob), L.ptr(cs), thr, float(D.conf_logit(0.05)), 1, pc, 0, 0,
-                                                L.ptr(rows), cap, L.ptr(off), L.ptr(ws), need, L.stream_ptr()))
+        L.check(lib.votenet_class_nms_aabb(b, n, nc, L.ptr(bb), L.ptr(ob), L.ptr(cs), thr, float(D.conf_logit(0.05)), 1, pc, 0, 0,
+                                           L.ptr(rows), cap, L.ptr(off), L.ptr(ws), need, L.stream_ptr()), side="aabb")
         want = out["aabb3d", "iou", True, bool(pc)]
         total = int(want["det_offset"][-1])
         assert 0 < total < cap and off.cpu().tolist() == want["det_offset"].tolist() + [0x5A5A5A5A]
@@ -301,7 +301,7 @@ for kw in (dict(), dict(protocol="per_class"), dict(protocol="per_class", nms_ov
 torch.cuda.synchronize()
 maps = open("/proc/self/maps").read()
 assert "libvotenet_hip.so" in maps and "libvotenet_detect.so" in maps
-assert _lib._aabb is None and "libvotenet_aabb" not in maps
+assert not _lib.side_loaded("aabb") and "libvotenet_aabb" not in maps
 pred = net.predict(x, batch_statistics=True, protocol="per_class", nms_overlap="aabb3d")
 assert "det_rows" in pred and "libvotenet_aabb" in open("/proc/self/maps").read()
 print("fresh ok")

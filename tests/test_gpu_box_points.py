@@ -120,15 +120,15 @@ def test_two_calls_write_the_same_bytes_and_overwrite_garbage(hiplib, dev):
     from votenet_amd import _lib as L
     boxes, pts = draw(8, 256, 2048, 5)
     bb, pp = T(boxes, dev), T(pts, dev)
-    lib = L.boxpts_lib()
+    lib = L.side_lib("boxpts")
     outs = []
     for fill in (GARBAGE, -1):
         counts = torch.full((8, 256), fill, dtype=torch.int32, device=dev)
-        L.check_boxpts(lib.votenet_box_point_counts(8, 256, 2048, L.ptr(bb), L.ptr(pp), L.ptr(counts), L.stream_ptr()))
+        L.check(lib.votenet_box_point_counts(8, 256, 2048, L.ptr(bb), L.ptr(pp), L.ptr(counts), L.stream_ptr()), side="boxpts")
         outs.append(counts)
     assert torch.equal(outs[0], outs[1]) and np.array_equal(outs[0].cpu().numpy(), R.counts(boxes, pts))
     counts = torch.full((8, 256), GARBAGE, dtype=torch.int32, device=dev)  # no points: zeros, written in full
-    L.check_boxpts(lib.votenet_box_point_counts(8, 256, 0, L.ptr(bb), None, L.ptr(counts), L.stream_ptr()))
+    L.check(lib.votenet_box_point_counts(8, 256, 0, L.ptr(bb), None, L.ptr(counts), L.stream_ptr()), side="boxpts")
     assert not counts.any()
 
 
@@ -346,7 +346,7 @@ for kw in (dict(), dict(protocol="per_class")):
 torch.cuda.synchronize()
 maps = open("/proc/self/maps").read()
 assert "libvotenet_hip.so" in maps and "libvotenet_detect.so" in maps
-assert _lib._boxpts is None and "libvotenet_boxpts" not in maps and "votenet_amd.box_points" not in sys.modules
+assert not _lib.side_loaded("boxpts") and "libvotenet_boxpts" not in maps and "votenet_amd.box_points" not in sys.modules
 pred = net.predict(x, batch_statistics=True, min_points=5)
 assert "point_counts" in pred and "libvotenet_boxpts" in open("/proc/self/maps").read()
 print("fresh ok")

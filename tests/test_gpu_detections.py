@@ -173,7 +173,7 @@ def test_invalid_arguments_raise_with_the_limit_and_launch_nothing(hiplib, dev):
             D.class_nms3d(z(1, 16, 8, 3), z(1, 16, 2), z(1, 16, NC), thr)
     with pytest.raises(InvalidArgumentError, match=r"conf_thresh must be in \[0, 1\)"):
         D.class_nms3d(z(1, 16, 8, 3), z(1, 16, 2), z(1, 16, NC), 0.25, 1.0)
-    lib = L.detect_lib()
+    lib = L.side_lib("detect")
     need = lib.votenet_class_nms3d_workspace_bytes(2, 16, NC)
     rows = torch.full((2 * 16 * NC, 4), 0x5A5A5A5A, dtype=torch.int32, device=dev)
     off = torch.full((3,), 0x5A5A5A5A, dtype=torch.int32, device=dev)
@@ -182,11 +182,11 @@ def test_invalid_arguments_raise_with_the_limit_and_launch_nothing(hiplib, dev):
     call = lambda n, nc, thr, wsb: lib.votenet_class_nms3d(2, n, nc, L.ptr(bb), L.ptr(ob), L.ptr(cs), thr, 0.0, 1, 1, L.ptr(rows), 2 * 16 * NC,
                                                            L.ptr(off), L.ptr(ws), wsb, L.stream_ptr())
     with pytest.raises(VotenetError, match="workspace of %d bytes required" % need):
-        L.check_detect(call(16, NC, 0.25, need - 1))
+        L.check(call(16, NC, 0.25, need - 1), side="detect")
     assert call(513, NC, 0.25, need) == 1 and call(16, 65, 0.25, need) == 1 and call(16, NC, 1.5, need) == 1
     torch.cuda.synchronize()
     assert bool((off == 0x5A5A5A5A).all()) and bool((rows == 0x5A5A5A5A).all())  # nothing ran
-    L.check_detect(call(16, NC, 0.25, need))  # ... and the same call with its workspace does
+    L.check(call(16, NC, 0.25, need), side="detect")  # ... and the same call with its workspace does
     assert off.cpu().tolist() == [0, 16 * NC, 32 * NC]  # boxes without volume: nothing removes anything
 
 

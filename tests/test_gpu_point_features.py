@@ -219,7 +219,7 @@ def test_invalid_arguments(hiplib, dev):
     with pytest.raises(L.InvalidArgumentError):
         IP.subsample_augment_features(raw, off, 10, order_stats=torch.zeros(3, 3, device=dev))
     # the C entry's own checks (the wrapper's come first): straight through the binding
-    F = L.features_lib()
+    F = L.side_lib("features")
     out, feats, floor = torch.empty(3, 10, 3, device=dev), torch.empty(3, 10, 4, device=dev), torch.empty(3, device=dev)
 
     def call(want_height=1, extra=3, stride=6, o=out, f=feats, fl=floor):
@@ -228,7 +228,7 @@ def test_invalid_arguments(hiplib, dev):
     for kw in (dict(want_height=0, extra=0), dict(extra=5), dict(want_height=2), dict(stride=5), dict(f=None), dict(fl=None), dict(o=None)):
         assert call(**kw) == 1, kw
         with pytest.raises(L.InvalidArgumentError, match="subsample_augment_features"):
-            L.check_features(1)
+            L.check(1, side="features")
     assert call() == 0 and call(want_height=0, fl=None) == 0
     torch.cuda.synchronize()
 

@@ -27,7 +27,7 @@ def _declared(header):
 def monlib(hiplib):
     """libvotenet_monitors.so, built by the same build as the main library."""
     from votenet_amd import _lib
-    return _lib.monitors_lib()
+    return _lib.side_lib("monitors")
 
 
 def test_header_declares_the_new_entries_and_the_library_exports_them_and_nothing_else(monlib):
@@ -35,7 +35,7 @@ def test_header_declares_the_new_entries_and_the_library_exports_them_and_nothin
     library exports what its own two headers declare -- nothing new came with the summaries."""
     from votenet_amd import _lib
     assert _declared("votenet_monitors.h") == NEW
-    out = subprocess.run(["nm", "-D", "--defined-only", _lib._MON_PATH], capture_output=True, text=True, check=True).stdout
+    out = subprocess.run(["nm", "-D", "--defined-only", _lib.side_path("monitors")], capture_output=True, text=True, check=True).stdout
     rows = [line.split() for line in out.splitlines()]
     assert all(r[1] in "Tt" for r in rows), rows
     assert {r[2] for r in rows} == set(NEW)
@@ -63,10 +63,10 @@ def test_existing_loss_entries_keep_their_signatures(hiplib):
 
 def test_a_missing_monitors_library_is_an_error(monkeypatch, tmp_path):
     from votenet_amd import _lib
-    monkeypatch.setattr(_lib, "_mon", None)
-    monkeypatch.setattr(_lib, "_MON_PATH", str(tmp_path / "libvotenet_monitors.so"))
+    monkeypatch.delitem(_lib._side, "monitors", raising=False)
+    monkeypatch.setattr(_lib, "_LIB_PATH", str(tmp_path / "libvotenet_hip.so"))  # the side libraries lie beside the main one
     with pytest.raises(_lib.VotenetError, match="no CPU fallback"):
-        _lib.monitors_lib()
+        _lib.side_lib("monitors")
 
 
 def test_argument_validation_without_a_device(monlib):

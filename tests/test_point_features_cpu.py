@@ -67,11 +67,11 @@ def test_header_declares_the_entry_and_the_binding_follows_it():
 def test_library_exports_exactly_its_header_and_binds_it(hiplib):
     import ctypes
     import subprocess
-    F = L.features_lib()
+    F = L.side_lib("features")
     fn = F.votenet_subsample_augment_features
     assert fn.restype is ctypes.c_int and len(fn.argtypes) == 21
     assert F.votenet_point_features_last_error.restype is ctypes.c_char_p
-    out = subprocess.run(["nm", "-D", "--defined-only", L._FEAT_PATH], capture_output=True, text=True, check=True).stdout
+    out = subprocess.run(["nm", "-D", "--defined-only", L.side_path("features")], capture_output=True, text=True, check=True).stdout
     assert sorted(line.split()[-1] for line in out.splitlines()) == ["votenet_point_features_last_error", "votenet_subsample_augment_features"]
     # the argument checks need no device: every invalid-argument case returns 1 with a message before anything is launched
     import numpy as np

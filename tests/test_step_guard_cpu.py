@@ -28,14 +28,14 @@ def _declared(header):
 def guardlib(hiplib):
     """libvotenet_guard.so, built by the same build as the main library."""
     from votenet_amd import _lib
-    return _lib.guard_lib()
+    return _lib.side_lib("guard")
 
 
 def test_header_declares_the_entries_and_the_library_exports_exactly_them(guardlib):
     """A library of its own: the drop-in library still exports what its two headers declare, votenet_clip_adam included and unchanged."""
     from votenet_amd import _lib
     assert _declared("votenet_step_guard.h") == NEW
-    out = subprocess.run(["nm", "-D", "--defined-only", _lib._GUARD_PATH], capture_output=True, text=True, check=True).stdout
+    out = subprocess.run(["nm", "-D", "--defined-only", _lib.side_path("guard")], capture_output=True, text=True, check=True).stdout
     rows = [line.split() for line in out.splitlines()]
     assert all(r[1] in "Tt" for r in rows), rows
     assert {r[2] for r in rows} == set(NEW)
@@ -203,7 +203,7 @@ def test_wrong_state_size_and_mismatched_averages_are_argument_errors(guardlib):
 
 def test_a_missing_guard_library_is_an_error(monkeypatch, tmp_path):
     from votenet_amd import _lib
-    monkeypatch.setattr(_lib, "_guard", None)
-    monkeypatch.setattr(_lib, "_GUARD_PATH", str(tmp_path / "libvotenet_guard.so"))
+    monkeypatch.delitem(_lib._side, "guard", raising=False)
+    monkeypatch.setattr(_lib, "_LIB_PATH", str(tmp_path / "libvotenet_hip.so"))  # the side libraries lie beside the main one
     with pytest.raises(_lib.VotenetError, match="no CPU fallback"):
-        _lib.guard_lib()
+        _lib.side_lib("guard")

@@ -13,19 +13,18 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_PATH = os.path.join(_HERE, "lib", "libvotenet_hip.so")
-_MON_PATH = os.path.join(_HERE, "lib", "libvotenet_monitors.so")  # the training summaries (include/votenet_monitors.h): a library of its own
-_GUARD_PATH = os.path.join(_HERE, "lib", "libvotenet_guard.so")  # the guarded optimizer step (include/votenet_step_guard.h): likewise
-_FEAT_PATH = os.path.join(_HERE, "lib", "libvotenet_features.so")  # the input step with point features (include/votenet_point_features.h): likewise
 _lib = None
-_mon = None
-_guard = None
-_feat = None
-_DETECT_PATH = os.path.join(_HERE, "lib", "libvotenet_detect.so")  # per-class detections (include/votenet_detections.h): likewise
-_detect = None
-_BOXPTS_PATH = os.path.join(_HERE, "lib", "libvotenet_boxpts.so")  # points inside predicted boxes (include/votenet_box_points.h): likewise
-_boxpts = None
-_AABB_PATH = os.path.join(_HERE, "lib", "libvotenet_aabb.so")  # axis-aligned NMS overlaps (include/votenet_aabb_nms.h): likewise
-_aabb = None
+# The side libraries: each feature that must stay out of the drop-in library's export list is libvotenet_<name>.so beside it, built
+# from csrc/<name>/ (csrc/build.sh has the same rows), with its own header and its own error text.  name -> header under include/.
+SIDE_LIBS = {
+    "monitors": "votenet_monitors.h",        # the training summaries
+    "guard": "votenet_step_guard.h",         # the guarded optimizer step
+    "features": "votenet_point_features.h",  # the input step with point features
+    "detect": "votenet_detections.h",        # class-wise 3D NMS, per-class detections and their matching
+    "boxpts": "votenet_box_points.h",        # points inside predicted boxes, the empty-box gate
+    "aabb": "votenet_aabb_nms.h",            # the axis-aligned overlaps of the paper's NMS
+}
+_side = {}  # name -> (the loaded library, its *_last_error function)
 
 
 class VotenetError(RuntimeError):
@@ -44,15 +43,8 @@ def build(force=False):
     """Compile libvotenet_hip.so for gfx950 with hipcc (cross-compiles without a GPU)."""
     if force:  # a clean build: the library AND every cached object file (build.sh recompiles what is missing)
         import glob
-        mon = os.path.join(os.path.dirname(_LIB_PATH), os.path.basename(_MON_PATH))
-        guard = os.path.join(os.path.dirname(_LIB_PATH), os.path.basename(_GUARD_PATH))
-        feat = os.path.join(os.path.dirname(_LIB_PATH), os.path.basename(_FEAT_PATH))
-        detect = os.path.join(os.path.dirname(_LIB_PATH), os.path.basename(_DETECT_PATH))
-        boxpts = os.path.join(os.path.dirname(_LIB_PATH), os.path.basename(_BOXPTS_PATH))
-        aabb = os.path.join(os.path.dirname(_LIB_PATH), os.path.basename(_AABB_PATH))
-        for f in [_LIB_PATH, mon, guard, feat, detect, boxpts, aabb] + [o for d in ("obj", os.path.join("monitors", "obj"), os.path.join("guard", "obj"), os.path.join("features", "obj"),
-                                                                               os.path.join("detect", "obj"), os.path.join("boxpts", "obj"), os.path.join("aabb", "obj"))
-                                            for o in glob.glob(os.path.join(_HERE, "csrc", d, "*.o"))]:
+        objs = [o for d in ["obj"] + [os.path.join(name, "obj") for name in SIDE_LIBS] for o in glob.glob(os.path.join(_HERE, "csrc", d, "*.o"))]
+        for f in [_LIB_PATH] + [side_path(name) for name in SIDE_LIBS] + objs:
             if os.path.exists(f):
                 os.remove(f)
     out = subprocess.run(["bash", os.path.join(_HERE, "csrc", "build.sh")], capture_output=True, text=True)
@@ -175,182 +167,46 @@ def lib():
     return _lib
 
 
-def monitors_lib():
-    """libvotenet_monitors.so, loaded when a summary is first asked for; every function of include/votenet_monitors.h gets its header's
-    prototype (parse_header, as for the main library).  No fallback: a missing library is an error."""
-    global _mon
-    if _mon is None:
-        if not os.path.exists(_MON_PATH):
-            raise VotenetError("libvotenet_monitors.so not found at %s -- run `python -c 'import __graft_entry__ as g; g.build()'` "
-                               "(there is no CPU fallback)" % _MON_PATH)
-        with open(os.path.join(_HERE, os.pardir, "include", "votenet_monitors.h")) as f:
+def side_path(name):
+    """Where libvotenet_<name>.so of SIDE_LIBS lies: beside the main library."""
+    return os.path.join(os.path.dirname(_LIB_PATH), "libvotenet_%s.so" % name)
+
+
+def side_loaded(name):
+    return name in _side
+
+
+def side_lib(name):
+    """libvotenet_<name>.so, loaded when something of it is first asked for; every function of its header gets the header's prototype
+    (parse_header, as for the main library).  No fallback: a missing library is an error."""
+    if name not in _side:
+        path = side_path(name)
+        if not os.path.exists(path):
+            raise VotenetError("libvotenet_%s.so not found at %s -- run `python -c 'import __graft_entry__ as g; g.build()'` "
+                               "(there is no CPU fallback)" % (name, path))
+        with open(os.path.join(_HERE, os.pardir, "include", SIDE_LIBS[name])) as f:
             protos = parse_header(f.read(), {})
-        M = ctypes.CDLL(_MON_PATH)
-        for name, (restype, argtypes) in protos.items():
-            fn = getattr(M, name)
+        S = ctypes.CDLL(path)
+        for fname, (restype, argtypes) in protos.items():
+            fn = getattr(S, fname)
             fn.restype, fn.argtypes = restype, argtypes
-        _mon = M
-    return _mon
+        last_error, = [getattr(S, fname) for fname in protos if fname.endswith("_last_error")]  # each library keeps its own text
+        _side[name] = (S, last_error)
+    return _side[name][0]
 
 
-def guard_lib():
-    """libvotenet_guard.so, loaded when a step guard is first asked for; every function of include/votenet_step_guard.h gets its
-    header's prototype (parse_header, as for the main library).  No fallback: a missing library is an error."""
-    global _guard
-    if _guard is None:
-        if not os.path.exists(_GUARD_PATH):
-            raise VotenetError("libvotenet_guard.so not found at %s -- run `python -c 'import __graft_entry__ as g; g.build()'` "
-                               "(there is no CPU fallback)" % _GUARD_PATH)
-        with open(os.path.join(_HERE, os.pardir, "include", "votenet_step_guard.h")) as f:
-            protos = parse_header(f.read(), {})
-        G = ctypes.CDLL(_GUARD_PATH)
-        for name, (restype, argtypes) in protos.items():
-            fn = getattr(G, name)
-            fn.restype, fn.argtypes = restype, argtypes
-        _guard = G
-    return _guard
-
-
-def features_lib():
-    """libvotenet_features.so, loaded when point features are first asked for; every function of include/votenet_point_features.h gets
-    its header's prototype (parse_header, as for the main library).  No fallback: a missing library is an error."""
-    global _feat
-    if _feat is None:
-        if not os.path.exists(_FEAT_PATH):
-            raise VotenetError("libvotenet_features.so not found at %s -- run `python -c 'import __graft_entry__ as g; g.build()'` "
-                               "(there is no CPU fallback)" % _FEAT_PATH)
-        with open(os.path.join(_HERE, os.pardir, "include", "votenet_point_features.h")) as f:
-            protos = parse_header(f.read(), {})
-        F = ctypes.CDLL(_FEAT_PATH)
-        for name, (restype, argtypes) in protos.items():
-            fn = getattr(F, name)
-            fn.restype, fn.argtypes = restype, argtypes
-        _feat = F
-    return _feat
-
-
-def detect_lib():
-    """libvotenet_detect.so, loaded when per-class detections are first asked for; every function of include/votenet_detections.h gets
-    its header's prototype (parse_header, as for the main library).  No fallback: a missing library is an error."""
-    global _detect
-    if _detect is None:
-        if not os.path.exists(_DETECT_PATH):
-            raise VotenetError("libvotenet_detect.so not found at %s -- run `python -c 'import __graft_entry__ as g; g.build()'` "
-                               "(there is no CPU fallback)" % _DETECT_PATH)
-        with open(os.path.join(_HERE, os.pardir, "include", "votenet_detections.h")) as f:
-            protos = parse_header(f.read(), {})
-        D = ctypes.CDLL(_DETECT_PATH)
-        for name, (restype, argtypes) in protos.items():
-            fn = getattr(D, name)
-            fn.restype, fn.argtypes = restype, argtypes
-        _detect = D
-    return _detect
-
-
-def boxpts_lib():
-    """libvotenet_boxpts.so, loaded when the points inside predicted boxes are first asked for; every function of
-    include/votenet_box_points.h gets its header's prototype (parse_header, as for the main library).  No fallback: a missing library
-    is an error."""
-    global _boxpts
-    if _boxpts is None:
-        if not os.path.exists(_BOXPTS_PATH):
-            raise VotenetError("libvotenet_boxpts.so not found at %s -- run `python -c 'import __graft_entry__ as g; g.build()'` "
-                               "(there is no CPU fallback)" % _BOXPTS_PATH)
-        with open(os.path.join(_HERE, os.pardir, "include", "votenet_box_points.h")) as f:
-            protos = parse_header(f.read(), {})
-        B = ctypes.CDLL(_BOXPTS_PATH)
-        for name, (restype, argtypes) in protos.items():
-            fn = getattr(B, name)
-            fn.restype, fn.argtypes = restype, argtypes
-        _boxpts = B
-    return _boxpts
-
-
-def aabb_lib():
-    """libvotenet_aabb.so, loaded when an axis-aligned NMS overlap is first asked for; every function of include/votenet_aabb_nms.h
-    gets its header's prototype (parse_header, as for the main library).  No fallback: a missing library is an error."""
-    global _aabb
-    if _aabb is None:
-        if not os.path.exists(_AABB_PATH):
-            raise VotenetError("libvotenet_aabb.so not found at %s -- run `python -c 'import __graft_entry__ as g; g.build()'` "
-                               "(there is no CPU fallback)" % _AABB_PATH)
-        with open(os.path.join(_HERE, os.pardir, "include", "votenet_aabb_nms.h")) as f:
-            protos = parse_header(f.read(), {})
-        A = ctypes.CDLL(_AABB_PATH)
-        for name, (restype, argtypes) in protos.items():
-            fn = getattr(A, name)
-            fn.restype, fn.argtypes = restype, argtypes
-        _aabb = A
-    return _aabb
-
-
-def check_aabb(rc):
-    """check() for a status libvotenet_aabb.so returned (it keeps its own error text)."""
+def check(rc, side=None):
+    """Raise what a status means, with the text of the library that returned it: the main library's, or side library `side`'s."""
     if rc == 0:
         return
-    msg = aabb_lib().votenet_aabb_last_error().decode()
+    if side is None:
+        msg, who = lib().votenet_last_error().decode(), "hip"
+    else:
+        side_lib(side)
+        msg, who = _side[side][1]().decode(), side
     if rc == 1:
         raise InvalidArgumentError(msg)
-    raise VotenetError("libvotenet_aabb error %d: %s" % (rc, msg))
-
-
-def check_boxpts(rc):
-    """check() for a status libvotenet_boxpts.so returned (it keeps its own error text)."""
-    if rc == 0:
-        return
-    msg = boxpts_lib().votenet_box_points_last_error().decode()
-    if rc == 1:
-        raise InvalidArgumentError(msg)
-    raise VotenetError("libvotenet_boxpts error %d: %s" % (rc, msg))
-
-
-def check_detect(rc):
-    """check() for a status libvotenet_detect.so returned (it keeps its own error text)."""
-    if rc == 0:
-        return
-    msg = detect_lib().votenet_detections_last_error().decode()
-    if rc == 1:
-        raise InvalidArgumentError(msg)
-    raise VotenetError("libvotenet_detect error %d: %s" % (rc, msg))
-
-
-def check_features(rc):
-    """check() for a status libvotenet_features.so returned (it keeps its own error text)."""
-    if rc == 0:
-        return
-    msg = features_lib().votenet_point_features_last_error().decode()
-    if rc == 1:
-        raise InvalidArgumentError(msg)
-    raise VotenetError("libvotenet_features error %d: %s" % (rc, msg))
-
-
-def check_guard(rc):
-    """check() for a status libvotenet_guard.so returned (it keeps its own error text)."""
-    if rc == 0:
-        return
-    msg = guard_lib().votenet_step_guard_last_error().decode()
-    if rc == 1:
-        raise InvalidArgumentError(msg)
-    raise VotenetError("libvotenet_guard error %d: %s" % (rc, msg))
-
-
-def check_monitors(rc):
-    """check() for a status libvotenet_monitors.so returned (it keeps its own error text)."""
-    if rc == 0:
-        return
-    msg = monitors_lib().votenet_monitors_last_error().decode()
-    if rc == 1:
-        raise InvalidArgumentError(msg)
-    raise VotenetError("libvotenet_monitors error %d: %s" % (rc, msg))
-
-
-def check(rc):
-    if rc == 0:
-        return
-    msg = lib().votenet_last_error().decode()
-    if rc == 1:
-        raise InvalidArgumentError(msg)
-    raise VotenetError("libvotenet_hip error %d: %s" % (rc, msg))
+    raise VotenetError("libvotenet_%s error %d: %s" % (who, rc, msg))
 
 
 # The host side of a train step is ~250 launches: the Python objects behind torch.cuda.current_stream() / torch.cuda.device(...)

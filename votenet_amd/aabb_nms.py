@@ -50,7 +50,7 @@ def overlap_matrix(bboxes, overlap="aabb3d", measure="iou"):
     b, n = bboxes.shape[:2]
     out = torch.empty((b, n, n), dtype=torch.float32, device=bboxes.device)
     with L.device_guard(bboxes.device):
-        L.check_aabb(L.aabb_lib().votenet_aabb_overlap_matrix(b, n, L.ptr(bboxes), mode, meas, L.ptr(out), L.stream_ptr()))
+        L.check(L.side_lib("aabb").votenet_aabb_overlap_matrix(b, n, L.ptr(bboxes), mode, meas, L.ptr(out), L.stream_ptr()), side="aabb")
     return out
 
 
@@ -71,14 +71,14 @@ def class_nms_aabb(bboxes, objectness, class_scores, iou_threshold=0.25, conf_th
         raise L.InvalidArgumentError("class_nms_aabb expects (batch_size, nbbox, num_class) class_scores shape.")
     nc = class_scores.shape[2]
     t = conf_logit(conf_thresh)
-    A = L.aabb_lib()
+    A = L.side_lib("aabb")
     cap = b * n * (nc if per_class else 1)
     rows = torch.empty((max(cap, 1), 4), dtype=torch.int32, device=bboxes.device)
     offset = torch.empty(b + 1, dtype=torch.int32, device=bboxes.device)
     wbytes = A.votenet_class_nms_aabb_workspace_bytes(b, n, nc)
     ws = torch.empty(wbytes, dtype=torch.uint8, device=bboxes.device)
     with L.device_guard(bboxes.device):
-        L.check_aabb(A.votenet_class_nms_aabb(b, n, nc, L.ptr(bboxes), L.ptr(objectness), L.ptr(class_scores), float(iou_threshold), t,
-                                              1 if class_nms else 0, 1 if per_class else 0, mode, meas, L.ptr(rows), cap, L.ptr(offset),
-                                              L.ptr(ws), wbytes, L.stream_ptr()))
+        L.check(A.votenet_class_nms_aabb(b, n, nc, L.ptr(bboxes), L.ptr(objectness), L.ptr(class_scores), float(iou_threshold), t,
+                                         1 if class_nms else 0, 1 if per_class else 0, mode, meas, L.ptr(rows), cap, L.ptr(offset),
+                                         L.ptr(ws), wbytes, L.stream_ptr()), side="aabb")
     return dict(det_rows=rows[:cap], det_offset=offset)

@@ -31,8 +31,8 @@ def box_point_counts(bboxes, points):
         raise L.InvalidArgumentError("box_point_counts: bboxes and points live on different devices")
     counts = torch.empty((b, n), dtype=torch.int32, device=bboxes.device)
     with L.device_guard(bboxes.device):
-        L.check_boxpts(L.boxpts_lib().votenet_box_point_counts(b, n, points.shape[1], L.ptr(bboxes), L.ptr(points), L.ptr(counts),
-                                                               L.stream_ptr()))
+        L.check(L.side_lib("boxpts").votenet_box_point_counts(b, n, points.shape[1], L.ptr(bboxes), L.ptr(points), L.ptr(counts),
+                                                               L.stream_ptr()), side="boxpts")
     return counts
 
 
@@ -52,6 +52,6 @@ def gate_objectness(objectness, counts, min_points=PAPER_MIN_POINTS):
         raise L.InvalidArgumentError("gate_objectness: min_points must be an integer, got %r" % (min_points,)) from None
     gated = torch.empty_like(objectness)
     with L.device_guard(objectness.device):
-        L.check_boxpts(L.boxpts_lib().votenet_gate_objectness(b, n, L.ptr(counts), min_points, L.ptr(objectness), L.ptr(gated),
-                                                              L.stream_ptr()))
+        L.check(L.side_lib("boxpts").votenet_gate_objectness(b, n, L.ptr(counts), min_points, L.ptr(objectness), L.ptr(gated),
+                                                              L.stream_ptr()), side="boxpts")
     return gated

@@ -10,6 +10,7 @@
 // bit for bit.
 #include "../common.h"
 #include "../detect/det_emit.h"
+#include "../error_text.h"
 
 #include <climits>
 #include <cstdint>
@@ -20,25 +21,8 @@
 namespace votenet {
 
 // ---- error plumbing of this library (thread-local text behind votenet_aabb_last_error()) ----
-static thread_local char g_aabb_err[512] = "";
-static int aabb_set_error(int code, const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_aabb_err, sizeof(g_aabb_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
-static int aabb_check_launch(const char *what)
-{
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return aabb_set_error(VOTENET_E_HIP, "%s: %s", what, hipGetErrorString(e));
-    return VOTENET_OK;
-}
-#define AABB_REQUIRE(cond, ...)                                                               \
-    do {                                                                                      \
-        if (!(cond)) return ::votenet::aabb_set_error(VOTENET_E_INVALID_ARGUMENT, __VA_ARGS__); \
-    } while (0)
+static thread_local ErrorText g_aabb_err;
+#define AABB_REQUIRE(cond, ...) VN_REQUIRE_IN(::votenet::g_aabb_err, cond, __VA_ARGS__)
 
 constexpr int AABB_MAX_B = 65535;     // scenes: a grid extent
 constexpr int AABB_MAX_MATRIX_N = 32768;
@@ -204,7 +188,7 @@ __global__ __launch_bounds__(DET_NMS_THREADS) void class_nms_aabb_kernel(int n, 
 
 using namespace votenet;
 
-extern "C" const char *votenet_aabb_last_error(void) { return g_aabb_err; }
+extern "C" const char *votenet_aabb_last_error(void) { return g_aabb_err.text; }
 
 extern "C" int votenet_aabb_overlap_matrix(int b, int n, const float *bboxes, int mode, int measure, float *out, void *stream)
 {
@@ -217,7 +201,7 @@ extern "C" int votenet_aabb_overlap_matrix(int b, int n, const float *bboxes, in
     AABB_REQUIRE(bboxes && out, "aabb_overlap_matrix: null buffer");
     hipLaunchKernelGGL(aabb_matrix_kernel, dim3((n + AABB_TILE - 1) / AABB_TILE, b), dim3(AABB_MATRIX_THREADS), 0, as_stream(stream), n,
                        bboxes, mode, measure, out);
-    return aabb_check_launch("aabb_overlap_matrix");
+    return g_aabb_err.check_launch("aabb_overlap_matrix");
 }
 
 extern "C" size_t votenet_class_nms_aabb_workspace_bytes(int b, int n, int nc)
@@ -249,18 +233,18 @@ extern "C" int votenet_class_nms_aabb(int b, int n, int nc, const float *bboxes,
     hipStream_t st = as_stream(stream);
     if (b == 0 || n == 0) {
         (void)hipMemsetAsync(det_offset, 0, ((size_t)b + 1) * sizeof(int), st);
-        return aabb_check_launch("class_nms_aabb");
+        return g_aabb_err.check_launch("class_nms_aabb");
     }
     AABB_REQUIRE(bboxes && objectness && class_scores && det_rows, "class_nms_aabb: null buffer");
     AABB_REQUIRE(((uintptr_t)det_rows & 15) == 0, "class_nms_aabb: det_rows must be 16-byte aligned");
     const size_t wbytes = votenet_class_nms_aabb_workspace_bytes(b, n, nc);
     if (workspace == nullptr || workspace_bytes < wbytes)
-        return aabb_set_error(VOTENET_E_WORKSPACE, "class_nms_aabb: workspace of %zu bytes required, got %zu", wbytes, workspace ? workspace_bytes : (size_t)0);
+        return g_aabb_err.set(VOTENET_E_WORKSPACE, "class_nms_aabb: workspace of %zu bytes required, got %zu", wbytes, workspace ? workspace_bytes : (size_t)0);
     int *kept = (int *)workspace;
     int *count = (int *)((char *)workspace + align256((size_t)b * n * sizeof(int)));
     hipLaunchKernelGGL(class_nms_aabb_kernel, dim3(b), dim3(DET_NMS_THREADS), 0, st, n, nc, bboxes, objectness, class_scores, iou_threshold,
                        conf_logit, class_nms, mode, measure, kept, count);
     hipLaunchKernelGGL(det_emit_kernel, dim3(b), dim3(256), 0, st, b, n, nc, objectness, class_scores, per_class, kept, count,
                        (uint4 *)det_rows, det_offset);
-    return aabb_check_launch("class_nms_aabb");
+    return g_aabb_err.check_launch("class_nms_aabb");
 }

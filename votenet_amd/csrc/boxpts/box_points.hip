@@ -6,6 +6,7 @@
 // The rule of the header is plain fp32 arithmetic in a fixed order (-ffp-contract=off, as everywhere in this project):
 // tests/box_points_ref.py restates it in numpy float32 and the counts are compared exactly.
 #include "../common.h"
+#include "../error_text.h"
 
 #include <cstdint>
 #pragma GCC visibility push(default)
@@ -15,24 +16,8 @@
 namespace votenet {
 
 // ---- error plumbing of this library (thread-local text behind votenet_box_points_last_error()) ----
-static thread_local char g_bp_err[512] = "";
-static int bp_set_error(int code, const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_bp_err, sizeof(g_bp_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
-static int bp_check(hipError_t e, const char *what)
-{
-    if (e != hipSuccess) return bp_set_error(VOTENET_E_HIP, "%s: %s", what, hipGetErrorString(e));
-    return VOTENET_OK;
-}
-#define BP_REQUIRE(cond, ...)                                                              \
-    do {                                                                                   \
-        if (!(cond)) return ::votenet::bp_set_error(VOTENET_E_INVALID_ARGUMENT, __VA_ARGS__); \
-    } while (0)
+static thread_local ErrorText g_bp_err;
+#define BP_REQUIRE(cond, ...) VN_REQUIRE_IN(::votenet::g_bp_err, cond, __VA_ARGS__)
 
 constexpr int BP_MAX_B = 65535;       // scenes: the grid's y extent
 constexpr int BP_MAX_N = 1024;
@@ -120,7 +105,7 @@ __global__ __launch_bounds__(256) void gate_objectness_kernel(int total, const i
 
 using namespace votenet;
 
-extern "C" const char *votenet_box_points_last_error(void) { return g_bp_err; }
+extern "C" const char *votenet_box_points_last_error(void) { return g_bp_err.text; }
 
 extern "C" int votenet_box_point_counts(int b, int n, long npts, const float *bboxes, const float *points, int *counts, void *stream)
 {
@@ -131,11 +116,11 @@ extern "C" int votenet_box_point_counts(int b, int n, long npts, const float *bb
     BP_REQUIRE(bboxes && counts, "box_point_counts: null boxes or counts");
     BP_REQUIRE(points || npts == 0, "box_point_counts: null points");
     hipStream_t st = as_stream(stream);
-    int rc = bp_check(hipMemsetAsync(counts, 0, (size_t)b * n * sizeof(int), st), "box_point_counts (memset)");
+    int rc = g_bp_err.check(hipMemsetAsync(counts, 0, (size_t)b * n * sizeof(int), st), "box_point_counts (memset)");
     if (rc != VOTENET_OK || npts == 0) return rc;
     const unsigned tiles = (unsigned)((npts + BP_TILE - 1) / BP_TILE); // < 2^15
     hipLaunchKernelGGL(box_point_counts_kernel, dim3(tiles, b), dim3(BP_THREADS), 0, st, n, npts, bboxes, points, counts);
-    return bp_check(hipGetLastError(), "box_point_counts");
+    return g_bp_err.check_launch("box_point_counts");
 }
 
 extern "C" int votenet_gate_objectness(int b, int n, const int *counts, int min_points, const float *objectness, float *gated,
@@ -153,5 +138,5 @@ extern "C" int votenet_gate_objectness(int b, int n, const int *counts, int min_
     const int total = b * n; // <= 65535 * 1024 < 2^31
     hipLaunchKernelGGL(gate_objectness_kernel, dim3((total + 255) / 256), dim3(256), 0, as_stream(stream), total, counts, min_points,
                        (const uint2 *)objectness, (uint2 *)gated);
-    return bp_check(hipGetLastError(), "gate_objectness");
+    return g_bp_err.check_launch("gate_objectness");
 }

@@ -13,7 +13,7 @@ for src in "$HERE"/*.hip; do
   obj="$HERE/obj/$(basename "${src%.hip}").o"
   # (this script carries the flags: an object older than it is stale too)
   if [ ! -f "$obj" ] || [ "$src" -nt "$obj" ] || [ "$HERE/common.h" -nt "$obj" ] || [ "$HERE/mlp_types.h" -nt "$obj" ] || [ "$HERE/iou3d.h" -nt "$obj" ] \
-     || [ "$HERE/nearest_box.h" -nt "$obj" ] || [ "$HERE/sumsq.h" -nt "$obj" ] || [ "$HERE/augment_points.h" -nt "$obj" ] \
+     || [ "$HERE/nearest_box.h" -nt "$obj" ] || [ "$HERE/sumsq.h" -nt "$obj" ] || [ "$HERE/augment_points.h" -nt "$obj" ] || [ "$HERE/error_text.h" -nt "$obj" ] \
      || [ "$HERE/../../include/votenet_hip.h" -nt "$obj" ] || [ "$HERE/../../include/votenet_hip_debug.h" -nt "$obj" ] \
      || [ "${BASH_SOURCE[0]}" -nt "$obj" ]; then
     extra=""
@@ -32,107 +32,44 @@ for p in "${pids[@]:-}"; do [ -n "$p" ] && wait "$p"; done
 # Link under a temporary name, run the ISA-hazard gate on THAT, and only then move it into place: a library that fails the gate never
 # becomes the one later imports load.  exports.map: only the votenet_* C ABI and the reference's eight launcher names are visible.
 TMP="$OUT/.libvotenet_hip.so.tmp.$$"
-trap 'rm -f "$TMP"' EXIT
+trap 'rm -f "$OUT"/.lib*.so.tmp.$$' EXIT # whatever temporary this run has made, the side libraries' below included
 $HIPCC --offload-arch=gfx950 -shared -fPIC -Wl,--version-script="$HERE/exports.map" "$HERE"/obj/*.o -o "$TMP"
 python3 "$HERE/../../tools/check_isa_hazards.py" "$TMP"
 mv -f "$TMP" "$OUT/libvotenet_hip.so"
 echo "built $OUT/libvotenet_hip.so"
-# libvotenet_monitors.so (include/votenet_monitors.h): the training summaries, a library of its own -- the drop-in library's export
-# list stays the reference's ops.  Same flags, same gate; -fno-slp-vectorize as loss.hip, whose assignment loop it shares.
-MOBJ="$HERE/monitors/obj/monitors.o"
-mkdir -p "$HERE/monitors/obj"
-if [ ! -f "$MOBJ" ] || [ "$HERE/monitors/monitors.hip" -nt "$MOBJ" ] || [ "$HERE/nearest_box.h" -nt "$MOBJ" ] \
-   || [ "$HERE/../../include/votenet_monitors.h" -nt "$MOBJ" ] || [ "${BASH_SOURCE[0]}" -nt "$MOBJ" ]; then
-  $HIPCC $FLAGS -fno-slp-vectorize -c "$HERE/monitors/monitors.hip" -o "$MOBJ"
-fi
-MTMP="$OUT/.libvotenet_monitors.so.tmp.$$"
-trap 'rm -f "$TMP" "$MTMP"' EXIT
-$HIPCC --offload-arch=gfx950 -shared -fPIC -Wl,--version-script="$HERE/monitors/exports.map" "$MOBJ" -o "$MTMP"
-python3 "$HERE/../../tools/check_isa_hazards.py" "$MTMP"
-mv -f "$MTMP" "$OUT/libvotenet_monitors.so"
-echo "built $OUT/libvotenet_monitors.so"
-# libvotenet_guard.so (include/votenet_step_guard.h): the guarded optimizer step, a library of its own for the same reason.  Same
-# flags, same gate; sumsq.h is the text of votenet_clip_adam's partial sums, so both libraries form the same bits.
-GOBJ="$HERE/guard/obj/step_guard.o"
-mkdir -p "$HERE/guard/obj"
-if [ ! -f "$GOBJ" ] || [ "$HERE/guard/step_guard.hip" -nt "$GOBJ" ] || [ "$HERE/sumsq.h" -nt "$GOBJ" ] \
-   || [ "$HERE/../../include/votenet_step_guard.h" -nt "$GOBJ" ] || [ "$HERE/../../include/votenet_hip.h" -nt "$GOBJ" ] \
-   || [ "${BASH_SOURCE[0]}" -nt "$GOBJ" ]; then
-  $HIPCC $FLAGS -fno-slp-vectorize -c "$HERE/guard/step_guard.hip" -o "$GOBJ"
-fi
-GTMP="$OUT/.libvotenet_guard.so.tmp.$$"
-trap 'rm -f "$TMP" "$MTMP" "$GTMP"' EXIT
-$HIPCC --offload-arch=gfx950 -shared -fPIC -Wl,--version-script="$HERE/guard/exports.map" "$GOBJ" -o "$GTMP"
-python3 "$HERE/../../tools/check_isa_hazards.py" "$GTMP"
-mv -f "$GTMP" "$OUT/libvotenet_guard.so"
-echo "built $OUT/libvotenet_guard.so"
-# libvotenet_features.so (include/votenet_point_features.h): the input step of a network with point features, a library of its own for
-# the same reason.  Same flags, same gate; augment_points.h is the text of votenet_subsample_augment's points, so both libraries write
-# the same bits.
-FOBJ="$HERE/features/obj/point_features.o"
-mkdir -p "$HERE/features/obj"
-if [ ! -f "$FOBJ" ] || [ "$HERE/features/point_features.hip" -nt "$FOBJ" ] || [ "$HERE/augment_points.h" -nt "$FOBJ" ] \
-   || [ "$HERE/common.h" -nt "$FOBJ" ] || [ "$HERE/../../include/votenet_point_features.h" -nt "$FOBJ" ] \
-   || [ "$HERE/../../include/votenet_hip.h" -nt "$FOBJ" ] || [ "$HERE/../../include/votenet_hip_debug.h" -nt "$FOBJ" ] \
-   || [ "${BASH_SOURCE[0]}" -nt "$FOBJ" ]; then
-  $HIPCC $FLAGS -c "$HERE/features/point_features.hip" -o "$FOBJ"
-fi
-FTMP="$OUT/.libvotenet_features.so.tmp.$$"
-trap 'rm -f "$TMP" "$MTMP" "$GTMP" "$FTMP"' EXIT
-$HIPCC --offload-arch=gfx950 -shared -fPIC -Wl,--version-script="$HERE/features/exports.map" "$FOBJ" -o "$FTMP"
-python3 "$HERE/../../tools/check_isa_hazards.py" "$FTMP"
-mv -f "$FTMP" "$OUT/libvotenet_features.so"
-echo "built $OUT/libvotenet_features.so"
-# libvotenet_detect.so (include/votenet_detections.h): class-wise 3D NMS, per-class detections and their matching, a library of its own
-# for the same reason.  Same flags, same gate; iou3d.h is the text of votenet_iou3d_matrix's overlaps, so both libraries decide on the
-# same bits.
-DOBJ="$HERE/detect/obj/detections.o"
-mkdir -p "$HERE/detect/obj"
-if [ ! -f "$DOBJ" ] || [ "$HERE/detect/detections.hip" -nt "$DOBJ" ] || [ "$HERE/iou3d.h" -nt "$DOBJ" ] \
-   || [ "$HERE/detect/det_emit.h" -nt "$DOBJ" ] \
-   || [ "$HERE/common.h" -nt "$DOBJ" ] || [ "$HERE/../../include/votenet_detections.h" -nt "$DOBJ" ] \
-   || [ "$HERE/../../include/votenet_hip.h" -nt "$DOBJ" ] || [ "$HERE/../../include/votenet_hip_debug.h" -nt "$DOBJ" ] \
-   || [ "${BASH_SOURCE[0]}" -nt "$DOBJ" ]; then
-  $HIPCC $FLAGS -c "$HERE/detect/detections.hip" -o "$DOBJ"
-fi
-DTMP="$OUT/.libvotenet_detect.so.tmp.$$"
-trap 'rm -f "$TMP" "$MTMP" "$GTMP" "$FTMP" "$DTMP"' EXIT
-$HIPCC --offload-arch=gfx950 -shared -fPIC -Wl,--version-script="$HERE/detect/exports.map" "$DOBJ" -o "$DTMP"
-python3 "$HERE/../../tools/check_isa_hazards.py" "$DTMP"
-mv -f "$DTMP" "$OUT/libvotenet_detect.so"
-echo "built $OUT/libvotenet_detect.so"
-# libvotenet_boxpts.so (include/votenet_box_points.h): the points inside each predicted box and the gate that keeps empty boxes out of
-# the NMS, a library of its own for the same reason.  Same flags (no floating-point contraction: tests/box_points_ref.py restates the
-# rule operation for operation), same gate; -fno-slp-vectorize as loss.hip: the point slots' dot products pack into the v_pk_*_f32 forms
-# the gate refuses.
-BOBJ="$HERE/boxpts/obj/box_points.o"
-mkdir -p "$HERE/boxpts/obj"
-if [ ! -f "$BOBJ" ] || [ "$HERE/boxpts/box_points.hip" -nt "$BOBJ" ] || [ "$HERE/common.h" -nt "$BOBJ" ] \
-   || [ "$HERE/../../include/votenet_box_points.h" -nt "$BOBJ" ] || [ "$HERE/../../include/votenet_hip.h" -nt "$BOBJ" ] \
-   || [ "$HERE/../../include/votenet_hip_debug.h" -nt "$BOBJ" ] || [ "${BASH_SOURCE[0]}" -nt "$BOBJ" ]; then
-  $HIPCC $FLAGS -fno-slp-vectorize -c "$HERE/boxpts/box_points.hip" -o "$BOBJ"
-fi
-BTMP="$OUT/.libvotenet_boxpts.so.tmp.$$"
-trap 'rm -f "$TMP" "$MTMP" "$GTMP" "$FTMP" "$DTMP" "$BTMP"' EXIT
-$HIPCC --offload-arch=gfx950 -shared -fPIC -Wl,--version-script="$HERE/boxpts/exports.map" "$BOBJ" -o "$BTMP"
-python3 "$HERE/../../tools/check_isa_hazards.py" "$BTMP"
-mv -f "$BTMP" "$OUT/libvotenet_boxpts.so"
-echo "built $OUT/libvotenet_boxpts.so"
-# libvotenet_aabb.so (include/votenet_aabb_nms.h): the axis-aligned overlaps of the paper's NMS and the class-wise NMS that decides on
-# them, a library of its own for the same reason.  Same flags (no floating-point contraction: tests/aabb_nms_ref.py restates the rules
-# operation for operation), same gate; -fno-slp-vectorize as box_points.hip: the three axes' products would pack into the v_pk_*_f32
-# forms the gate refuses.  detect/det_emit.h is the text of votenet_class_nms3d's rows, so both libraries write the same bytes.
-AOBJ="$HERE/aabb/obj/aabb_nms.o"
-mkdir -p "$HERE/aabb/obj"
-if [ ! -f "$AOBJ" ] || [ "$HERE/aabb/aabb_nms.hip" -nt "$AOBJ" ] || [ "$HERE/detect/det_emit.h" -nt "$AOBJ" ] \
-   || [ "$HERE/common.h" -nt "$AOBJ" ] || [ "$HERE/../../include/votenet_aabb_nms.h" -nt "$AOBJ" ] \
-   || [ "$HERE/../../include/votenet_hip.h" -nt "$AOBJ" ] || [ "$HERE/../../include/votenet_hip_debug.h" -nt "$AOBJ" ] \
-   || [ "${BASH_SOURCE[0]}" -nt "$AOBJ" ]; then
-  $HIPCC $FLAGS -fno-slp-vectorize -c "$HERE/aabb/aabb_nms.hip" -o "$AOBJ"
-fi
-ATMP="$OUT/.libvotenet_aabb.so.tmp.$$"
-trap 'rm -f "$TMP" "$MTMP" "$GTMP" "$FTMP" "$DTMP" "$BTMP" "$ATMP"' EXIT
-$HIPCC --offload-arch=gfx950 -shared -fPIC -Wl,--version-script="$HERE/aabb/exports.map" "$AOBJ" -o "$ATMP"
-python3 "$HERE/../../tools/check_isa_hazards.py" "$ATMP"
-mv -f "$ATMP" "$OUT/libvotenet_aabb.so"
-echo "built $OUT/libvotenet_aabb.so"
+# The side libraries: what must stay out of the drop-in library's export list (the reference's ops) ships as a library of its own, with
+# its own header under include/ and its own exports.map.  Same flags, same gate.  One row each: directory, source, library, extra flags.
+SIDE_LIBS=(
+  # the training summaries.  -fno-slp-vectorize as loss.hip, whose assignment loop (nearest_box.h) it shares
+  "monitors monitors.hip       monitors -fno-slp-vectorize"
+  # the guarded optimizer step.  sumsq.h is the text of votenet_clip_adam's partial sums, so both libraries form the same bits
+  "guard    step_guard.hip     guard    -fno-slp-vectorize"
+  # the input step of a network with point features.  augment_points.h is the text of votenet_subsample_augment's points
+  "features point_features.hip features"
+  # class-wise 3D NMS, per-class detections and their matching.  iou3d.h is the text of votenet_iou3d_matrix's overlaps
+  "detect   detections.hip     detect"
+  # the points inside each predicted box and the empty-box gate.  No contraction: tests/box_points_ref.py restates the rule operation
+  # for operation; -fno-slp-vectorize as loss.hip: the point slots' dot products pack into the v_pk_*_f32 forms the gate refuses
+  "boxpts   box_points.hip     boxpts   -fno-slp-vectorize"
+  # the axis-aligned overlaps of the paper's NMS (tests/aabb_nms_ref.py restates them).  -fno-slp-vectorize as box_points.hip: the three
+  # axes' products would pack likewise.  detect/det_emit.h is the text of votenet_class_nms3d's rows, so both libraries write the same bytes
+  "aabb     aabb_nms.hip       aabb     -fno-slp-vectorize"
+)
+# A side object is stale when its source, this script or ANY header of the project is newer: no list to keep by hand.
+side_lib() { # directory, source, library name, extra flags ...
+  local dir="$HERE/$1" src="$HERE/$1/$2" lib="libvotenet_$3.so" obj="$HERE/$1/obj/$(basename "${2%.hip}").o" tmp dep
+  shift 3
+  mkdir -p "$dir/obj"
+  for dep in "$src" "${BASH_SOURCE[0]}" "$HERE"/*.h "$HERE"/*/*.h "$HERE"/../../include/*.h; do
+    if [ ! -f "$obj" ] || [ "$dep" -nt "$obj" ]; then
+      $HIPCC $FLAGS "$@" -c "$src" -o "$obj"
+      break
+    fi
+  done
+  tmp="$OUT/.$lib.tmp.$$"
+  $HIPCC --offload-arch=gfx950 -shared -fPIC -Wl,--version-script="$dir/exports.map" "$obj" -o "$tmp"
+  python3 "$HERE/../../tools/check_isa_hazards.py" "$tmp"
+  mv -f "$tmp" "$OUT/$lib"
+  echo "built $OUT/$lib"
+}
+for row in "${SIDE_LIBS[@]}"; do side_lib $row; done

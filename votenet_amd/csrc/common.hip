@@ -1,27 +1,23 @@
 // common.hip -- error text, version string, launch checking.
 #include "common.h"
+#include "error_text.h"
 #include <atomic>
 #include <cstdlib>
 #include <cstring>
 
 namespace votenet {
-static thread_local char g_err[512] = "";
+static thread_local ErrorText g_err;
 
 int set_error(int code, const char *fmt, ...)
 {
     va_list ap;
     va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
+    g_err.vset(code, fmt, ap);
     va_end(ap);
     return code;
 }
 
-int check_launch(const char *what)
-{
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(VOTENET_E_HIP, "%s: %s", what, hipGetErrorString(e));
-    return VOTENET_OK;
-}
+int check_launch(const char *what) { return g_err.check_launch(what); }
 
 static std::atomic<int> g_debug_enabled{-1}; // -1: not decided yet (the environment is read once, at the first switch call)
 bool debug_gate(const char *name)
@@ -41,5 +37,5 @@ bool debug_gate(const char *name)
 
 extern "C" void votenet_debug_enable(int on) { votenet::g_debug_enabled.store(on ? 1 : 0); }
 extern "C" int votenet_debug_enabled(void) { return votenet::g_debug_enabled.load() > 0 ? 1 : 0; }
-extern "C" const char *votenet_last_error(void) { return votenet::g_err; }
+extern "C" const char *votenet_last_error(void) { return votenet::g_err.text; }
 extern "C" const char *votenet_version(void) { return "votenet_hip 0.1 gfx950"; }

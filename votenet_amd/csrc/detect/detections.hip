@@ -8,6 +8,7 @@
 #include "../common.h"
 #include "../iou3d.h"
 #include "det_emit.h"
+#include "../error_text.h"
 
 #include <climits>
 #pragma GCC visibility push(default)
@@ -17,25 +18,8 @@
 namespace votenet {
 
 // ---- error plumbing of this library (thread-local text behind votenet_detections_last_error()) ----
-static thread_local char g_det_err[512] = "";
-static int det_set_error(int code, const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_det_err, sizeof(g_det_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
-static int det_check_launch(const char *what)
-{
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return det_set_error(VOTENET_E_HIP, "%s: %s", what, hipGetErrorString(e));
-    return VOTENET_OK;
-}
-#define DET_REQUIRE(cond, ...)                                                              \
-    do {                                                                                    \
-        if (!(cond)) return ::votenet::det_set_error(VOTENET_E_INVALID_ARGUMENT, __VA_ARGS__); \
-    } while (0)
+static thread_local ErrorText g_det_err;
+#define DET_REQUIRE(cond, ...) VN_REQUIRE_IN(::votenet::g_det_err, cond, __VA_ARGS__)
 
 // ---- votenet_class_nms3d (the limits, argmax_first and det_emit_kernel: det_emit.h) ----
 // One workgroup per scene, thread t owns box t.
@@ -281,7 +265,7 @@ __global__ __launch_bounds__(256) void eval_match_rows_kernel(int n, int g, int 
 
 using namespace votenet;
 
-extern "C" const char *votenet_detections_last_error(void) { return g_det_err; }
+extern "C" const char *votenet_detections_last_error(void) { return g_det_err.text; }
 
 extern "C" size_t votenet_class_nms3d_workspace_bytes(int b, int n, int nc)
 {
@@ -308,20 +292,20 @@ extern "C" int votenet_class_nms3d(int b, int n, int nc, const float *bboxes, co
     hipStream_t st = as_stream(stream);
     if (b == 0 || n == 0) {
         (void)hipMemsetAsync(det_offset, 0, ((size_t)b + 1) * sizeof(int), st);
-        return det_check_launch("class_nms3d");
+        return g_det_err.check_launch("class_nms3d");
     }
     DET_REQUIRE(bboxes && objectness && class_scores && det_rows, "class_nms3d: null buffer");
     DET_REQUIRE(((uintptr_t)det_rows & 15) == 0, "class_nms3d: det_rows must be 16-byte aligned");
     const size_t wbytes = votenet_class_nms3d_workspace_bytes(b, n, nc);
     if (workspace == nullptr || workspace_bytes < wbytes)
-        return det_set_error(VOTENET_E_WORKSPACE, "class_nms3d: workspace of %zu bytes required, got %zu", wbytes, workspace ? workspace_bytes : (size_t)0);
+        return g_det_err.set(VOTENET_E_WORKSPACE, "class_nms3d: workspace of %zu bytes required, got %zu", wbytes, workspace ? workspace_bytes : (size_t)0);
     int *kept = (int *)workspace;
     int *count = (int *)((char *)workspace + align256((size_t)b * n * sizeof(int)));
     hipLaunchKernelGGL(class_nms_kernel, dim3(b), dim3(DET_NMS_THREADS), 0, st, n, nc, bboxes, objectness, class_scores, iou_threshold,
                        conf_logit, class_nms, kept, count);
     hipLaunchKernelGGL(det_emit_kernel, dim3(b), dim3(256), 0, st, b, n, nc, objectness, class_scores, per_class, kept, count,
                        (uint4 *)det_rows, det_offset);
-    return det_check_launch("class_nms3d");
+    return g_det_err.check_launch("class_nms3d");
 }
 
 extern "C" int votenet_eval_match_rows(int b, int n, int g, int nc, const float *bboxes, const void *det_rows, long nrows,
@@ -349,5 +333,5 @@ extern "C" int votenet_eval_match_rows(int b, int n, int g, int nc, const float 
     hipLaunchKernelGGL(eval_match_rows_kernel, dim3(nc, b), dim3(256), 0, as_stream(stream), n, g, nc, bboxes, (const int4 *)det_rows,
                        nrows, det_offset, gt_boxes, gt_labels, gt_count, thr, nthr, (int)scene0, arrival0, (uint4 *)records, capacity,
                        rec_count, npos, flags);
-    return det_check_launch("eval_match_rows");
+    return g_det_err.check_launch("eval_match_rows");
 }

@@ -4,6 +4,7 @@
 //                                        point, the height above the scene's floor and up to four raw columns (colour, intensity).
 // Two launches: subsample_augment_kernel<T, true> (gather + transform + columns), floor_height_kernel (floor + heights).
 #include "../augment_points.h"
+#include "../error_text.h"
 #include <cmath>
 #pragma GCC visibility push(default)
 #include "../../../include/votenet_point_features.h"
@@ -12,25 +13,8 @@
 namespace votenet {
 
 // ---- error plumbing of this library (thread-local text behind votenet_point_features_last_error()) ----
-static thread_local char g_feat_err[512] = "";
-static int feat_set_error(int code, const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_feat_err, sizeof(g_feat_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
-static int feat_check_launch(const char *what)
-{
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return feat_set_error(VOTENET_E_HIP, "%s: %s", what, hipGetErrorString(e));
-    return VOTENET_OK;
-}
-#define FEAT_REQUIRE(cond, ...)                                                              \
-    do {                                                                                     \
-        if (!(cond)) return ::votenet::feat_set_error(VOTENET_E_INVALID_ARGUMENT, __VA_ARGS__); \
-    } while (0)
+static thread_local ErrorText g_feat_err;
+#define FEAT_REQUIRE(cond, ...) VN_REQUIRE_IN(::votenet::g_feat_err, cond, __VA_ARGS__)
 
 // ---- height above the floor (votenet_subsample_augment_features) ----
 // up = -y of the output point (upright camera, y down); the floor of a scene is np.percentile(up, 0.99) over its finite values:
@@ -158,7 +142,7 @@ __global__ __launch_bounds__(FLOOR_THREADS) void floor_height_kernel(int n_out, 
 
 using namespace votenet;
 
-extern "C" const char *votenet_point_features_last_error(void) { return g_feat_err; }
+extern "C" const char *votenet_point_features_last_error(void) { return g_feat_err.text; }
 
 extern "C" int votenet_subsample_augment_features(int b, int n_out, const void *raw, int raw_f64, int raw_stride,
                                                   const long *raw_offset, const int *choice, unsigned long long seed, long scene0,
@@ -183,5 +167,5 @@ extern "C" int votenet_subsample_augment_features(int b, int n_out, const void *
     if (want_height)
         hipLaunchKernelGGL(floor_height_kernel, dim3(b), dim3(FLOOR_THREADS), 0, as_stream(stream), n_out, out, c, feats, floor,
                            order_stats);
-    return feat_check_launch(what);
+    return g_feat_err.check_launch(what);
 }

@@ -14,37 +14,19 @@
 // the partials decide; so does a finite element whose square overflows.  The verdict reads what the all-reduce left in g: replicas agree.
 #include <hip/hip_runtime.h>
 #include <cmath>
-#include <cstdarg>
 #include <cstdint>
-#include <cstdio>
 #pragma GCC visibility push(default)
 #include "../../../include/votenet_step_guard.h"
 #pragma GCC visibility pop
-#include "../../../include/votenet_hip.h" // VOTENET_SUMSQ_SLICES
+#include "../../../include/votenet_hip.h" // VOTENET_SUMSQ_SLICES, the status codes
+#include "../error_text.h"
 
 namespace votenet {
 
 // ---- error plumbing of this library (thread-local text behind votenet_step_guard_last_error()) ----
-static thread_local char g_guard_err[512] = "";
-static int guard_set_error(int code, const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_guard_err, sizeof(g_guard_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
-static int guard_check_launch(const char *what)
-{
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return guard_set_error(2 /* VOTENET_E_HIP */, "%s: %s", what, hipGetErrorString(e));
-    return 0;
-}
+static thread_local ErrorText g_guard_err;
 static inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
-#define VN_REQUIRE(cond, ...)                                                                    \
-    do {                                                                                         \
-        if (!(cond)) return ::votenet::guard_set_error(1 /* VOTENET_E_INVALID_ARGUMENT */, __VA_ARGS__); \
-    } while (0)
+#define VN_REQUIRE(cond, ...) VN_REQUIRE_IN(::votenet::g_guard_err, cond, __VA_ARGS__)
 
 #include "../sumsq.h" // seg_sumsq_kernel, kSumsqSlices
 
@@ -120,7 +102,7 @@ __global__ void clip_adam_guarded_kernel(const long *__restrict__ seg, const flo
 
 using namespace votenet;
 
-extern "C" const char *votenet_step_guard_last_error(void) { return g_guard_err; }
+extern "C" const char *votenet_step_guard_last_error(void) { return g_guard_err.text; }
 
 extern "C" int votenet_step_guard_state_ints(void) { return VOTENET_STEP_GUARD_STATE_INTS; }
 
@@ -142,5 +124,5 @@ extern "C" int votenet_clip_adam_guarded(int ntensors, const long *seg, float *s
     const float bc1 = 1.0f - powf(beta1, (float)step), bc2 = 1.0f - powf(beta2, (float)step);
     hipLaunchKernelGGL(clip_adam_guarded_kernel, dim3(64, ntensors), dim3(256), 0, st, seg, sumsq_scratch, p, g, m, v, lr, beta1, beta2,
                        eps, bc1, bc2, grad_scale, clip_avg_norm, guard_state);
-    return guard_check_launch("clip_adam_guarded");
+    return g_guard_err.check_launch("clip_adam_guarded");
 }

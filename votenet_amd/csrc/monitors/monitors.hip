@@ -11,43 +11,25 @@
 // shuffles, the sixteen waves' partials in wave order -- so two runs, and two data-parallel replicas that hold the same bucket, give
 // the same bits; nothing is exchanged between workgroups.  The bucket is 3.8 MB: the launch is latency, not traffic.
 #include <hip/hip_runtime.h>
-#include <cstdarg>
 #include <cstdint>
-#include <cstdio>
 #pragma GCC visibility push(default)
 #include "../../../include/votenet_monitors.h"
 #pragma GCC visibility pop
+#include "../error_text.h" // (with include/votenet_hip.h for the status codes only)
 #include "../nearest_box.h"
 
 namespace votenet {
 
 // ---- error plumbing of this library (thread-local text behind votenet_monitors_last_error()) ----
-static thread_local char g_mon_err[512] = "";
-static int mon_set_error(int code, const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_mon_err, sizeof(g_mon_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
-static int mon_check_launch(const char *what)
-{
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return mon_set_error(2 /* VOTENET_E_HIP */, "%s: %s", what, hipGetErrorString(e));
-    return 0;
-}
+static thread_local ErrorText g_mon_err;
 static inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
-#define VN_REQUIRE(cond, ...)                                                                  \
-    do {                                                                                       \
-        if (!(cond)) return ::votenet::mon_set_error(1 /* VOTENET_E_INVALID_ARGUMENT */, __VA_ARGS__); \
-    } while (0)
+#define VN_REQUIRE(cond, ...) VN_REQUIRE_IN(::votenet::g_mon_err, cond, __VA_ARGS__)
 
 } // namespace votenet
 
 using namespace votenet;
 
-extern "C" const char *votenet_monitors_last_error(void) { return g_mon_err; }
+extern "C" const char *votenet_monitors_last_error(void) { return g_mon_err.text; }
 
 // ---------------------------------------------------------------- the step's accuracies (model.py:164-166, 215-216; run.py:127)
 namespace votenet {
@@ -169,7 +151,7 @@ extern "C" int votenet_accuracies(int b, int n_prop, int n_box, int nh, int ns, 
     AccArgs a = {n_prop, n_box, nc, proposals_xyz, proposals_output, output_pitch, bboxes_xyz, semantic_labels, pos_thr, neg_thr, losses,
                  ring, ring_row, accuracies, counts, workspace, 5 + 2 * nh + 4 * ns};
     hipLaunchKernelGGL(votenet_accuracies_kernel, dim3(b), dim3(ACC_T), 0, as_stream(stream), a);
-    return mon_check_launch("votenet_accuracies");
+    return g_mon_err.check_launch("votenet_accuracies");
 }
 
 // ---------------------------------------------------------------- per-tensor statistics
@@ -297,5 +279,5 @@ extern "C" int votenet_tensor_stats(int ntensors, const long *seg, const float *
     VN_REQUIRE(seg && x && stats && hist, "tensor_stats: null buffer");
     VN_REQUIRE((reinterpret_cast<uintptr_t>(x) & 15) == 0, "tensor_stats: the bucket must be 16-byte aligned");
     hipLaunchKernelGGL(tensor_stats_kernel, dim3(ntensors), dim3(TS_T), 0, as_stream(stream), seg, x, scale, clip_avg_norm, stats, hist);
-    return mon_check_launch("tensor_stats");
+    return g_mon_err.check_launch("tensor_stats");
 }

@@ -58,16 +58,16 @@ def class_nms3d(bboxes, objectness, class_scores, iou_threshold=0.25, conf_thres
         raise L.InvalidArgumentError("class_nms3d expects (batch_size, nbbox, num_class) class_scores shape.")
     nc = class_scores.shape[2]
     t = conf_logit(conf_thresh)
-    D = L.detect_lib()
+    D = L.side_lib("detect")
     cap = b * n * (nc if per_class else 1)
     rows = torch.empty((max(cap, 1), 4), dtype=torch.int32, device=bboxes.device)
     offset = torch.empty(b + 1, dtype=torch.int32, device=bboxes.device)
     wbytes = D.votenet_class_nms3d_workspace_bytes(b, n, nc)
     ws = torch.empty(wbytes, dtype=torch.uint8, device=bboxes.device)
     with L.device_guard(bboxes.device):
-        L.check_detect(D.votenet_class_nms3d(b, n, nc, L.ptr(bboxes), L.ptr(objectness), L.ptr(class_scores), float(iou_threshold), t,
-                                             1 if class_nms else 0, 1 if per_class else 0, L.ptr(rows), cap, L.ptr(offset), L.ptr(ws),
-                                             wbytes, L.stream_ptr()))
+        L.check(D.votenet_class_nms3d(b, n, nc, L.ptr(bboxes), L.ptr(objectness), L.ptr(class_scores), float(iou_threshold), t,
+                                      1 if class_nms else 0, 1 if per_class else 0, L.ptr(rows), cap, L.ptr(offset), L.ptr(ws),
+                                      wbytes, L.stream_ptr()), side="detect")
     return dict(det_rows=rows[:cap], det_offset=offset)
 
 

@@ -245,10 +245,10 @@ class DetectionAccumulator:
             raise L.VotenetError("DetectionAccumulator: more than 2^32 detection rows offered")
         st = self._state
         with L.device_guard(self.device):
-            L.check_detect(L.detect_lib().votenet_eval_match_rows(
+            L.check(L.side_lib("detect").votenet_eval_match_rows(
                 b, n, ng, NC, L.ptr(boxes), L.ptr(rows) if k else None, k, L.ptr(offset), L.ptr(g["boxes"]), L.ptr(g["labels"]),
                 L.ptr(g["count"]), len(self.thresholds), self._thr, self._scene, self._arrival, L.ptr(self._records), self.capacity,
-                st.data_ptr(), st.data_ptr() + 8, st.data_ptr() + 4, L.stream_ptr()))
+                st.data_ptr(), st.data_ptr() + 8, st.data_ptr() + 4, L.stream_ptr()), side="detect")
         self._scene += b
         self._arrival += k
 

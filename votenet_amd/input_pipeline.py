@@ -129,11 +129,11 @@ def subsample_augment_features(raw, raw_offset, n_out=POINT_NUM, aug=None, choic
     if aug is not None:
         flip, _, c_, s, sc = aug.host_arrays()
     with L.device_guard(raw.device):
-        L.check_features(L.features_lib().votenet_subsample_augment_features(b, n_out, L.ptr(raw), 1 if raw.dtype == torch.float64 else 0, raw.shape[1],
+        L.check(L.side_lib("features").votenet_subsample_augment_features(b, n_out, L.ptr(raw), 1 if raw.dtype == torch.float64 else 0, raw.shape[1],
                                                            _hp(off), L.ptr(ch), int(seed) & (2 ** 64 - 1), int(scene0),
                                                            1 if depth_to_camera else 0, _hp(flip), _hp(c_), _hp(s), _hp(sc), want_height,
                                                            extra_cols, L.ptr(out), L.ptr(feats), L.ptr(floor), L.ptr(order_stats),
-                                                           L.stream_ptr()))
+                                                           L.stream_ptr()), side="features")
     return out, feats, floor
 
 

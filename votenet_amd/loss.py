@@ -108,9 +108,9 @@ def votenet_accuracies(out, gt, nh=NH, ns=NS, nc=NC, losses=None, ring=None, rin
     if losses is not None and (losses.numel() != 12 or losses.dtype != torch.float32 or not losses.is_cuda):
         raise L.InvalidArgumentError("accuracies: losses must be the 12 floats of votenet_loss on the device")
     with L.device_guard(dev):
-        L.check_monitors(L.monitors_lib().votenet_accuracies(b, p, gxyz.shape[1], nh, ns, nc, L.ptr(pxyz), L.ptr(pout), pout.stride(1), L.ptr(gxyz), L.ptr(sem),
+        L.check(L.side_lib("monitors").votenet_accuracies(b, p, gxyz.shape[1], nh, ns, nc, L.ptr(pxyz), L.ptr(pout), pout.stride(1), L.ptr(gxyz), L.ptr(sem),
                                            POSITIVE_THRES, NEGATIVE_THRES, L.ptr(losses), L.ptr(ring), rows, ring_row, L.ptr(acc),
-                                           L.ptr(counts), L.ptr(work), L.stream_ptr()))
+                                           L.ptr(counts), L.ptr(work), L.stream_ptr()), side="monitors")
     return acc, counts
 
 

@@ -1604,7 +1604,7 @@ def clip_adam_guarded(seg, sumsq, p, g, m, v, lr, step, guard_state, ema=None, e
     nt = seg.numel() // 2
     if sumsq.numel() < SUMSQ_SLICES * nt:
         raise L.InvalidArgumentError("clip_adam_guarded: the scratch holds %d floats, %d tensors need %d" % (sumsq.numel(), nt, SUMSQ_SLICES * nt))
-    G = L.guard_lib()
+    G = L.side_lib("guard")
     want = G.votenet_step_guard_state_ints()
     if guard_state.dtype != torch.int32 or guard_state.numel() != want or not guard_state.is_contiguous():
         raise L.InvalidArgumentError("clip_adam_guarded: guard_state must be %d contiguous int32, got %d %s"
@@ -1621,7 +1621,7 @@ def clip_adam_guarded(seg, sumsq, p, g, m, v, lr, step, guard_state, ema=None, e
     if not p.is_cuda:
         raise L.VotenetError("clip_adam_guarded: the buffers must live on the GPU (no CPU fallback in votenet_amd)")
     with L.device_guard(p.device):
-        L.check_guard(G.votenet_clip_adam_guarded(nt, L.ptr(seg), L.ptr(sumsq), L.ptr(p), L.ptr(g), L.ptr(m), L.ptr(v), float(lr),
-                                                  float(beta1), float(beta2), float(eps), int(step), float(grad_scale), float(clip),
-                                                  L.ptr(ema) if n_ema else None, L.ptr(ema_snapshot) if n_ema else None, n_ema,
-                                                  L.ptr(guard_state), L.stream_ptr()))
+        L.check(G.votenet_clip_adam_guarded(nt, L.ptr(seg), L.ptr(sumsq), L.ptr(p), L.ptr(g), L.ptr(m), L.ptr(v), float(lr),
+                                            float(beta1), float(beta2), float(eps), int(step), float(grad_scale), float(clip),
+                                            L.ptr(ema) if n_ema else None, L.ptr(ema_snapshot) if n_ema else None, n_ema,
+                                            L.ptr(guard_state), L.stream_ptr()), side="guard")

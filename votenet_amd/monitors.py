@@ -66,7 +66,7 @@ def tensor_stats(seg, x, scale=1.0, clip=0.0, out=None):
     if tuple(stats.shape) != (nt, STATS_FLOATS) or tuple(hist.shape) != (nt, STATS_INTS):
         raise L.InvalidArgumentError("tensor_stats: output buffers made for another table")
     with L.device_guard(x.device):
-        L.check_monitors(L.monitors_lib().votenet_tensor_stats(nt, L.ptr(seg), L.ptr(x), float(scale), float(clip), L.ptr(stats), L.ptr(hist), L.stream_ptr()))
+        L.check(L.side_lib("monitors").votenet_tensor_stats(nt, L.ptr(seg), L.ptr(x), float(scale), float(clip), L.ptr(stats), L.ptr(hist), L.stream_ptr()), side="monitors")
     return stats, hist
 
 

@@ -44,7 +44,7 @@ class StepGuard:
         if not hasattr(net, "_seg"):
             raise L.InvalidArgumentError("enable_step_guard: the optimizer has no state yet -- call init_optimizer() (or load a "
                                          "checkpoint) first")
-        self.state_ints = L.guard_lib().votenet_step_guard_state_ints()
+        self.state_ints = L.side_lib("guard").votenet_step_guard_state_ints()
         self.state = torch.zeros(self.state_ints, dtype=torch.int32, device=net.store.flat.device)
         net._ema_state()  # (creates _ema_flat on first use)
         self._ema = net._ema_flat
