@@ -23,6 +23,7 @@ SIDE_LIBS = {
     "detect": "votenet_detections.h",        # class-wise 3D NMS, per-class detections and their matching
     "boxpts": "votenet_box_points.h",        # points inside predicted boxes, the empty-box gate
     "aabb": "votenet_aabb_nms.h",            # the axis-aligned overlaps of the paper's NMS
+    "depth": "votenet_depth_scan.h",         # the raw scan from the depth image
 }
 _side = {}  # name -> (the loaded library, its *_last_error function)
 

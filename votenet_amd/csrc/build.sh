@@ -54,6 +54,8 @@ SIDE_LIBS=(
   # the axis-aligned overlaps of the paper's NMS (tests/aabb_nms_ref.py restates them).  -fno-slp-vectorize as box_points.hip: the three
   # axes' products would pack likewise.  detect/det_emit.h is the text of votenet_class_nms3d's rows, so both libraries write the same bytes
   "aabb     aabb_nms.hip       aabb     -fno-slp-vectorize"
+  # the raw scan from the depth image.  No contraction: tests/depth_scan_ref.py restates the rule operation for operation in double
+  "depth    depth_scan.hip     depth"
 )
 # A side object is stale when its source, this script or ANY header of the project is newer: no list to keep by hand.
 side_lib() { # directory, source, library name, extra flags ...
