@@ -288,6 +288,43 @@ def test_match_rows_equals_the_restated_evaluation(hiplib, dev, O):
     assert all(abs(res2[0.25]["ap"][c] - both["ap"][c]) <= 1e-12 for c in both["ap"])
 
 
+def test_match_rows_of_one_class_cross_the_rounds_of_a_scene(hiplib, dev, O):
+    """b = 2, n = 257, two classes, every box a row of either class: each (scene, class) workgroup reads its scene's 514 rows in
+    rounds of 256 and keeps 128, 128 and 1 of them -- 257, past one round's worth of slots.  Through the entry itself (the
+    accumulator's launches have ten classes), against the restated evaluation."""
+    from votenet_amd import _lib as L, evaluator as E
+    B, N, G, nc = 2, 257, 16, 2
+    det, gtb, labels, count, rng = match_case(O, 23, B=B, N=N, G=G)
+    labels = (labels % nc).astype(np.int32)
+    count = np.array([G - 3, G // 2], np.int32)
+    table = cross_table(det, gtb, dev)
+    scene = np.repeat(np.arange(B), N * nc).astype(np.int32)
+    box = np.tile(np.repeat(np.arange(N), nc), B).astype(np.int32)
+    klass = np.tile(np.arange(nc), B * N).astype(np.int32)
+    score = rng.integers(-5, 40, len(scene)).astype(np.float32)
+    K = len(scene)
+    bb, rows, offset = T(det, dev), rows_tensor(scene, box, klass, score, dev), T(np.array([0, N * nc, 2 * N * nc], np.int32), dev)
+    g = E.gt_to_device(dict(boxes=gtb, labels=labels, count=count), dev)
+    records = torch.zeros((K, 4), dtype=torch.int32, device=dev)
+    state = torch.zeros(2 + nc, dtype=torch.int32, device=dev)  # [records offered, flags, npos[nc]], the accumulator's layout
+    thr = (ctypes.c_float * len(THRESHOLDS))(*THRESHOLDS)
+    L.check(L.side_lib("detect").votenet_eval_match_rows(
+        B, N, G, nc, L.ptr(bb), L.ptr(rows), K, L.ptr(offset), L.ptr(g["boxes"]), L.ptr(g["labels"]), L.ptr(g["count"]), len(THRESHOLDS),
+        thr, 0, 0, L.ptr(records), K, state.data_ptr(), state.data_ptr() + 8, state.data_ptr() + 4, L.stream_ptr()), side="detect")
+    state = state.cpu().numpy()
+    assert state[0] == K and state[1] == 0
+    rec = records.cpu().numpy()
+    rec = rec[np.argsort(rec[:, 3].view(np.uint32), kind="stable")]  # arrival order: the order of the rows
+    assert np.array_equal(rec[:, 3].view(np.uint32), np.arange(K)) and np.array_equal(rec[:, 0].copy().view(np.float32), score)
+    assert np.array_equal(rec[:, 1] & 0xff, klass) and np.array_equal(rec[:, 2], scene)
+    for t, thr_t in enumerate(THRESHOLDS):
+        exp = R.eval_rows(scene, box, klass, score, table, labels, count, nc, thr_t)
+        assert np.array_equal((rec[:, 1] >> (8 + t)) & 1, exp["tp"].astype(np.int64)), thr_t
+        assert np.array_equal(state[2:], exp["npos"])
+        print("thr %.2f: %d true positives of %d rows" % (thr_t, int(exp["tp"].sum()), K))
+        assert 0 < exp["tp"].sum() < K
+
+
 def test_match_rows_flags_bad_rows_and_overflow(hiplib, dev, O):
     from votenet_amd import InvalidArgumentError, VotenetError, evaluator as E
     det, gtb, labels, count, rng = match_case(O, 22, B=2, N=32, G=8)

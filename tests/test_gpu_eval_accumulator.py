@@ -172,6 +172,19 @@ def test_ties_empty_scenes_empty_add_and_repeated_padding(hiplib, dev):
         assert n == sum(int((gt["labels"][s, :count[s]] == c).sum()) for s in range(8))
 
 
+def test_a_scene_fills_a_round_of_kept_rows_and_another_has_one_row_in_the_next(hiplib, dev):
+    """257 kept rows: scene 1's 256 fill the first round of 256 rows the workgroups read, scene 0's single row is listed last, alone
+    in the second round; three ground-truth rows per scene."""
+    rng = np.random.default_rng(13)
+    pred, gt = random_scenes(rng, dev, B=2, N=256, G=3, count=[3, 3])
+    rows = np.array([[1, i] for i in range(256)] + [[0, 200]], np.int32)
+    pred["nms_idx"] = torch.from_numpy(rows).to(dev)
+    parts = [(pred, gt)]
+    acc = accumulate(dev, parts, capacity=257)
+    maps = check_against_eval_det(acc.result(), parts, "257 rows, 256 + 1:")
+    assert int(acc._state[0]) == 257 and maps[0.25] > 0.0
+
+
 def test_overlaps_are_bit_equal_to_iou3d_cross(hiplib, dev):
     """Thresholds one ulp either side of a detection's largest overlap (taken from votenet_iou3d_cross) flip its true-positive bit
     exactly there: the kernel's ovmax is that table's value, bit for bit.  One detection per scene, so nothing is ever taken."""

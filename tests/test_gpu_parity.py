@@ -594,6 +594,22 @@ def test_nms_greedy_by_bit_masks_and_by_the_wave_loop_vs_oracle(ops, dev, O, b, 
     assert keep.shape == exp.shape and (keep == exp).all()
 
 
+@pytest.mark.parametrize("b,n", [(4, 256), (5, 205)])
+def test_nms_candidates_fill_the_compaction_rounds_exactly_and_by_one_more_vs_oracle(ops, dev, O, b, n):
+    """Every box a candidate, 1024 and 1025 in the batch: nms_emit_kernel's round of 1024 rows is exactly full, then crossed by one
+    row; the mask kernel's rounds of 256 rows are full with the scenes' rows interleaved (the scores are a permutation over the
+    batch), the last one holding one row.  A room wide enough that the oracle keeps far more than 256 boxes of the batch (a scene
+    of 256 or 205 boxes cannot keep more than it has), so the kept rows cross the rounds as well.  The oracle's loop (tf_nms3d.cpp:202-273) is the yardstick: identical keep lists."""
+    c = cases.nms_random(b=b, n=n, seed=7 * n + b, room=8.0)
+    ob = np.tile(np.array([0.0, 1.0], np.float32), (b, n, 1))
+    keep = N(ops.n.NMS3D(T(c["bboxes"], dev), T(c["scores"], dev), T(ob, dev), 0.25))
+    exp = O.nms3d(c["bboxes"], c["scores"], ob, 0.25)
+    iou = np.stack([O.iou3d_matrix(c["bboxes"][s]) for s in range(b)])
+    assert b * n in (1024, 1025) and 256 < len(exp) < b * n  # something was suppressed
+    assert not (np.abs(iou - 0.25) < 1e-5).any()  # seeds chosen so (an IoU within rounding of the threshold could fall either side)
+    assert keep.shape == exp.shape and (keep == exp).all()
+
+
 def _greedy_on_matrix(M, order, thr):
     """tf_nms3d.cpp:237-262 on a given IoU matrix of one scene: M is read as M[candidate][kept] (suppress_check(candidate, selected))."""
     kept = []

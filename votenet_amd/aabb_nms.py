@@ -9,13 +9,16 @@ float32."""
 import torch
 
 from . import _lib as L
-from .detections import conf_logit
+from .detections import _class_nms, _entry
 
 OVERLAPS = ("rotated", "aabb3d", "bev")  # predict / evaluate's nms_overlap; "rotated" is detections.class_nms3d
 PAPER_OVERLAP = "aabb3d"  # parse_predictions' default: use_3d_nms
 MEASURES = ("iou", "over_later")  # "over_later": the paper's use_old_type_nms
 _MODE = dict(aabb3d=0, bev=1)  # VOTENET_AABB_3D, VOTENET_AABB_BEV
 _MEASURE = dict(iou=0, over_later=1)  # VOTENET_AABB_IOU, VOTENET_AABB_OVER_LATER
+
+
+_CLASS_NMS_AABB = _entry("aabb", "class_nms_aabb")
 
 
 def check_overlap(protocol, nms_overlap, nms_measure, who):
@@ -58,27 +61,5 @@ def class_nms_aabb(bboxes, objectness, class_scores, iou_threshold=0.25, conf_th
                    overlap="aabb3d", measure="iou"):
     """detections.class_nms3d deciding on the axis-aligned overlap: the same arguments, the same dict(det_rows, det_offset), the same
     rows wherever the two overlaps agree on which side of iou_threshold every pair falls.  N <= 512, NC <= 64."""
-    mode, meas = _codes(overlap, measure, "class_nms_aabb")
-    bboxes = L.dev_f32(bboxes.detach(), "class_nms_aabb expects (batch_size, nbbox, 8, 3) bbox shape.", 4, 3)
-    if bboxes.shape[2] != 8:
-        raise L.InvalidArgumentError("class_nms_aabb expects (batch_size, nbbox, 8, 3) bbox shape.")
-    b, n = bboxes.shape[:2]
-    objectness = L.dev_f32(objectness.detach(), "class_nms_aabb expects (batch_size, nbbox, 2) objectness shape.", 3, 2)
-    if tuple(objectness.shape) != (b, n, 2):
-        raise L.InvalidArgumentError("class_nms_aabb expects (batch_size, nbbox, 2) objectness shape.")
-    class_scores = L.dev_f32(class_scores.detach(), "class_nms_aabb expects (batch_size, nbbox, num_class) class_scores shape.", 3)
-    if tuple(class_scores.shape[:2]) != (b, n):
-        raise L.InvalidArgumentError("class_nms_aabb expects (batch_size, nbbox, num_class) class_scores shape.")
-    nc = class_scores.shape[2]
-    t = conf_logit(conf_thresh)
-    A = L.side_lib("aabb")
-    cap = b * n * (nc if per_class else 1)
-    rows = torch.empty((max(cap, 1), 4), dtype=torch.int32, device=bboxes.device)
-    offset = torch.empty(b + 1, dtype=torch.int32, device=bboxes.device)
-    wbytes = A.votenet_class_nms_aabb_workspace_bytes(b, n, nc)
-    ws = torch.empty(wbytes, dtype=torch.uint8, device=bboxes.device)
-    with L.device_guard(bboxes.device):
-        L.check(A.votenet_class_nms_aabb(b, n, nc, L.ptr(bboxes), L.ptr(objectness), L.ptr(class_scores), float(iou_threshold), t,
-                                         1 if class_nms else 0, 1 if per_class else 0, mode, meas, L.ptr(rows), cap, L.ptr(offset),
-                                         L.ptr(ws), wbytes, L.stream_ptr()), side="aabb")
-    return dict(det_rows=rows[:cap], det_offset=offset)
+    return _class_nms(_CLASS_NMS_AABB, _codes(overlap, measure, "class_nms_aabb"), bboxes, objectness, class_scores, iou_threshold,
+                      conf_thresh, class_nms, per_class)

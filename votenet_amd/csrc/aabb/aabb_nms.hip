@@ -3,17 +3,13 @@
 //   votenet_aabb_overlap_matrix   every (later, earlier) overlap of a scene's boxes.  aabb_matrix_kernel: a workgroup per
 //                                 (64 later boxes, scene).
 //   votenet_class_nms_aabb        votenet_class_nms3d (../detect/detections.hip) deciding on those overlaps.  class_nms_aabb_kernel
-//                                 (one workgroup per scene), then det_emit_kernel of ../detect/det_emit.h: the rows of
-//                                 libvotenet_detect.so, from one text.
+//                                 (one workgroup per scene), then det_emit_kernel and the host entry of ../detect/det_emit.h:
+//                                 the rows and the argument checks of libvotenet_detect.so, from one text.
 // Both kernels call aabb_of and aabb_overlap below.  The rules of the header are plain fp32 arithmetic in a fixed order
 // (-ffp-contract=off, as everywhere in this project): tests/aabb_nms_ref.py restates them in numpy float32 and the table is compared
 // bit for bit.
-#include "../common.h"
 #include "../detect/det_emit.h"
-#include "../error_text.h"
 
-#include <climits>
-#include <cstdint>
 #pragma GCC visibility push(default)
 #include "../../../include/votenet_aabb_nms.h"
 #pragma GCC visibility pop
@@ -207,8 +203,7 @@ extern "C" int votenet_aabb_overlap_matrix(int b, int n, const float *bboxes, in
 extern "C" size_t votenet_class_nms_aabb_workspace_bytes(int b, int n, int nc)
 {
     (void)nc;
-    if (b <= 0 || n <= 0) return 256;
-    return align256((size_t)b * n * sizeof(int)) + align256((size_t)b * sizeof(int)); // kept boxes per scene, their counts
+    return class_nms_workspace_bytes(b, n);
 }
 
 extern "C" int votenet_class_nms_aabb(int b, int n, int nc, const float *bboxes, const float *objectness, const float *class_scores,
@@ -216,35 +211,13 @@ extern "C" int votenet_class_nms_aabb(int b, int n, int nc, const float *bboxes,
                                       void *det_rows, long det_capacity, int *det_offset, void *workspace, size_t workspace_bytes,
                                       void *stream)
 {
-    AABB_REQUIRE(b >= 0 && b <= 65535, "class_nms_aabb: batch must be in [0, 65535], got %d", b);
-    AABB_REQUIRE(n >= 0 && n <= DET_MAX_N, "class_nms_aabb: at most %d boxes per scene, got n = %d", DET_MAX_N, n);
-    AABB_REQUIRE(nc >= 1 && nc <= DET_MAX_NC, "class_nms_aabb: the number of classes must be in [1, %d], got %d", DET_MAX_NC, nc);
-    AABB_REQUIRE(iou_threshold >= 0 && iou_threshold <= 1, "class_nms_aabb: iou_threshold must be in [0, 1], got %g", (double)iou_threshold);
-    AABB_REQUIRE(conf_logit == conf_logit && conf_logit < __builtin_inff(),
-                 "class_nms_aabb: conf_logit must be the logit of a confidence threshold in [0, 1): -inf <= T < +inf, got %g", (double)conf_logit);
-    AABB_REQUIRE((class_nms == 0 || class_nms == 1) && (per_class == 0 || per_class == 1), "class_nms_aabb: class_nms and per_class are 0 or 1");
     AABB_REQUIRE(mode == VOTENET_AABB_3D || mode == VOTENET_AABB_BEV, "class_nms_aabb: mode must be 0 (3D) or 1 (bird's-eye), got %d", mode);
     AABB_REQUIRE(measure == VOTENET_AABB_IOU || measure == VOTENET_AABB_OVER_LATER,
                  "class_nms_aabb: measure must be 0 (IoU) or 1 (intersection over the later box), got %d", measure);
-    AABB_REQUIRE(det_offset != nullptr, "class_nms_aabb: det_offset is required");
-    const long need = (long)b * n * (per_class ? nc : 1);
-    AABB_REQUIRE((long)b * n * nc <= (long)INT_MAX, "class_nms_aabb: b * n * nc must fit 31 bits");
-    AABB_REQUIRE(det_capacity >= need, "class_nms_aabb: det_rows must hold b * n * %d = %ld rows, got %ld", per_class ? nc : 1, need, det_capacity);
-    hipStream_t st = as_stream(stream);
-    if (b == 0 || n == 0) {
-        (void)hipMemsetAsync(det_offset, 0, ((size_t)b + 1) * sizeof(int), st);
-        return g_aabb_err.check_launch("class_nms_aabb");
-    }
-    AABB_REQUIRE(bboxes && objectness && class_scores && det_rows, "class_nms_aabb: null buffer");
-    AABB_REQUIRE(((uintptr_t)det_rows & 15) == 0, "class_nms_aabb: det_rows must be 16-byte aligned");
-    const size_t wbytes = votenet_class_nms_aabb_workspace_bytes(b, n, nc);
-    if (workspace == nullptr || workspace_bytes < wbytes)
-        return g_aabb_err.set(VOTENET_E_WORKSPACE, "class_nms_aabb: workspace of %zu bytes required, got %zu", wbytes, workspace ? workspace_bytes : (size_t)0);
-    int *kept = (int *)workspace;
-    int *count = (int *)((char *)workspace + align256((size_t)b * n * sizeof(int)));
-    hipLaunchKernelGGL(class_nms_aabb_kernel, dim3(b), dim3(DET_NMS_THREADS), 0, st, n, nc, bboxes, objectness, class_scores, iou_threshold,
-                       conf_logit, class_nms, mode, measure, kept, count);
-    hipLaunchKernelGGL(det_emit_kernel, dim3(b), dim3(256), 0, st, b, n, nc, objectness, class_scores, per_class, kept, count,
-                       (uint4 *)det_rows, det_offset);
-    return g_aabb_err.check_launch("class_nms_aabb");
+    return class_nms_entry(g_aabb_err, "class_nms_aabb", b, n, nc, bboxes, objectness, class_scores, iou_threshold, conf_logit, class_nms,
+                           per_class, det_rows, det_capacity, det_offset, workspace, workspace_bytes, stream,
+                           [&](hipStream_t st, int *kept, int *count) {
+                               hipLaunchKernelGGL(class_nms_aabb_kernel, dim3(b), dim3(DET_NMS_THREADS), 0, st, n, nc, bboxes, objectness,
+                                                  class_scores, iou_threshold, conf_logit, class_nms, mode, measure, kept, count);
+                           });
 }

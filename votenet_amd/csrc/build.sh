@@ -8,14 +8,19 @@ OUT="$HERE/../lib"
 mkdir -p "$OUT" "$HERE/obj"
 HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -fvisibility=hidden -ffp-contract=off -Wall -Wno-unused-function"
+# An object is stale when its source, this script (it carries the flags) or ANY header of the project is newer: no list to keep by hand.
+stale() { # object, source
+  local dep
+  [ -f "$1" ] || return 0
+  for dep in "$2" "${BASH_SOURCE[0]}" "$HERE"/*.h "$HERE"/*/*.h "$HERE"/../../include/*.h; do
+    [ "$dep" -nt "$1" ] && return 0
+  done
+  return 1
+}
 pids=()
 for src in "$HERE"/*.hip; do
   obj="$HERE/obj/$(basename "${src%.hip}").o"
-  # (this script carries the flags: an object older than it is stale too)
-  if [ ! -f "$obj" ] || [ "$src" -nt "$obj" ] || [ "$HERE/common.h" -nt "$obj" ] || [ "$HERE/mlp_types.h" -nt "$obj" ] || [ "$HERE/iou3d.h" -nt "$obj" ] \
-     || [ "$HERE/nearest_box.h" -nt "$obj" ] || [ "$HERE/sumsq.h" -nt "$obj" ] || [ "$HERE/augment_points.h" -nt "$obj" ] || [ "$HERE/error_text.h" -nt "$obj" ] \
-     || [ "$HERE/../../include/votenet_hip.h" -nt "$obj" ] || [ "$HERE/../../include/votenet_hip_debug.h" -nt "$obj" ] \
-     || [ "${BASH_SOURCE[0]}" -nt "$obj" ]; then
+  if stale "$obj" "$src"; then
     extra=""
     # fps.hip: no NaN can occur (distances of finite points); dropping NaN canonicalisation shortens the
     # serial per-round instruction chain.  Infinities (empty bucket boxes) are still honoured.
@@ -57,17 +62,11 @@ SIDE_LIBS=(
   # the raw scan from the depth image.  No contraction: tests/depth_scan_ref.py restates the rule operation for operation in double
   "depth    depth_scan.hip     depth"
 )
-# A side object is stale when its source, this script or ANY header of the project is newer: no list to keep by hand.
 side_lib() { # directory, source, library name, extra flags ...
-  local dir="$HERE/$1" src="$HERE/$1/$2" lib="libvotenet_$3.so" obj="$HERE/$1/obj/$(basename "${2%.hip}").o" tmp dep
+  local dir="$HERE/$1" src="$HERE/$1/$2" lib="libvotenet_$3.so" obj="$HERE/$1/obj/$(basename "${2%.hip}").o" tmp
   shift 3
   mkdir -p "$dir/obj"
-  for dep in "$src" "${BASH_SOURCE[0]}" "$HERE"/*.h "$HERE"/*/*.h "$HERE"/../../include/*.h; do
-    if [ ! -f "$obj" ] || [ "$dep" -nt "$obj" ]; then
-      $HIPCC $FLAGS "$@" -c "$src" -o "$obj"
-      break
-    fi
-  done
+  if stale "$obj" "$src"; then $HIPCC $FLAGS "$@" -c "$src" -o "$obj"; fi
   tmp="$OUT/.$lib.tmp.$$"
   $HIPCC --offload-arch=gfx950 -shared -fPIC -Wl,--version-script="$dir/exports.map" "$obj" -o "$tmp"
   python3 "$HERE/../../tools/check_isa_hazards.py" "$tmp"

@@ -15,7 +15,10 @@ namespace votenet {
 // ---- error plumbing (thread-local text behind votenet_last_error()) ----
 int set_error(int code, const char *fmt, ...);
 int check_launch(const char *what);
+struct ErrorText;
+ErrorText &error_text(); // this library's text (error_text.h), for a check that other libraries compile too
 inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
+inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; } // a workspace's arrays start on 256 bytes
 
 // The votenet_debug_* / votenet_fps_debug_* switches (include/votenet_hip_debug.h) are process-global measurement / tuning hooks.  They do
 // nothing until votenet_debug_enable(1) has been called (or VOTENET_DEBUG=1 was in the environment when the first one was called): a host that

@@ -7,6 +7,7 @@
 
 namespace votenet {
 static thread_local ErrorText g_err;
+ErrorText &error_text() { return g_err; }
 
 int set_error(int code, const char *fmt, ...)
 {

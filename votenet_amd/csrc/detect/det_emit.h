@@ -1,11 +1,15 @@
-// det_emit.h -- the part of a class-wise NMS that does not depend on its overlap: the limits, the class of a box and the launch that
-// turns a scene's kept boxes into detection rows.  One text for the two translation units that compile it, detections.hip
-// (libvotenet_detect.so, rotated-box IoU) and ../aabb/aabb_nms.hip (libvotenet_aabb.so, axis-aligned overlaps), as ../sumsq.h and
-// ../augment_points.h are shared: both libraries write the same rows for the same kept boxes.
+// det_emit.h -- the part of a class-wise NMS that does not depend on its overlap: the limits, the class of a box, the launch that
+// turns a scene's kept boxes into detection rows and the host entry around the two launches.  One text for the two translation
+// units that compile it, detections.hip (libvotenet_detect.so, rotated-box IoU) and ../aabb/aabb_nms.hip (libvotenet_aabb.so,
+// axis-aligned overlaps), as ../sumsq.h and ../augment_points.h are shared: both libraries refuse the same arguments and write the
+// same rows for the same kept boxes.
 #pragma once
-#include <hip/hip_runtime.h>
+#include "../common.h"
+#include "../error_text.h"
 
+#include <climits>
 #include <cstddef>
+#include <cstdint>
 
 namespace votenet {
 
@@ -78,6 +82,48 @@ __global__ __launch_bounds__(256) void det_emit_kernel(int b, int n, int nc, con
     }
 }
 
-static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+// ---- the host side of votenet_class_nms3d and votenet_class_nms_aabb ----
+inline size_t class_nms_workspace_bytes(int b, int n)
+{
+    if (b <= 0 || n <= 0) return 256;
+    return align256((size_t)b * n * sizeof(int)) + align256((size_t)b * sizeof(int)); // kept boxes per scene, their counts
+}
+
+// The argument checks (`name` is the entry's, the text goes to the library's own `err`), the empty batch, the workspace's two
+// arrays, launch_nms(stream, kept, count) -- the entry's own kernel -- and det_emit_kernel.
+template <class LaunchNms>
+inline int class_nms_entry(ErrorText &err, const char *name, int b, int n, int nc, const float *bboxes, const float *objectness,
+                           const float *class_scores, float iou_threshold, float conf_logit, int class_nms, int per_class,
+                           void *det_rows, long det_capacity, int *det_offset, void *workspace, size_t workspace_bytes, void *stream,
+                           LaunchNms launch_nms)
+{
+    VN_REQUIRE_IN(err, b >= 0 && b <= 65535, "%s: batch must be in [0, 65535], got %d", name, b);
+    VN_REQUIRE_IN(err, n >= 0 && n <= DET_MAX_N, "%s: at most %d boxes per scene, got n = %d", name, DET_MAX_N, n);
+    VN_REQUIRE_IN(err, nc >= 1 && nc <= DET_MAX_NC, "%s: the number of classes must be in [1, %d], got %d", name, DET_MAX_NC, nc);
+    VN_REQUIRE_IN(err, iou_threshold >= 0 && iou_threshold <= 1, "%s: iou_threshold must be in [0, 1], got %g", name, (double)iou_threshold);
+    VN_REQUIRE_IN(err, conf_logit == conf_logit && conf_logit < __builtin_inff(),
+                  "%s: conf_logit must be the logit of a confidence threshold in [0, 1): -inf <= T < +inf, got %g", name, (double)conf_logit);
+    VN_REQUIRE_IN(err, (class_nms == 0 || class_nms == 1) && (per_class == 0 || per_class == 1), "%s: class_nms and per_class are 0 or 1", name);
+    VN_REQUIRE_IN(err, det_offset != nullptr, "%s: det_offset is required", name);
+    const long need = (long)b * n * (per_class ? nc : 1);
+    VN_REQUIRE_IN(err, (long)b * n * nc <= (long)INT_MAX, "%s: b * n * nc must fit 31 bits", name);
+    VN_REQUIRE_IN(err, det_capacity >= need, "%s: det_rows must hold b * n * %d = %ld rows, got %ld", name, per_class ? nc : 1, need, det_capacity);
+    hipStream_t st = as_stream(stream);
+    if (b == 0 || n == 0) {
+        (void)hipMemsetAsync(det_offset, 0, ((size_t)b + 1) * sizeof(int), st);
+        return err.check_launch(name);
+    }
+    VN_REQUIRE_IN(err, bboxes && objectness && class_scores && det_rows, "%s: null buffer", name);
+    VN_REQUIRE_IN(err, ((uintptr_t)det_rows & 15) == 0, "%s: det_rows must be 16-byte aligned", name);
+    const size_t wbytes = class_nms_workspace_bytes(b, n);
+    if (workspace == nullptr || workspace_bytes < wbytes)
+        return err.set(VOTENET_E_WORKSPACE, "%s: workspace of %zu bytes required, got %zu", name, wbytes, workspace ? workspace_bytes : (size_t)0);
+    int *kept = (int *)workspace;
+    int *count = (int *)((char *)workspace + align256((size_t)b * n * sizeof(int)));
+    launch_nms(st, kept, count);
+    hipLaunchKernelGGL(det_emit_kernel, dim3(b), dim3(256), 0, st, b, n, nc, objectness, class_scores, per_class, kept, count,
+                       (uint4 *)det_rows, det_offset);
+    return err.check_launch(name);
+}
 
 } // namespace votenet

@@ -2,15 +2,14 @@
 // list is the drop-in ABI of the reference's ops and stays what it was): the VoteNet paper's detection protocol on the device.
 //   votenet_class_nms3d       class-wise greedy NMS ordered by objectness, a confidence threshold, one detection per class and kept
 //                             box, scored P(object) * P(class).  class_nms_kernel (one workgroup per scene), det_emit_kernel.
-//   votenet_eval_match_rows   votenet_eval_match (../eval_match.hip) on those rows: one workgroup per (scene, class).
+//   votenet_eval_match_rows   votenet_eval_match (../eval_match.hip) on those rows: one workgroup per (scene, class); the match
+//                             itself is ../eval_match_steps.h, the text eval_match.hip compiles.
 // The overlaps are iou3d_pair of ../iou3d.h, the one text nms3d.hip and eval_match.hip compile, under the same flags: a decision here
 // is the decision votenet_iou3d_matrix / votenet_iou3d_cross would tabulate.
-#include "../common.h"
-#include "../iou3d.h"
+#include "../block_compact.h"
+#include "../eval_match_steps.h"
 #include "det_emit.h"
-#include "../error_text.h"
 
-#include <climits>
 #pragma GCC visibility push(default)
 #include "../../../include/votenet_detections.h"
 #pragma GCC visibility pop
@@ -109,24 +108,8 @@ __global__ __launch_bounds__(DET_NMS_THREADS) void class_nms_kernel(int n, int n
     }
 }
 
-// ---- votenet_eval_match_rows: eval_match.hip's steps (b)-(f) for one (scene, class) ----
-constexpr int EVAL_MAX_DET = 1024; // rows of one scene and class: one per box
-constexpr int EVAL_MAX_GT = 4096;
-constexpr int EVAL_MAX_NC = 256; // the class travels in 8 bits of the record
-constexpr int EVAL_MAX_THR = 8;
-struct EvalThr {
-    float t[EVAL_MAX_THR];
-};
-constexpr int EVAL_F_OVERFLOW = 1, EVAL_F_BAD_ROW = 2, EVAL_F_SCENE = 4; // eval_match.hip's flags word
-
-// float bits -> unsigned that orders like the float (no NaN reaches this); eval_match.hip's key
-__device__ __forceinline__ unsigned ordered_bits(float v)
-{
-    const unsigned u = __float_as_uint(v);
-    return (u >> 31) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float from_ordered_bits(unsigned o) { return __uint_as_float((o >> 31) ? (o & 0x7fffffffu) : ~o); }
-
+// ---- votenet_eval_match_rows: votenet_eval_match (../eval_match.hip) for one (scene, class); its steps (d)-(f) are
+// ../eval_match_steps.h's ----
 __global__ __launch_bounds__(256) void eval_match_rows_kernel(int n, int g, int nc, const float *__restrict__ bboxes,
                                                               const int4 *__restrict__ rows, long nrows,
                                                               const int *__restrict__ det_offset,
@@ -145,7 +128,7 @@ __global__ __launch_bounds__(256) void eval_match_rows_kernel(int n, int g, int 
     __shared__ int s_qmask[EVAL_MAX_DET]; // {t : ovmax > thr[t]}
     __shared__ int s_gtlist[EVAL_MAX_GT]; // the scene's valid ground-truth rows of this class
     __shared__ int s_wcnt[4], s_len, s_ngc, s_base;
-    const int cls = blockIdx.x, scene = blockIdx.y, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int cls = blockIdx.x, scene = blockIdx.y, tid = threadIdx.x;
     int flag = 0;
     long lo = det_offset[scene], hi = det_offset[scene + 1];
     if (lo < 0 || hi < lo || hi > nrows) { // offsets that do not ascend inside the buffer: the scene is skipped
@@ -167,29 +150,15 @@ __global__ __launch_bounds__(256) void eval_match_rows_kernel(int n, int g, int 
             else if (r.z == cls)
                 mine = true, box = r.y, score = __int_as_float(r.w);
         }
-        const unsigned long long bal = __ballot(mine);
-        if (lane == 0) s_wcnt[w] = __popcll(bal);
-        __syncthreads();
-        int woff = 0, tot = 0;
-        for (int i = 0; i < 4; i++) {
-            if (i < w) woff += s_wcnt[i];
-            tot += s_wcnt[i];
+        const int q = block_compact<4>(mine, s_wcnt, &s_len);
+        if (mine && q < EVAL_MAX_DET) {
+            s_box[q] = box, s_row[q] = (unsigned)p;
+            s_score[q] = score != score ? -__builtin_inff() : score;
+            s_key[q] = 0ull;
+            s_nan[q] = 0;
         }
-        const int base = s_len;
-        if (mine) {
-            const int q = base + woff + __popcll(bal & ((1ull << lane) - 1ull));
-            if (q < EVAL_MAX_DET) {
-                s_box[q] = box, s_row[q] = (unsigned)p;
-                s_score[q] = score != score ? -__builtin_inff() : score;
-                s_key[q] = 0ull;
-                s_nan[q] = 0;
-            }
-        }
-        __syncthreads();
-        if (tid == 0) s_len = base + tot;
-        __syncthreads();
     }
-    int L = s_len;
+    int L = s_len; // (the slots are read after (b)'s barrier)
     if (L > EVAL_MAX_DET) {
         L = EVAL_MAX_DET;
         flag |= EVAL_F_SCENE;
@@ -211,54 +180,15 @@ __global__ __launch_bounds__(256) void eval_match_rows_kernel(int n, int g, int 
     for (int p = tid; p < npair; p += 256) {
         const int d = p / ngc;
         const int j = s_gtlist[p - d * ngc];
-        const float *__restrict__ pb = bboxes + ((size_t)scene * n + s_box[d]) * 24;
-        const float *__restrict__ pg = gt_boxes + ((size_t)scene * g + j) * 24;
-        float bi[24], bj[24];
-#pragma unroll
-        for (int t = 0; t < 24; t++) {
-            bi[t] = pb[t];
-            bj[t] = pg[t];
-        }
-        const float ov = iou3d_pair(bi, bj); // detection first, as votenet_iou3d_cross
-        if (ov != ov)
-            atomicOr(&s_nan[d], 1);
-        else
-            atomicMax(&s_key[d], ((unsigned long long)ordered_bits(ov + 0.0f) << 32) | (unsigned)(~j)); // -0 == +0 in a '>' scan
+        eval_fold_pair(bboxes + ((size_t)scene * n + s_box[d]) * 24, gt_boxes + ((size_t)scene * g + j) * 24, d, j, s_key, s_nan);
     }
     __syncthreads();
     // (e) ovmax, jmax and the thresholds they pass
-    for (int d = tid; d < L; d += 256) {
-        const unsigned long long k = s_key[d];
-        int q = 0, jm = -1;
-        if (k != 0ull && !s_nan[d]) {
-            const float ovmax = from_ordered_bits((unsigned)(k >> 32));
-            jm = (int)~(unsigned)k;
-            for (int t = 0; t < nthr; t++)
-                if (ovmax > thr.t[t]) q |= 1 << t;
-        }
-        s_jmax[d] = jm;
-        s_qmask[d] = q;
-    }
+    eval_pass_masks(L, s_key, s_nan, thr, nthr, s_jmax, s_qmask);
     __syncthreads();
     // (f) the box is taken at threshold t iff an earlier detection with the same jmax passes t
-    const int base = s_base;
-    for (int d = tid; d < L; d += 256) {
-        const int jm = s_jmax[d];
-        const float sd = s_score[d];
-        int taken = 0;
-        if (s_qmask[d])
-            for (int e = 0; e < L; e++) {
-                const float se = s_score[e];
-                if (s_jmax[e] == jm && (se > sd || (se == sd && e < d))) taken |= s_qmask[e];
-            }
-        const int tp = s_qmask[d] & ~taken;
-        const long pos = (long)base + d;
-        if (pos < (long)capacity)
-            records[pos] = make_uint4(__float_as_uint(sd), (unsigned)cls | ((unsigned)tp << 8), (unsigned)(scene0 + scene),
-                                      arrival0 + s_row[d]);
-        else
-            atomicOr(flags, EVAL_F_OVERFLOW);
-    }
+    eval_write_records(L, s_base, s_score, s_jmax, s_qmask, s_row, [cls](int) { return cls; }, (unsigned)(scene0 + scene), arrival0, records,
+                       capacity, flags);
 }
 
 } // namespace votenet
@@ -270,42 +200,19 @@ extern "C" const char *votenet_detections_last_error(void) { return g_det_err.te
 extern "C" size_t votenet_class_nms3d_workspace_bytes(int b, int n, int nc)
 {
     (void)nc;
-    if (b <= 0 || n <= 0) return 256;
-    return align256((size_t)b * n * sizeof(int)) + align256((size_t)b * sizeof(int)); // kept boxes per scene, their counts
+    return class_nms_workspace_bytes(b, n);
 }
 
 extern "C" int votenet_class_nms3d(int b, int n, int nc, const float *bboxes, const float *objectness, const float *class_scores,
                                    float iou_threshold, float conf_logit, int class_nms, int per_class, void *det_rows,
                                    long det_capacity, int *det_offset, void *workspace, size_t workspace_bytes, void *stream)
 {
-    DET_REQUIRE(b >= 0 && b <= 65535, "class_nms3d: batch must be in [0, 65535], got %d", b);
-    DET_REQUIRE(n >= 0 && n <= DET_MAX_N, "class_nms3d: at most %d boxes per scene, got n = %d", DET_MAX_N, n);
-    DET_REQUIRE(nc >= 1 && nc <= DET_MAX_NC, "class_nms3d: the number of classes must be in [1, %d], got %d", DET_MAX_NC, nc);
-    DET_REQUIRE(iou_threshold >= 0 && iou_threshold <= 1, "class_nms3d: iou_threshold must be in [0, 1], got %g", (double)iou_threshold);
-    DET_REQUIRE(conf_logit == conf_logit && conf_logit < __builtin_inff(),
-                "class_nms3d: conf_logit must be the logit of a confidence threshold in [0, 1): -inf <= T < +inf, got %g", (double)conf_logit);
-    DET_REQUIRE((class_nms == 0 || class_nms == 1) && (per_class == 0 || per_class == 1), "class_nms3d: class_nms and per_class are 0 or 1");
-    DET_REQUIRE(det_offset != nullptr, "class_nms3d: det_offset is required");
-    const long need = (long)b * n * (per_class ? nc : 1);
-    DET_REQUIRE((long)b * n * nc <= (long)INT_MAX, "class_nms3d: b * n * nc must fit 31 bits");
-    DET_REQUIRE(det_capacity >= need, "class_nms3d: det_rows must hold b * n * %d = %ld rows, got %ld", per_class ? nc : 1, need, det_capacity);
-    hipStream_t st = as_stream(stream);
-    if (b == 0 || n == 0) {
-        (void)hipMemsetAsync(det_offset, 0, ((size_t)b + 1) * sizeof(int), st);
-        return g_det_err.check_launch("class_nms3d");
-    }
-    DET_REQUIRE(bboxes && objectness && class_scores && det_rows, "class_nms3d: null buffer");
-    DET_REQUIRE(((uintptr_t)det_rows & 15) == 0, "class_nms3d: det_rows must be 16-byte aligned");
-    const size_t wbytes = votenet_class_nms3d_workspace_bytes(b, n, nc);
-    if (workspace == nullptr || workspace_bytes < wbytes)
-        return g_det_err.set(VOTENET_E_WORKSPACE, "class_nms3d: workspace of %zu bytes required, got %zu", wbytes, workspace ? workspace_bytes : (size_t)0);
-    int *kept = (int *)workspace;
-    int *count = (int *)((char *)workspace + align256((size_t)b * n * sizeof(int)));
-    hipLaunchKernelGGL(class_nms_kernel, dim3(b), dim3(DET_NMS_THREADS), 0, st, n, nc, bboxes, objectness, class_scores, iou_threshold,
-                       conf_logit, class_nms, kept, count);
-    hipLaunchKernelGGL(det_emit_kernel, dim3(b), dim3(256), 0, st, b, n, nc, objectness, class_scores, per_class, kept, count,
-                       (uint4 *)det_rows, det_offset);
-    return g_det_err.check_launch("class_nms3d");
+    return class_nms_entry(g_det_err, "class_nms3d", b, n, nc, bboxes, objectness, class_scores, iou_threshold, conf_logit, class_nms,
+                           per_class, det_rows, det_capacity, det_offset, workspace, workspace_bytes, stream,
+                           [&](hipStream_t st, int *kept, int *count) {
+                               hipLaunchKernelGGL(class_nms_kernel, dim3(b), dim3(DET_NMS_THREADS), 0, st, n, nc, bboxes, objectness,
+                                                  class_scores, iou_threshold, conf_logit, class_nms, kept, count);
+                           });
 }
 
 extern "C" int votenet_eval_match_rows(int b, int n, int g, int nc, const float *bboxes, const void *det_rows, long nrows,
@@ -313,21 +220,14 @@ extern "C" int votenet_eval_match_rows(int b, int n, int g, int nc, const float 
                                        int nthr, const float *thresholds, long scene0, unsigned arrival0, void *records,
                                        int capacity, int *rec_count, int *npos, int *flags, void *stream)
 {
-    DET_REQUIRE(b >= 0 && b <= 65535, "eval_match_rows: batch must be in [0, 65535], got %d", b);
     DET_REQUIRE(n >= 1 && n <= EVAL_MAX_DET, "eval_match_rows: 1 to %d boxes per scene, got n = %d", EVAL_MAX_DET, n);
-    DET_REQUIRE(g >= 0 && g <= EVAL_MAX_GT, "eval_match_rows: at most %d ground-truth rows per scene, got %d", EVAL_MAX_GT, g);
-    DET_REQUIRE(nc >= 1 && nc <= EVAL_MAX_NC, "eval_match_rows: the number of classes must be in [1, %d], got %d", EVAL_MAX_NC, nc);
-    DET_REQUIRE(nthr >= 1 && nthr <= EVAL_MAX_THR, "eval_match_rows: 1 to %d IoU thresholds, got %d", EVAL_MAX_THR, nthr);
-    DET_REQUIRE(thresholds != nullptr, "eval_match_rows: null thresholds");
-    DET_REQUIRE(nrows >= 0 && capacity >= 0, "eval_match_rows: negative row count or capacity");
-    DET_REQUIRE(scene0 >= 0 && scene0 + b <= (long)INT_MAX, "eval_match_rows: scene numbers must fit 31 bits, got %ld + %d", scene0, b);
-    DET_REQUIRE((unsigned long long)arrival0 + (unsigned long long)nrows <= 0xffffffffull, "eval_match_rows: arrival numbers must fit 32 bits");
-    DET_REQUIRE(records && rec_count && npos && flags, "eval_match_rows: null accumulator buffer");
+    if (int rc = eval_match_check(g_det_err, "eval_match_rows", b, g, nc, nthr, thresholds, nrows, capacity, scene0, arrival0, records,
+                                  rec_count, npos, flags, gt_boxes, gt_labels, gt_count))
+        return rc;
     if (b == 0) return VOTENET_OK;
     DET_REQUIRE(bboxes && det_offset, "eval_match_rows: null prediction buffer");
     DET_REQUIRE(nrows == 0 || det_rows, "eval_match_rows: null detection rows");
     DET_REQUIRE(((uintptr_t)det_rows & 15) == 0 && ((uintptr_t)records & 15) == 0, "eval_match_rows: det_rows and records must be 16-byte aligned");
-    DET_REQUIRE(g == 0 || (gt_boxes && gt_labels && gt_count), "eval_match_rows: null ground-truth buffer");
     EvalThr thr = {};
     for (int t = 0; t < nthr; t++) thr.t[t] = thresholds[t];
     hipLaunchKernelGGL(eval_match_rows_kernel, dim3(nc, b), dim3(256), 0, as_stream(stream), n, g, nc, bboxes, (const int4 *)det_rows,

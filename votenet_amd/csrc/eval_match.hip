@@ -27,34 +27,13 @@
 //   (f) per detection: a scan over the scene's records in LDS for an earlier claimant of the same box, then one 16-byte store.
 // Visit order inside a scene: score descending, then row index ascending.  Integer atomics and vector stores only: the records
 // of a launch do not depend on scheduling (their position in the buffer does; the host sorts by (score, arrival)).
+// A pair of (d), (e) and (f) are eval_match_steps.h's, the text votenet_eval_match_rows (detect/detections.hip) compiles too; the
+// compaction of (a) is block_compact.h's.
 #include "common.h"
-#include "iou3d.h"
-
-#include <climits>
+#include "block_compact.h"
+#include "eval_match_steps.h"
 
 namespace votenet {
-
-constexpr int EVAL_MAX_DET = 1024; // kept rows of one scene
-constexpr int EVAL_MAX_GT = 4096;  // ground-truth rows of one scene
-constexpr int EVAL_MAX_NC = 256;   // the class travels in 8 bits of the record
-constexpr int EVAL_MAX_THR = 8;    // one bit each in the record's mask
-
-struct EvalThr {
-    float t[EVAL_MAX_THR];
-};
-
-// flags word
-constexpr int EVAL_F_OVERFLOW = 1; // records dropped: the buffer was full
-constexpr int EVAL_F_BAD_ROW = 2;  // a kept row names a scene or a box outside the batch (skipped)
-constexpr int EVAL_F_SCENE = 4;    // more than EVAL_MAX_DET kept rows in one scene (the rest skipped)
-
-// float bits -> unsigned that orders like the float (no NaN reaches this)
-__device__ __forceinline__ unsigned ordered_bits(float v)
-{
-    const unsigned u = __float_as_uint(v);
-    return (u >> 31) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float from_ordered_bits(unsigned o) { return __uint_as_float((o >> 31) ? (o & 0x7fffffffu) : ~o); }
 
 __global__ __launch_bounds__(256) void eval_match_kernel(int n, int g, int nc, const float *__restrict__ bboxes,
                                                          const int *__restrict__ rows, int nrows,
@@ -78,7 +57,7 @@ __global__ __launch_bounds__(256) void eval_match_kernel(int n, int g, int nc, c
     __shared__ int s_gtlist[EVAL_MAX_GT];              // valid ground-truth rows, bucketed by class
     __shared__ int s_ccnt[EVAL_MAX_NC], s_cfill[EVAL_MAX_NC], s_cstart[EVAL_MAX_NC + 1];
     __shared__ int s_wcnt[4], s_len, s_base;
-    const int scene = blockIdx.x, nscene = gridDim.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int scene = blockIdx.x, nscene = gridDim.x, tid = threadIdx.x;
     int R = nrows;
     if (nrows_dev) { // the length NMS left on the device, never beyond the rows the caller says the buffer holds
         const int c = *nrows_dev;
@@ -100,23 +79,10 @@ __global__ __launch_bounds__(256) void eval_match_kernel(int n, int g, int nc, c
             else if (sc == scene)
                 mine = true, box = bx;
         }
-        const unsigned long long bal = __ballot(mine);
-        if (lane == 0) s_wcnt[w] = __popcll(bal);
-        __syncthreads();
-        int woff = 0, tot = 0;
-        for (int i = 0; i < 4; i++) {
-            if (i < w) woff += s_wcnt[i];
-            tot += s_wcnt[i];
-        }
-        const int base = s_len;
-        if (mine) {
-            const int q = base + woff + __popcll(bal & ((1ull << lane) - 1ull));
-            if (q < EVAL_MAX_DET) s_box[q] = box, s_row[q] = (unsigned)p;
-        }
-        __syncthreads();
-        if (tid == 0) s_len = base + tot;
-        __syncthreads();
+        const int q = block_compact<4>(mine, s_wcnt, &s_len);
+        if (mine && q < EVAL_MAX_DET) s_box[q] = box, s_row[q] = (unsigned)p;
     }
+    __syncthreads(); // the last round's slots
     int L = s_len;
     if (L > EVAL_MAX_DET) {
         L = EVAL_MAX_DET;
@@ -178,54 +144,15 @@ __global__ __launch_bounds__(256) void eval_match_kernel(int n, int g, int nc, c
         }
         const int d = lo;
         const int j = s_gtlist[s_cstart[s_cls[d]] + (p - s_poff[d])];
-        const float *__restrict__ pb = bboxes + ((size_t)scene * n + s_box[d]) * 24;
-        const float *__restrict__ pg = gt_boxes + ((size_t)scene * g + j) * 24;
-        float bi[24], bj[24];
-#pragma unroll
-        for (int t = 0; t < 24; t++) {
-            bi[t] = pb[t];
-            bj[t] = pg[t];
-        }
-        const float ov = iou3d_pair(bi, bj); // detection first, as votenet_iou3d_cross
-        if (ov != ov)
-            atomicOr(&s_nan[d], 1);
-        else
-            atomicMax(&s_key[d], ((unsigned long long)ordered_bits(ov + 0.0f) << 32) | (unsigned)(~j)); // -0 == +0 in a '>' scan
+        eval_fold_pair(bboxes + ((size_t)scene * n + s_box[d]) * 24, gt_boxes + ((size_t)scene * g + j) * 24, d, j, s_key, s_nan);
     }
     __syncthreads();
     // (e) ovmax, jmax and the thresholds they pass
-    for (int d = tid; d < L; d += 256) {
-        const unsigned long long k = s_key[d];
-        int q = 0, jm = -1;
-        if (k != 0ull && !s_nan[d]) {
-            const float ovmax = from_ordered_bits((unsigned)(k >> 32));
-            jm = (int)~(unsigned)k;
-            for (int t = 0; t < nthr; t++)
-                if (ovmax > thr.t[t]) q |= 1 << t;
-        }
-        s_jmax[d] = jm;
-        s_qmask[d] = q;
-    }
+    eval_pass_masks(L, s_key, s_nan, thr, nthr, s_jmax, s_qmask);
     __syncthreads();
     // (f) the box is taken at threshold t iff an earlier detection with the same jmax passes t
-    const int base = s_base;
-    for (int d = tid; d < L; d += 256) {
-        const int jm = s_jmax[d];
-        const float sd = s_score[d];
-        int taken = 0;
-        if (s_qmask[d])
-            for (int e = 0; e < L; e++) {
-                const float se = s_score[e];
-                if (s_jmax[e] == jm && (se > sd || (se == sd && e < d))) taken |= s_qmask[e];
-            }
-        const int tp = s_qmask[d] & ~taken;
-        const long pos = (long)base + d;
-        if (pos < (long)capacity)
-            records[pos] = make_uint4(__float_as_uint(sd), (unsigned)s_cls[d] | ((unsigned)tp << 8), (unsigned)(scene0 + scene),
-                                      arrival0 + s_row[d]);
-        else
-            atomicOr(flags, EVAL_F_OVERFLOW);
-    }
+    eval_write_records(L, s_base, s_score, s_jmax, s_qmask, s_row, [&](int d) { return s_cls[d]; }, (unsigned)(scene0 + scene), arrival0,
+                       records, capacity, flags);
 }
 
 } // namespace votenet
@@ -237,20 +164,13 @@ extern "C" int votenet_eval_match(int b, int n, int g, int nc, const float *bbox
                                   const int *gt_count, int nthr, const float *thresholds, long scene0, unsigned arrival0,
                                   void *records, int capacity, int *rec_count, int *npos, int *flags, void *stream)
 {
-    VN_REQUIRE(b >= 0 && b <= 65535, "eval_match: batch must be in [0, 65535], got %d", b);
     VN_REQUIRE(n >= 1, "eval_match expects (batch, n, 8, 3) predicted boxes with n >= 1, got n = %d", n);
-    VN_REQUIRE(g >= 0 && g <= EVAL_MAX_GT, "eval_match: at most %d ground-truth rows per scene, got %d", EVAL_MAX_GT, g);
-    VN_REQUIRE(nc >= 1 && nc <= EVAL_MAX_NC, "eval_match: the number of classes must be in [1, %d], got %d", EVAL_MAX_NC, nc);
-    VN_REQUIRE(nthr >= 1 && nthr <= EVAL_MAX_THR, "eval_match: 1 to %d IoU thresholds, got %d", EVAL_MAX_THR, nthr);
-    VN_REQUIRE(thresholds != nullptr, "eval_match: null thresholds");
-    VN_REQUIRE(nrows >= 0 && capacity >= 0, "eval_match: negative row count or capacity");
-    VN_REQUIRE(scene0 >= 0 && scene0 + b <= (long)INT_MAX, "eval_match: scene numbers must fit 31 bits, got %ld + %d", scene0, b);
-    VN_REQUIRE((unsigned long long)arrival0 + (unsigned long long)nrows <= 0xffffffffull, "eval_match: arrival numbers must fit 32 bits");
-    VN_REQUIRE(records && rec_count && npos && flags, "eval_match: null accumulator buffer");
+    if (int rc = eval_match_check(error_text(), "eval_match", b, g, nc, nthr, thresholds, nrows, capacity, scene0, arrival0, records, rec_count,
+                                  npos, flags, gt_boxes, gt_labels, gt_count))
+        return rc;
     if (b == 0) return VOTENET_OK;
     VN_REQUIRE(bboxes && class_scores, "eval_match: null prediction buffer");
     VN_REQUIRE(nrows == 0 || rows, "eval_match: null kept rows");
-    VN_REQUIRE(g == 0 || (gt_boxes && gt_labels && gt_count), "eval_match: null ground-truth buffer");
     EvalThr thr = {};
     for (int t = 0; t < nthr; t++) thr.t[t] = thresholds[t];
     hipLaunchKernelGGL(eval_match_kernel, dim3(b), dim3(256), 0, as_stream(stream), n, g, nc, bboxes, rows, nrows, nrows_dev,

@@ -16,6 +16,7 @@
 // Everything stays on the device; the data-dependent output length is returned through
 // *out_count.
 #include "common.h"
+#include "block_compact.h"
 #include "iou3d.h"
 
 namespace votenet {
@@ -112,20 +113,10 @@ __global__ __launch_bounds__(256) void nms_greedy_mask_kernel(int n, float thr, 
         const int p = start + tid;
         const int e = p < nc ? order[p] : -1;
         const bool mine = e >= 0 && e / n == scene;
-        const unsigned long long bal = __ballot(mine);
-        if (lane == 0) s_wcnt[w] = __popcll(bal);
-        __syncthreads();
-        int woff = 0, tot = 0;
-        for (int i = 0; i < 4; i++) {
-            if (i < w) woff += s_wcnt[i];
-            tot += s_wcnt[i];
-        }
-        const int base = s_len;
-        if (mine) s_list[base + woff + __popcll(bal & ((1ull << lane) - 1ull))] = e - scene * n;
-        __syncthreads();
-        if (tid == 0) s_len = base + tot;
-        __syncthreads();
+        const int q = block_compact<4>(mine, s_wcnt, &s_len);
+        if (mine) s_list[q] = e - scene * n;
     }
+    __syncthreads(); // the last round's slots
     const int L = s_len;
     // (b) suppression rows: bit j of row i = candidate j comes later and overlaps candidate i by more than thr.  A wave per row,
     //     a lane per candidate j of the word: the word is the ballot of the 64 comparisons
@@ -192,7 +183,7 @@ __global__ __launch_bounds__(1024) void nms_emit_kernel(int n, const int *__rest
     __shared__ int s_wsum[16];
     __shared__ int s_base;
     const int nc = *ncand;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int tid = threadIdx.x;
     if (tid == 0) s_base = 0;
     __syncthreads();
     for (int start = 0; start < nc; start += 1024) {
@@ -202,24 +193,11 @@ __global__ __launch_bounds__(1024) void nms_emit_kernel(int n, const int *__rest
             e = order[p];
             k = keep_flag[e];
         }
-        const unsigned long long bal = __ballot(k != 0);
-        const int before = __popcll(bal & ((1ull << lane) - 1ull));
-        if (lane == 0) s_wsum[w] = __popcll(bal);
-        __syncthreads();
-        int woff = 0, tot = 0;
-        for (int i = 0; i < 16; i++) {
-            if (i < w) woff += s_wsum[i];
-            tot += s_wsum[i];
-        }
-        const int base = s_base;
+        const int r = block_compact<16>(k != 0, s_wsum, &s_base);
         if (k) {
-            const int r = base + woff + before;
             out[r * 2 + 0] = e / n;
             out[r * 2 + 1] = e % n;
         }
-        __syncthreads();
-        if (tid == 0) s_base = base + tot;
-        __syncthreads();
     }
     if (tid == 0) *out_count = s_base;
 }
@@ -229,7 +207,6 @@ struct NmsWorkspace {
     int *order, *keep_flag, *ncand;
     size_t bytes;
 };
-static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 static NmsWorkspace nms_layout(int b, int n, void *base)
 {
     NmsWorkspace w;

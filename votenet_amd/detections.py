@@ -41,34 +41,50 @@ def protocol_params(protocol, iou_threshold=0.25):
     return params
 
 
+def _entry(side, who):
+    """What _class_nms needs of an entry votenet_<who> of side library `side`, formed once: the names and the three shape messages."""
+    return (side, "votenet_" + who, "votenet_%s_workspace_bytes" % who, "%s expects (batch_size, nbbox, 8, 3) bbox shape." % who,
+            "%s expects (batch_size, nbbox, 2) objectness shape." % who, "%s expects (batch_size, nbbox, num_class) class_scores shape." % who)
+
+
+def _class_nms(entry, tail, bboxes, objectness, class_scores, iou_threshold, conf_thresh, class_nms, per_class):
+    """class_nms3d and aabb_nms.class_nms_aabb: the shape checks, the buffers and the call of an _entry (its library is loaded here,
+    so only when it is asked for); `tail`: the entry's arguments between per_class and det_rows."""
+    side, fn, ws_fn, box_shape, obj_shape, cls_shape = entry
+    bboxes = L.dev_f32(bboxes.detach(), box_shape, 4, 3)
+    if bboxes.shape[2] != 8:
+        raise L.InvalidArgumentError(box_shape)
+    b, n = bboxes.shape[:2]
+    objectness = L.dev_f32(objectness.detach(), obj_shape, 3, 2)
+    if tuple(objectness.shape) != (b, n, 2):
+        raise L.InvalidArgumentError(obj_shape)
+    class_scores = L.dev_f32(class_scores.detach(), cls_shape, 3)
+    if tuple(class_scores.shape[:2]) != (b, n):
+        raise L.InvalidArgumentError(cls_shape)
+    nc = class_scores.shape[2]
+    t = conf_logit(conf_thresh)
+    lib = L.side_lib(side)
+    cap = b * n * (nc if per_class else 1)
+    rows = torch.empty((max(cap, 1), 4), dtype=torch.int32, device=bboxes.device)
+    offset = torch.empty(b + 1, dtype=torch.int32, device=bboxes.device)
+    wbytes = getattr(lib, ws_fn)(b, n, nc)
+    ws = torch.empty(wbytes, dtype=torch.uint8, device=bboxes.device)
+    with L.device_guard(bboxes.device):
+        L.check(getattr(lib, fn)(b, n, nc, L.ptr(bboxes), L.ptr(objectness), L.ptr(class_scores), float(iou_threshold), t,
+                                 1 if class_nms else 0, 1 if per_class else 0, *tail, L.ptr(rows), cap, L.ptr(offset), L.ptr(ws), wbytes,
+                                 L.stream_ptr()), side=side)
+    return dict(det_rows=rows[:cap], det_offset=offset)
+
+
+_CLASS_NMS3D = _entry("detect", "class_nms3d")
+
+
 def class_nms3d(bboxes, objectness, class_scores, iou_threshold=0.25, conf_thresh=0.05, class_nms=True, per_class=True):
     """(B,N,8,3) boxes, (B,N,2) objectness logits, (B,N,NC) class logits, all f32 on the device ->
     dict(det_rows (B*N*NC or B*N, 4) int32 {scene, box, class, score bits}, det_offset (B+1,) int32): scene s owns
     det_rows[det_offset[s]:det_offset[s+1]], the total is det_offset[B]; rows beyond it are not written.  Everything stays on the
     device and nothing synchronises (rows_to_host does).  N <= 512, NC <= 64."""
-    bboxes = L.dev_f32(bboxes.detach(), "class_nms3d expects (batch_size, nbbox, 8, 3) bbox shape.", 4, 3)
-    if bboxes.shape[2] != 8:
-        raise L.InvalidArgumentError("class_nms3d expects (batch_size, nbbox, 8, 3) bbox shape.")
-    b, n = bboxes.shape[:2]
-    objectness = L.dev_f32(objectness.detach(), "class_nms3d expects (batch_size, nbbox, 2) objectness shape.", 3, 2)
-    if tuple(objectness.shape) != (b, n, 2):
-        raise L.InvalidArgumentError("class_nms3d expects (batch_size, nbbox, 2) objectness shape.")
-    class_scores = L.dev_f32(class_scores.detach(), "class_nms3d expects (batch_size, nbbox, num_class) class_scores shape.", 3)
-    if tuple(class_scores.shape[:2]) != (b, n):
-        raise L.InvalidArgumentError("class_nms3d expects (batch_size, nbbox, num_class) class_scores shape.")
-    nc = class_scores.shape[2]
-    t = conf_logit(conf_thresh)
-    D = L.side_lib("detect")
-    cap = b * n * (nc if per_class else 1)
-    rows = torch.empty((max(cap, 1), 4), dtype=torch.int32, device=bboxes.device)
-    offset = torch.empty(b + 1, dtype=torch.int32, device=bboxes.device)
-    wbytes = D.votenet_class_nms3d_workspace_bytes(b, n, nc)
-    ws = torch.empty(wbytes, dtype=torch.uint8, device=bboxes.device)
-    with L.device_guard(bboxes.device):
-        L.check(D.votenet_class_nms3d(b, n, nc, L.ptr(bboxes), L.ptr(objectness), L.ptr(class_scores), float(iou_threshold), t,
-                                      1 if class_nms else 0, 1 if per_class else 0, L.ptr(rows), cap, L.ptr(offset), L.ptr(ws),
-                                      wbytes, L.stream_ptr()), side="detect")
-    return dict(det_rows=rows[:cap], det_offset=offset)
+    return _class_nms(_CLASS_NMS3D, (), bboxes, objectness, class_scores, iou_threshold, conf_thresh, class_nms, per_class)
 
 
 def rows_to_host(det):
