@@ -36,6 +36,14 @@ def test_linear_dense_vs_oracle(hiplib, dev, O, rows, cin, cout):
     st = N(stats)
     assert np.allclose(st[:cout], oz.astype(np.float64).sum(0), rtol=1e-5, atol=1e-3)
     assert np.allclose(st[cout:], (oz.astype(np.float64) ** 2).sum(0), rtol=1e-5, atol=1e-3)
+    # ... and what BatchNorm makes of the sums: the device's scale and shift against the float64 BatchNorm of the oracle's z, 1e-5 of the
+    # normalised output (tests/bn_stats_ref.py: metric)
+    import bn_stats_ref as S
+    g = (rng.normal(size=cout) * 0.3 + 1).astype(np.float32)
+    be = (rng.normal(size=cout) * 0.2).astype(np.float32)
+    sc, sh, _, _ = mlp.bn_finalize(rows, stats, T(g, dev), T(be, dev))
+    e = S.metric(oz, N(sc), N(sh), g, be)["e"]
+    assert e.max() <= S.BAR, e.max()
 
 
 def test_linear_dense_with_folded_bn_relu(hiplib, dev, O):

@@ -20,6 +20,7 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import bn_stats_ref as S  # noqa: E402
 import tile_walk_ref as R  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -153,6 +154,14 @@ def check_forward(f, z, stats, rows=None, weights=None):
         wt = torch.ones(rows, 1, dtype=torch.float64, device=ref.device) if weights is None else weights.double()[:, None]
         sref = torch.cat([(ref * wt).sum(0), (ref * ref * wt).sum(0)])
         assert np.allclose(stats.cpu().numpy(), sref.cpu().numpy(), rtol=1e-5, atol=1e-3 * f.bound)
+        # ... and what BatchNorm makes of them: the scale and shift the device derives from these sums against the float64 BatchNorm of
+        # the float64 product, 1e-5 of the normalised output (tests/bn_stats_ref.py: metric)
+        from votenet_amd import mlp as M
+        n = int(round(float(wt.sum())))
+        beta = torch.zeros_like(f.gamma)
+        sc, sh, _, _ = M.bn_finalize(n, stats, f.gamma, beta)
+        m = S.metric(ref.cpu().numpy(), sc.cpu().numpy(), sh.cpu().numpy(), f.gamma.cpu().numpy(), beta.cpu().numpy(), wt[:, 0].cpu().numpy())
+        assert float(m["e"].max()) <= S.BAR, float(m["e"].max())
 
 
 @cases("dense")

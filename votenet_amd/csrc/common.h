@@ -53,10 +53,10 @@ __device__ __forceinline__ void bn_raw_channel(const BnRaw &r, int c, int o, boo
 {
     const double mu = r.stats[o] / (double)r.rows;
     double v = r.stats[c + o] / (double)r.rows - mu * mu;
-    if (v < 0) v = 0;
+    if (v < 0 || r.rows == 1) v = 0;
     const float muf = (float)mu, vf = (float)v;
     sc = r.gamma[o] / sqrtf(vf + r.eps);
-    sh = r.beta[o] - muf * sc;
+    sh = (float)((double)r.beta[o] - mu * (double)sc);
     if (writer && r.out) {
         r.out[o] = sc;
         r.out[c + o] = sh;

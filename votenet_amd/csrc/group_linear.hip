@@ -19,14 +19,18 @@ __global__ __launch_bounds__(256) void group_linear_kernel(long rows, int n, int
                                                            const float *__restrict__ w_xyz, const float *__restrict__ bias,
                                                            float *__restrict__ z, double *__restrict__ stats)
 {
-    __shared__ float red[2][256][4];
+    __shared__ double red[2][256][4];
+    __shared__ int cnt[256];
     const int qc = cout >> 2, rpp = 256 / qc;
     const int q = threadIdx.x % qc, rl = threadIdx.x / qc;
     const float4 w0 = *reinterpret_cast<const float4 *>(w_xyz + 4 * q);
     const float4 w1 = *reinterpret_cast<const float4 *>(w_xyz + cout + 4 * q);
     const float4 w2 = *reinterpret_cast<const float4 *>(w_xyz + 2 * cout + 4 * q);
     const float4 bv = bias ? *reinterpret_cast<const float4 *>(bias + 4 * q) : make_float4(0.f, 0.f, 0.f, 0.f);
-    float4 s1 = make_float4(0.f, 0.f, 0.f, 0.f), s2 = s1;
+    // the statistics are summed about a pivot: the fp32 partials carry z - pc, pc = the first z this thread meets in the column cut to eight bits (their
+    // rounding is then that of a channel whose mean is near zero whatever |mean| / std of z is); the flush adds the pivot back in double
+    float4 s1 = make_float4(0.f, 0.f, 0.f, 0.f), s2 = s1, pc = s1;
+    int nrow = 0;
     const unsigned rows_per_scene = (unsigned)groups_per_scene * (unsigned)nsample; // rows < 2^31 (launcher): 32-bit divisions
     const long stride = (long)gridDim.x * rpp;
     constexpr int U = 4;
@@ -63,20 +67,30 @@ __global__ __launch_bounds__(256) void group_linear_kernel(long rows, int n, int
                 v.z = ((pv[u].z + dx[u] * w0.z) + dy[u] * w1.z) + dz[u] * w2.z + bv.z;
                 v.w = ((pv[u].w + dx[u] * w0.w) + dy[u] * w1.w) + dz[u] * w2.w + bv.w;
                 *reinterpret_cast<float4 *>(z + (size_t)r * cout + 4 * q) = v;
-                s1.x += v.x; s1.y += v.y; s1.z += v.z; s1.w += v.w;
-                s2.x += v.x * v.x; s2.y += v.y * v.y; s2.z += v.z * v.z; s2.w += v.w * v.w;
+                if (nrow++ == 0) pc = make_float4(stat_pivot(v.x), stat_pivot(v.y), stat_pivot(v.z), stat_pivot(v.w));
+                const float4 d = make_float4(v.x - pc.x, v.y - pc.y, v.z - pc.z, v.w - pc.w);
+                s1.x += d.x; s1.y += d.y; s1.z += d.z; s1.w += d.w;
+                s2.x += d.x * d.x; s2.y += d.y * d.y; s2.z += d.z * d.z; s2.w += d.w * d.w;
             }
         }
     }
     if (stats) {
-        *reinterpret_cast<float4 *>(&red[0][threadIdx.x][0]) = s1;
-        *reinterpret_cast<float4 *>(&red[1][threadIdx.x][0]) = s2;
+        const double nl = (double)nrow;
+        const float a1[4] = {s1.x, s1.y, s1.z, s1.w}, a2[4] = {s2.x, s2.y, s2.z, s2.w}, ap[4] = {pc.x, pc.y, pc.z, pc.w};
+#pragma unroll
+        for (int u = 0; u < 4; u++) stat_unpivot(a1[u], a2[u], (double)ap[u], nl, red[0][threadIdx.x][u], red[1][threadIdx.x][u]);
+        cnt[threadIdx.x] = nrow;
         __syncthreads();
-        for (int t = threadIdx.x; t < 2 * cout; t += 256) {
-            const int which = t / cout, ch = t % cout;
-            float v = 0.0f;
-            for (int i = 0; i < rpp; i++) v += red[which][i * qc + (ch >> 2)][ch & 3];
-            unsafeAtomicAdd(&stats[which * cout + ch], (double)v);
+        for (int ch = threadIdx.x; ch < cout; ch += 256) {
+            double t1 = 0.0, t2 = 0.0, n = 0.0;
+            for (int i = 0; i < rpp; i++) {
+                t1 += red[0][i * qc + (ch >> 2)][ch & 3];
+                t2 += red[1][i * qc + (ch >> 2)][ch & 3];
+                n += (double)cnt[i * qc + (ch >> 2)];
+            }
+            stat_cut(n, t1, t2); // the workgroup's rows of the column, as one short number per statistic
+            unsafeAtomicAdd(&stats[ch], t1);
+            unsafeAtomicAdd(&stats[cout + ch], t2);
         }
     }
 }

@@ -105,9 +105,14 @@ __global__ __launch_bounds__(256, (MT * NT >= 4 ? 2 : 3)) void mlp_linear_kernel
     constexpr int B_F4 = MLP_BK * BN / 4;       // 256 (BN=64) or 512 (BN=128)
     constexpr int B_PER_T = B_F4 / 256;         // 1 or 2
 
-    float s1[NT], s2[NT]; // per-lane partial column sums over all tiles of this workgroup
+    // per-lane partial column sums over all tiles of this workgroup, of z - pc: pc = the first z this lane meets in the column, cut to
+    // eight bits (the rounding of the fp32 partials is then that of a channel whose mean is near zero whatever |mean| / std of z is);
+    // the flush adds n pc and 2 pc s1 + n pc^2 back in double, exactly (stat_pivot)
+    float s1[NT], s2[NT], pc[NT];
 #pragma unroll
-    for (int j = 0; j < NT; j++) s1[j] = s2[j] = 0.0f;
+    for (int j = 0; j < NT; j++) s1[j] = s2[j] = pc[j] = 0.0f;
+    bool have_pc = false;
+    int nrow = 0; // rows this lane has added
 
     // The (tile, k-slab) iteration space is flattened into one sequence of steps so that the software
     // pipeline never drains between row tiles: while step s runs its MFMAs, the operands of step s+1
@@ -332,11 +337,19 @@ __global__ __launch_bounds__(256, (MT * NT >= 4 ? 2 : 3)) void mlp_linear_kernel
         if (last_k) {
             // epilogue: C/D layout of 32x32 MFMA: col = lane&31, row = (e&3) + 8*(e>>2) + 4*(lane>>5)
             const long m0 = tile * MLP_BM;
+            // valid rows are a prefix: where this lane's first row of the tile is past the end, so are its others
+            const bool first = !have_pc && (FAST || m0 + wm * MT * 32 + 4 * (lane >> 5) < rows);
+#pragma unroll
+            for (int i = 0; i < MT; i++)
+#pragma unroll
+                for (int e = 0; e < 16; e++)
+                    if (FAST || m0 + (wm * MT + i) * 32 + (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5) < rows) ++nrow;
 #pragma unroll
             for (int j = 0; j < NT; j++) {
                 const int col = n0 + (wn * NT + j) * 32 + (lane & 31);
                 const bool cok = col < cout;
                 const float bv = (bias && cok) ? bias[col] : 0.0f;
+                if (first) pc[j] = stat_pivot(acc[0][j][0] + bv);
 #pragma unroll
                 for (int i = 0; i < MT; i++) {
 #pragma unroll
@@ -345,24 +358,30 @@ __global__ __launch_bounds__(256, (MT * NT >= 4 ? 2 : 3)) void mlp_linear_kernel
                         if (FAST || (cok && row < rows)) {
                             const float v = acc[i][j][e] + bv;
                             z[(size_t)row * cout + col] = v;
-                            s1[j] += v;
-                            s2[j] += v * v;
+                            const float d = v - pc[j];
+                            s1[j] += d;
+                            s2[j] += d * d;
                         }
                     }
                 }
             }
+            have_pc = have_pc || first;
         }
         advance(tile, kt);
     }
     if (stats) {
 #pragma unroll
         for (int j = 0; j < NT; j++) {
-            const float t1 = s1[j] + __shfl_xor(s1[j], 32);
-            const float t2 = s2[j] + __shfl_xor(s2[j], 32);
+            double t1, t2, nw = (double)nrow;
+            stat_unpivot(s1[j], s2[j], (double)pc[j], nw, t1, t2);
+            t1 += __shfl_xor(t1, 32);
+            t2 += __shfl_xor(t2, 32);
+            nw += __shfl_xor(nw, 32);
+            stat_cut(nw, t1, t2); // the wave's rows of the column
             const int col = n0 + (wn * NT + j) * 32 + (lane & 31);
             if (lane < 32 && col < cout) {
-                unsafeAtomicAdd(&stats[col], (double)t1);
-                unsafeAtomicAdd(&stats[cout + col], (double)t2);
+                unsafeAtomicAdd(&stats[col], t1);
+                unsafeAtomicAdd(&stats[cout + col], t2);
             }
         }
     }
@@ -377,11 +396,11 @@ __global__ void bn_finalize_kernel(long rows, int c, const double *__restrict__ 
     if (o >= c) return;
     const double mu = stats[o] / (double)rows;
     double v = stats[c + o] / (double)rows - mu * mu;
-    if (v < 0) v = 0;
+    if (v < 0 || rows == 1) v = 0; // (one row: its variance is zero, whatever the rounding of its square says)
     const float muf = (float)mu, vf = (float)v;
     const float sc = gamma[o] / sqrtf(vf + eps);
     scale[o] = sc;
-    shift[o] = beta[o] - muf * sc;
+    shift[o] = (float)((double)beta[o] - mu * (double)sc); // one rounding: |mean| / std of 300 costs ulp(300 gamma) / 2, not three of them
     if (mean) mean[o] = muf;
     if (var) var[o] = vf;
 }

@@ -174,7 +174,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((EPI == 3 |
     constexpr int BN = WN * NT * 32;
     constexpr int LDB = BN + 4;
     constexpr int NB4 = FG_BK * BN / 4 / 256; // W float4 per thread per slab (1 or 2)
-    __shared__ float As[BF3 ? 1 : 2][BF3 ? 1 : FG_BK][FG_LDA];
+    __shared__ __attribute__((aligned(16))) float As[BF3 ? 1 : 2][BF3 ? 1 : FG_BK][FG_LDA]; // (aligned: the statistics' flush keeps doubles here)
     __shared__ float Bs[BF3 ? 1 : 2][BF3 ? 1 : FG_BK][LDB];
     // BF3: both operands as three bf16 pieces (split3 below), one image per (piece, k-half): [row or column][8 bf16 = 4 dwords] --
     // a lane's MFMA fragment is ONE 16-byte read and consecutive lanes read consecutive 16 bytes (conflict-free ds_read_b128);
@@ -685,6 +685,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((EPI == 3 |
     f32x2 s1p[NT], s2p[NT];
 #pragma unroll
     for (int j = 0; j < NT; j++) s1p[j] = s2p[j] = f32x2{0.0f, 0.0f};
+    // The forward statistics (EPI 0 / 2 / 8) are summed about a pivot: the fp32 partials carry z - c, c = the first z this lane meets in
+    // the column cut to eight significant bits (stat_pivot), so their rounding is that of a channel whose mean is within a few standard
+    // deviations of zero whatever |mean| / std of z is (DESIGN: BatchNorm statistics).  The pivot rides in the bias, bsh = bias - c, so
+    // the packed loop costs what it cost; the flush adds n c and 2 c s1 + n c^2 back in double (stat_unpivot), with the c in effect, and
+    // cuts the workgroup's sums to short numbers (stat_cut), so that the double atomics stay exact.
+    float bsh[NT];
+#pragma unroll
+    for (int j = 0; j < NT; j++) bsh[j] = (EPI == 2) ? 0.0f : bvs[j];
+    int stat_tiles = 0;   // tiles whose elements this lane has added (workgroup-uniform)
+    int stat_wex = 0;     // piece layout: the rows this lane's piece heads stand for beyond themselves
     // prologue: slab 0 (in flight since the top) -> LDS buffer 0; slabs 1 and 2 in flight in register sets 1 and 0
     store_regs(0, R[0]);
 #pragma unroll
@@ -919,10 +929,22 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((EPI == 3 |
                 }
             }
         }
+        if (EPI == 0 || POOL) {
+            if (stat_tiles == 0) {
+#pragma unroll
+                for (int j = 0; j < NT; j++) {
+                    const float c = stat_pivot(H2 ? __builtin_fmaf(acc[0][j][0], uns[j], bvs[j]) : acc[0][j][0] + bvs[j]);
+                    // EPI 2 forms z for the pool anyway and subtracts c itself.  Elsewhere c rides in the bias; bias - c is rounded to
+                    // fp32 like any other number, and the pivot the flush adds back is the one in effect, (double)bias - (double)bsh
+                    bsh[j] = (EPI == 2) ? c : bvs[j] - c;
+                }
+            }
+            ++stat_tiles;
+        }
         if (EPI == 0 || P32) {
 #pragma unroll
             for (int j = 0; j < NT; j++) {
-                const f32x2 bv2 = {bvs[j], bvs[j]};
+                const f32x2 bv2 = {bsh[j], bsh[j]}; // z - c (the stores above wrote z itself)
                 const f32x2 un2 = {uns[j], uns[j]};
 #pragma unroll
                 for (int i = 0; i < MT; i++) {
@@ -957,8 +979,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((EPI == 3 |
                                 pmini[i][j] = rloc;
                             }
                         }
-                        s1[j] += v;
-                        s2[j] += v * v;
+                        const float d = v - bsh[j]; // z - c
+                        s1[j] += d;
+                        s2[j] += d * d;
                     }
                 }
             }
@@ -983,12 +1006,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((EPI == 3 |
 #pragma unroll
                 for (int i = 0; i < MT; i++) {
                     const float wa = (kh == 0) ? whs[2 * i] - 1.0f : 0.0f, wb = (kh == 0) ? whs[2 * i + 1] - 1.0f : 0.0f;
+                    // (counted in integers: a float wa + wb seeds the SLP vectoriser, which then packs the weighted sums below into
+                    // v_pk_add_f32 with op_sel[1] = 1, the form tools/check_isa_hazards.py refuses)
+                    stat_wex += (kh == 0) ? (int)whs[2 * i] + (int)whs[2 * i + 1] - 2 : 0;
 #pragma unroll
                     for (int j = 0; j < NT; j++) {
-                        const float va = H2 ? __builtin_fmaf(acc[i][j][0], uns[j], bvs[j]) : acc[i][j][0] + bvs[j];
-                        const float vb = H2 ? __builtin_fmaf(acc[i][j][8], uns[j], bvs[j]) : acc[i][j][8] + bvs[j];
-                        s1[j] += wa * va + wb * vb;
-                        s2[j] += wa * (va * va) + wb * (vb * vb);
+                        const float ba = (EPI == 2) ? bvs[j] : bsh[j], bc = (EPI == 2) ? bsh[j] : 0.0f; // z - c either way
+                        const float va = (H2 ? __builtin_fmaf(acc[i][j][0], uns[j], ba) : acc[i][j][0] + ba) - bc;
+                        const float vb = (H2 ? __builtin_fmaf(acc[i][j][8], uns[j], ba) : acc[i][j][8] + ba) - bc;
+                        // (opaque products: with s1 and s2 consumed side by side in the flush the SLP vectoriser pairs them and forms
+                        // the two sums with a crossed v_pk_add_f32, op_sel[1] = 1 -- the form tools/check_isa_hazards.py refuses)
+                        float p1 = wa * va, p2 = wb * vb, p3 = wa * (va * va), p4 = wb * (vb * vb);
+                        asm volatile("" : "+v"(p1), "+v"(p2), "+v"(p3), "+v"(p4));
+                        s1[j] += p1 + p2;
+                        s2[j] += p3 + p4;
                     }
                 }
             }
@@ -1257,11 +1288,52 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((EPI == 3 |
     if (EPI == 0 || P32) {
 #pragma unroll
         for (int j = 0; j < NT; j++) {
-            s1[j] += s1p[j].x + s1p[j].y;
-            s2[j] += s2p[j].x + s2p[j].y;
+            // (opaque scalars: packed, the four horizontal adds come out as v_pk_add_f32 with op_sel[1] = 1, tools/check_isa_hazards.py)
+            float ax = s1p[j].x, ay = s1p[j].y, bx = s2p[j].x, by = s2p[j].y;
+            asm volatile("" : "+v"(ax), "+v"(ay), "+v"(bx), "+v"(by));
+            s1[j] += ax + ay;
+            s2[j] += bx + by;
         }
     }
-    if (EPI != 1 && A.stats && sk_contrib) {
+    if constexpr (EPI == 0 || POOL) {
+        if (A.stats && sk_contrib) {
+            // the pivots come back in double, per lane (a lane's c is its own); the half-waves and the WM waves that share a column
+            // block are combined in double in LDS (the operand buffers are free now), in a fixed order; the workgroup's sums are cut
+            // to short numbers (stat_cut) and go out as one atomic per column and statistic
+            double *redd = reinterpret_cast<double *>(BF3 ? reinterpret_cast<float *>(&As3[0][0][0][0]) : &As[0][0][0]); // [3][WM][BN]
+            static_assert(6 * WM * BN <= 2 * FG_BK * FG_LDA, "reduction scratch exceeds the A buffers");
+            static_assert(!BF3 || 6 * WM * BN <= 2 * NPC * 2 * PLA, "reduction scratch exceeds the split A buffers");
+            double nl = (double)(stat_tiles * (MT * 16)) + (double)stat_wex;
+            nl += __shfl_xor(nl, 32);
+#pragma unroll
+            for (int j = 0; j < NT; j++) {
+                const int c = (wn * NT + j) * 32 + l31;
+                double t1, t2;
+                stat_unpivot(s1[j], s2[j], (EPI == 2) ? (double)bsh[j] : (double)bvs[j] - (double)bsh[j],
+                             (double)(stat_tiles * (MT * 16)) + (double)stat_wex, t1, t2);
+                t1 += __shfl_xor(t1, 32);
+                t2 += __shfl_xor(t2, 32);
+                if (lane < 32) {
+                    redd[(0 * WM + wm) * BN + c] = t1;
+                    redd[(1 * WM + wm) * BN + c] = t2;
+                    redd[(2 * WM + wm) * BN + c] = nl;
+                }
+            }
+            __syncthreads();
+            for (int c = tid; c < BN; c += 256) {
+                double t1 = 0.0, t2 = 0.0, n = 0.0;
+#pragma unroll
+                for (int i = 0; i < WM; i++) {
+                    t1 += redd[(0 * WM + i) * BN + c];
+                    t2 += redd[(1 * WM + i) * BN + c];
+                    n += redd[(2 * WM + i) * BN + c];
+                }
+                stat_cut(n, t1, t2);
+                unsafeAtomicAdd(&A.stats[n0 + c], t1);
+                unsafeAtomicAdd(&A.stats[cout + n0 + c], t2);
+            }
+        }
+    } else if (EPI != 1 && A.stats && sk_contrib) {
         // combine the WM waves that share a column block in LDS (the operand buffers are free now: every wave is past
         // the last step's barrier), then one atomic per column and statistic per workgroup: a column's address takes
         // gridDim.x atomics instead of WM*gridDim.x, which is what bounds the tail of the narrow (BN = 64) variant

@@ -28,6 +28,35 @@ struct MlpIn {
     const float *geo, *ptab, *wx;
 };
 
+// The pivot the forward statistics are summed about (mlp.hip, mlp_fast.hip, group_linear.hip): a z of the column cut to eight
+// significant bits.  Short, so that n c, c s1 and n c^2 are exact in double and a flush adds short numbers (see mlp_fast.hip).
+__device__ __forceinline__ float stat_pivot(float z) { return __uint_as_float(__float_as_uint(z) & 0xffff0000u); }
+// A lane's (sum z, sum z^2) from its fp32 partials about the pivot c (n elements), in double (exact where c is a stat_pivot).
+__device__ __forceinline__ void stat_unpivot(float s1, float s2, double c, double n, double &t1, double &t2)
+{
+    const double d1 = (double)s1;
+    t1 = d1 + n * c;
+    t2 = (double)s2 + 2.0 * c * d1 + n * c * c;
+}
+// What a workgroup (mlp.hip: a wave) adds to the column's two sums with its double atomics, from the exact sums over its n rows: CUT to
+// a short number -- to 24 bits, what it was while it was an fp32 partial, or to 36 where the |mean| of these rows is 8 std or more
+// (there the variance needs them, and every workgroup's sums then have the column's exponent within a few binades, so 36-bit numbers
+// still add exactly).  Short contributions keep the double atomics exact, so the sums do not depend on the order in which the
+// workgroups arrive.  The decision is taken over a whole tile walk, never per lane: a lane's few rows are often constant (the copies of
+// a ball's first point) at any magnitude, and a long number of small magnitude is what does not add exactly.
+__device__ __forceinline__ void stat_cut(double n, double &t1, double &t2)
+{
+    if (t1 * t1 >= 64.0 * (n * t2 - t1 * t1)) { // (n^2 x the variance of these rows)
+        const double k = 131073.0;              // Veltkamp's splitter for 53 - 17 = 36 bits
+        const double g1 = t1 * k, g2 = t2 * k;
+        t1 = g1 - (g1 - t1);
+        t2 = g2 - (g2 - t2);
+    } else {
+        t1 = (double)(float)t1;
+        t2 = (double)(float)t2;
+    }
+}
+
 // z0[r,c] of a narrow first layer: ONE fma chain in a fixed order.  Every kernel that needs z0 rebuilds it with this function, so the
 // forward and the backward pass see bit-identical values (identical ReLU masks); zero-padded u / W0 entries add exactly nothing.
 __device__ __forceinline__ float narrow_z(const float (&u)[8], const float (&w)[8], float b)

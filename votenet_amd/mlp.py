@@ -151,7 +151,10 @@ def debug_switch(name, *args):
 
 
 def set_deterministic(on=True):
-    """Switch the bit-reproducible backward pass on / off; returns the previous setting."""
+    """Switch the bit-reproducible backward pass on / off; returns the previous setting.
+    (The forward BatchNorm sums are reproducible in either mode because what a workgroup adds with its double atomics is a short number
+    -- 24 bits, 36 where its rows' |mean| is 8 std or more: csrc/mlp_types.h, stat_cut.  That is a weaker guarantee than fp32 partials
+    gave: a workgroup of near-constant rows far smaller in magnitude than the column's others can round)"""
     global DETERMINISTIC
     prev, DETERMINISTIC = DETERMINISTIC, bool(on)
     return prev
