@@ -14,7 +14,7 @@ from votenet_amd import pointnet2 as P
 class _Graph:
     made = 0
 
-    def __init__(self, net, x, side):
+    def __init__(self, chain, x, side):
         _Graph.made += 1
         self.generation = 0
 
@@ -25,8 +25,8 @@ def net(monkeypatch):
     monkeypatch.setattr(VM, "GEOMETRY_GRAPHS", True)
     monkeypatch.setattr(torch.cuda, "is_current_stream_capturing", lambda: False)
     _Graph.made = 0
-    n = types.SimpleNamespace(proposal=types.SimpleNamespace(npoint=256))
-    n.pick = lambda x: VM.VoteNetHotPath._geometry_graph(n, x, None)
+    n = VM.GeometryPrefetch(chain=lambda *a: None, side_stream=lambda: None, device=torch.device("cpu"), prop_npoint=256)
+    n.pick = lambda x: n.next_graph(x, None)
     return n
 
 
@@ -43,9 +43,9 @@ def test_the_graph_under_the_running_pass_is_skipped(net):
     x = torch.zeros(2, 64, 3)
     net.pick(x)
     a, b, c = net.pick(x), net.pick(x), net.pick(x)
-    net._geometry_current = a
+    net.current = a
     assert net.pick(x) is None and net.pick(x) is b and net.pick(x) is c  # a's turn passes: that prefetch runs launch by launch
-    net._geometry_current = None
+    net.current = None
     assert net.pick(x) is a
 
 
@@ -63,21 +63,23 @@ def test_fallbacks_and_configuration_changes(net, monkeypatch):
     assert net.pick(x) is None                       # per-launch events wanted
     monkeypatch.setattr(P.tf_sampling, "PROFILE_EVENTS", None)
     assert net.pick(y) is None and net.pick(y) is not a          # another shape: its own warm-up and ring
-    assert len(net._geometry_rings) == 2
+    assert len(net.rings) == 2
     monkeypatch.setattr(P, "HALF_GROUPS", not P.HALF_GROUPS)     # a third configuration: the old rings (and their buffers) go
-    assert net.pick(x) is None and len(net._geometry_rings) == 1
+    assert net.pick(x) is None and len(net.rings) == 1
 
 
 def test_stale_hand_outs_are_not_trusted(net):
     x = torch.zeros(2, 64, 3)
     g = _Graph(None, x, None)
     g.generation = 5
-    net._prefetched = {id(x): (x, x._version, {"sa1": 1}, {"sa1": 2}, g, 5)}
-    assert VM.VoteNetHotPath._take_prefetched(net, x) == ({"sa1": 1}, {"sa1": 2}) and net._geometry_current is g
-    net._prefetched = {id(x): (x, x._version, {"sa1": 1}, {"sa1": 2}, g, 4)}  # the graph has served another batch since
-    assert VM.VoteNetHotPath._take_prefetched(net, x) is None and net._geometry_current is None
-    net._prefetched = {id(x): (x, x._version - 1 if x._version else -1, {}, {}, None, 0)}  # the tensor was written since
-    assert VM.VoteNetHotPath._take_prefetched(net, x) is None
+    pool = net.pool
+    pool[id(x)] = VM.PrefetchEntry(x, x._version, {"sa1": 1}, {"sa1": 2}, g, 5)
+    assert net.take(x) == ({"sa1": 1}, {"sa1": 2}) and net.current is g and not pool
+    pool[id(x)] = VM.PrefetchEntry(x, x._version, {"sa1": 1}, {"sa1": 2}, g, 4)  # the graph has served another batch since
+    assert net.take(x) is None and net.current is None
+    pool[id(x)] = VM.PrefetchEntry(x, x._version - 1 if x._version else -1, {}, {}, None, 0)  # the tensor was written since
+    assert net.take(x) is None
+    assert net.pool is pool  # (emptied in place, never rebound)
 
 
 def test_changing_shapes_turn_the_graphs_off(net):
@@ -86,7 +88,7 @@ def test_changing_shapes_turn_the_graphs_off(net):
             x = torch.zeros(1, 32 + i, 3)
             net.pick(x)
             net.pick(x)
-    assert net._geometry_graphs_off and net.pick(torch.zeros(1, 32, 3)) is None
+    assert net.graphs_off and net.pick(torch.zeros(1, 32, 3)) is None
     made = _Graph.made
     net.pick(torch.zeros(1, 32, 3))
     assert _Graph.made == made

@@ -322,7 +322,8 @@ def test_config5_dense_scan_forward_properties(hiplib, dev):
         z2 = r2["half"].full_rows(z2)
     act = z2.view(4 * 2048, 64, -1) * r2["scale"] + r2["shift"]
     pooled = torch.where(act > 0, act, torch.zeros_like(act)).amax(1)
-    again = net.sa1.forward(x, x, tape=None, geom=(sa1["fps_idx"], new_xyz, idx, cnt))[1]  # (a 4-tuple geometry: the full layout)
+    from votenet_amd import pointnet2 as P
+    again = net.sa1.forward(x, x, tape=None, geom=P.SAGeometry(sa1["fps_idx"], new_xyz, idx, cnt))[1]  # (no rows built ahead: the full layout)
     if r2.get("half") is None:
         assert torch.equal(pooled.view(4, 2048, -1), again)
     else:  # the two layouts associate the BatchNorm sums differently: equal to rounding; the same layout again: equal
@@ -365,7 +366,7 @@ def test_prefetched_geometry_is_the_same_computation(hiplib, dev):
     net = VM.VoteNetHotPath(dev, seed=3, npoints=(512, 256, 128, 64))
     ref_b = net.forward(xb)
     net.forward(xa, next_x=xb)
-    assert id(xb) in net._prefetched and net._prefetched[id(xb)][0] is xb
+    assert id(xb) in net._prefetched and net._prefetched[id(xb)].x is xb
     got_b = net.forward(xb)
     assert not net._prefetched
     for k in ref_b:
@@ -390,6 +391,52 @@ def test_prefetched_geometry_is_the_same_computation(hiplib, dev):
         assert torch.equal(ref_b[k], b2[k]) and torch.equal(ref_c[k], c2[k]), k
 
 
+def test_propose_called_directly_does_not_reuse_another_batchs_sampling(hiplib, dev):
+    """propose() takes the proposal layer's FPS indices as an argument; called without them it samples the seeds it is given.  (They
+    used to travel in an attribute that forward() left behind: a direct call after a forward pass on ANOTHER batch sampled its votes
+    with that batch's indices.)
+    (i) Batch b's votes and seeds after a pass on batch a, against batch b's own forward pass: the centres are equal bit for bit; the
+    outputs to 1e-5 of their maximum, the bound two row layouts of one level get above: inside forward() the level runs with the piece
+    count on the device, called directly with the count on the host.
+    (ii) That alone cannot tell a stale index list from the right one: the seeds a forward pass produces are in FPS order (sa2 samples
+    sa1's centres, which sa1 left in FPS order, and FPS prefixes nest), so the proposal layer's sampling of them is 0..255 for EVERY
+    batch -- measured here at 256 and at 512 seeds.  So the same call again with the seeds (and their votes) rotated by one place:
+    their sampling differs from the list the pass on batch a left (asserted), the centres must be the votes at the seeds' OWN sampling,
+    and centres and outputs those of the proposal module run by itself on these inputs (bit for bit / the bound of (i))."""
+    from votenet_amd import mlp as M
+    from votenet_amd import model as VM
+    from votenet_amd import synth, tf_sampling as S
+    xa = torch.from_numpy(synth.room_batch(2, 4096, 11)).to(dev)
+    xb = torch.from_numpy(synth.room_batch(2, 4096, 21)).to(dev)
+    net = VM.VoteNetHotPath(dev, seed=3, npoints=(512, 256, 128, 64))
+    out_b = {k: v.clone() for k, v in net.forward(xb).items()}
+    out_a = net.forward(xa)
+
+    def in_a_pass(fn, *args):  # as _device_layers runs a module by itself
+        net.store.refresh_split()
+        M.arena_begin(dev)
+        try:
+            return fn(*args)
+        finally:
+            M.arena_end()
+
+    def close(got, want, what):
+        err, top = float((got - want).abs().max()), float(want.abs().max())
+        print("%s: max |diff| %.3e, max |output| %.3e" % (what, err, top))
+        return err < 1e-5 * top
+    px, pout = in_a_pass(net.propose, out_b["votes_xyz"], out_b["votes_points"], out_b["seeds_xyz"])
+    assert torch.equal(px, out_b["proposals_xyz"])
+    assert close(pout, out_b["proposals_output"], "direct propose vs forward")
+    vx, vp, sx = (torch.roll(out_b[k], 1, dims=1).contiguous() for k in ("votes_xyz", "votes_points", "seeds_xyz"))
+    own, stale = S.farthest_point_sample(256, sx), S.farthest_point_sample(256, out_a["seeds_xyz"])
+    assert not torch.equal(own, stale)  # (a stale index list cannot pass by accident)
+    px, pout = in_a_pass(net.propose, vx, vp, sx)
+    assert torch.equal(px, S.gather_point(vx, own))
+    want_x, want, _ = in_a_pass(lambda: net.proposal.forward(vx, vp, sample_xyz=sx))
+    assert torch.equal(px, want_x)
+    assert close(pout, want, "direct propose vs the proposal module, rotated seeds")
+
+
 def test_geometry_graph_replays_are_the_launch_by_launch_chain(hiplib, dev, monkeypatch):
     """model.GeometryGraph: the prefetched chain replayed as one HIP graph gives bit-identical passes to the chain enqueued launch by
     launch, batch after batch around the ring of graphs; a prefetch whose graph has served another batch since is not trusted; a
@@ -406,7 +453,7 @@ def test_geometry_graph_replays_are_the_launch_by_launch_chain(hiplib, dev, monk
         got = net.forward(xs[i % 5], next_x=xs[(i + 1) % 5])
         for k in refs[0]:
             assert torch.equal(got[k], refs[i % 5][k]), (i, k)
-    ring = next(iter(net._geometry_rings.values()))
+    ring = next(iter(net._geometry.rings.values()))
     assert len(ring["graphs"]) == VM.GEOMETRY_RING and sum(g.generation for g in ring["graphs"]) >= 9
     # the tape of a pass on replayed geometry drives the same backward pass
     def grads(x, **kw):
@@ -420,7 +467,7 @@ def test_geometry_graph_replays_are_the_launch_by_launch_chain(hiplib, dev, monk
     o_ref, g_ref = grads(xs[2])
     monkeypatch.setattr(VM, "GEOMETRY_GRAPHS", True)
     net.forward(xs[0], next_x=xs[2])
-    assert net._prefetched[id(xs[2])][4] is not None  # a graph served it
+    assert net._prefetched[id(xs[2])].graph is not None  # a graph served it
     o_got, g_got = grads(xs[2])
     assert torch.equal(o_got["proposals_output"], o_ref["proposals_output"])
     assert (g_got - g_ref).abs().max() <= 1e-5 * g_ref.abs().max()  # atomics: the order of a sum varies run to run
@@ -431,7 +478,7 @@ def test_geometry_graph_replays_are_the_launch_by_launch_chain(hiplib, dev, monk
     for x in (xs[0], xs[1], xs[2], xs[4]):
         net.prefetch_geometry(x)
     net._prefetched[id(xs[3])] = held  # (the pool had dropped it: put the stale entry back)
-    assert held[4].generation != held[5]
+    assert held.graph.generation != held.generation
     got = net.forward(xs[3])
     assert torch.equal(got["proposals_output"], refs[3]["proposals_output"])
     # a lookahead of four with a ring of three: the graph under the running pass is skipped (that prefetch runs launch by launch)
@@ -459,7 +506,7 @@ def test_outputs_and_tapes_on_graph_geometry_do_not_silently_go_stale(hiplib, de
     tape = []
     out = net.forward(xs[0], tape)
     gg, gen = tape[0]["geometry_stamp"]
-    assert gg is net._geometry_current and gen == gg.generation
+    assert gg is net._geometry.current and gen == gg.generation
     sa2_centres = tape[1]["new_xyz"]
     assert out["seeds_xyz"].data_ptr() != sa2_centres.data_ptr() and torch.equal(out["seeds_xyz"], sa2_centres)
     seeds = out["seeds_xyz"].clone()

@@ -143,18 +143,18 @@ def test_prefetched_geometry_with_features_is_the_same_computation(hiplib, dev):
         x, f = data[i % 4]
         nx, nf = data[(i + 1) % 4]
         entry = net._prefetched[id(x)]
-        assert entry[0] is x and entry[6] is f
-        served.append(entry[4] is not None)
+        assert entry.x is x and entry.feats is f
+        served.append(entry.graph is not None)
         got = net.forward(x, feats=f, next_x=[nx], next_feats=[nf])
         for k in refs[0]:
             assert torch.equal(got[k], refs[i % 4][k]), (i, k)
     assert served[0] is False and served[-1] is True  # launch by launch first, then graphs
-    ring = next(iter(net._geometry_rings.values()))
+    ring = next(iter(net._geometry.rings.values()))
     assert len(ring["graphs"]) == VM.GEOMETRY_RING and all(g.feats is not None for g in ring["graphs"])
     # stale features: changed in place after the prefetch
     x, f = data[1]
     net.prefetch_geometry(x, f)
-    assert net._prefetched[id(x)][4] is not None
+    assert net._prefetched[id(x)].graph is not None
     f.add_(1)
     want = fresh.forward(x, feats=f)
     got = net.forward(x, feats=f)
@@ -169,9 +169,9 @@ def test_prefetched_geometry_with_features_is_the_same_computation(hiplib, dev):
     assert torch.equal(got["proposals_output"], want["proposals_output"])
     # the same through the launch-by-launch prefetch (graphs off)
     net.drop_graphs()
-    net._geometry_graphs_off = True
+    net._geometry.graphs_off = True
     net.prefetch_geometry(x, f)
-    assert net._prefetched[id(x)][4] is None
+    assert net._prefetched[id(x)].graph is None
     f.add_(1)
     want = fresh.forward(x, feats=f)
     got = net.forward(x, feats=f)

@@ -162,7 +162,7 @@ def test_small_balls_with_padding_and_an_empty_ball(hiplib, dev, pooling):
     moved = new_xyz + shift
     idx, cnt = tf_grouping.query_ball_point(0.15, 16, xyz, moved)
     assert int(cnt[1, 5]) == 0 and bool((cnt < 16).any())
-    geom = (fps_idx, moved, P.M.attach_inverse(idx, 600), cnt)
+    geom = P.SAGeometry(fps_idx, moved, P.M.attach_inverse(idx, 600), cnt)
     res = run(store, mod, xyz, pts, geom=geom)
     check_vs_ref(store, mod, xyz, pts, res, centre_shift=moved.double() - new_xyz.double())  # exact: the device's moved centres
 

@@ -169,16 +169,17 @@ def test_feats_are_checked_before_anything_runs():
 
 
 def test_prefetched_geometry_is_trusted_only_for_the_same_feature_tensor():
-    import types
-    net = types.SimpleNamespace()
+    net = VM.GeometryPrefetch(chain=lambda *a: None, side_stream=lambda: None, device=CPU, prop_npoint=256)
     x, f = torch.zeros(2, 8, 3), torch.zeros(2, 8, 2)
-    entry = lambda: {id(x): (x, x._version, {"sa1": 1}, {"sa1": 2}, None, 0, f, f._version)}
-    net._prefetched = entry()
-    assert VM.VoteNetHotPath._take_prefetched(net, x, f) == ({"sa1": 1}, {"sa1": 2})
-    net._prefetched = entry()
-    assert VM.VoteNetHotPath._take_prefetched(net, x, f.clone()) is None  # another tensor
-    net._prefetched = entry()
-    assert VM.VoteNetHotPath._take_prefetched(net, x, None) is None
-    net._prefetched = entry()
+
+    def entry():
+        net.pool[id(x)] = VM.PrefetchEntry(x, x._version, {"sa1": 1}, {"sa1": 2}, None, 0, f, f._version)
+    entry()
+    assert net.take(x, f) == ({"sa1": 1}, {"sa1": 2})
+    entry()
+    assert net.take(x, f.clone()) is None  # another tensor
+    entry()
+    assert net.take(x, None) is None
+    entry()
     f.add_(1)  # changed in place after the prefetch
-    assert VM.VoteNetHotPath._take_prefetched(net, x, f) is None
+    assert net.take(x, f) is None

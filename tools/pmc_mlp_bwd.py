@@ -16,7 +16,7 @@ import torch
 from votenet_amd import _lib as L_
 if os.environ.get("VARIANT"):  # tools/probe/build_variant.sh NAME ...: the library with one source rebuilt under other flags
     L_._LIB_PATH = os.path.join(R, "tools", "probe", "lib", "libvotenet_%s.so" % os.environ["VARIANT"])
-from votenet_amd import mlp as M, model as VM, synth
+from votenet_amd import mlp as M, model as VM, pointnet2 as P2, synth  # (P below is a matrix)
 
 mode = sys.argv[1] if len(sys.argv) > 1 else "alone"
 REP = int(os.environ.get("REP", "4"))
@@ -29,11 +29,13 @@ pos = lambda *s: (torch.rand(*s, generator=g) + 0.5).to(dev)
 
 # ---- sa1 (narrow) and sa2 (assembled) geometry of real room scenes
 geom1 = net.sa1.geometry(x, points=None)
-new1, idx1 = geom1[1], geom1[2]
-u8, mom = geom1[4:6] if len(geom1) >= 6 else M.narrow_rows(x, new1, None, idx1)
+new1 = geom1.new_xyz
+rows1_ = geom1.first if isinstance(geom1.first, P2.NarrowRows) else P2.NarrowRows(*M.narrow_rows(x, new1, None, geom1.idx))
+u8, mom = rows1_.u8, rows1_.mom
 geom2 = net.sa2.geometry(new1)
-new2, idx2, cnt2 = geom2[1], geom2[2], geom2[3]
-geo, cntv, mom2 = geom2[4:7] if len(geom2) >= 7 else M.assemble_rows(new1, new2, idx2, pts_cnt=cnt2)
+rows2_ = geom2.first if isinstance(geom2.first, P2.AssembledRows) else \
+    P2.AssembledRows(*M.assemble_rows(new1, geom2.new_xyz, geom2.idx, pts_cnt=geom2.pts_cnt))
+geo, cntv, mom2 = rows2_.geo, rows2_.cntv, rows2_.mom
 
 jobs = {}
 # sa2: 524288 x 128 -> 128

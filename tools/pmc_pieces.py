@@ -21,7 +21,7 @@ g = torch.Generator().manual_seed(1)
 gout = torch.randn(rec["b"], mod.npoint, mod.mlp[-1].cout, generator=g).to(dev)
 net.store.grad.zero_()
 torch.cuda.synchronize()
-half = geom[-1].resolve()
+half = geom.first.half.resolve()
 print("%s: %d balls, %d pieces = %d compact rows (%.0f %% of %d)" % (level, half.G, half.nh, half.rows, 100.0 * half.rows / (half.G * 64), half.G * 64))
 for _ in range(REP):
     t = []

@@ -13,6 +13,7 @@ the hot path can be driven, checked and timed end to end:
 """
 
 import math
+from typing import NamedTuple
 
 import torch
 
@@ -43,7 +44,8 @@ class GeometryGraph:
     generation.  The piece counts still reach the host through mapped pinned ints (the graph's own), the layouts are re-armed with the
     event that follows the replay."""
 
-    def __init__(self, net, x, side, feats=None):
+    def __init__(self, chain, x, side, feats=None):
+        """chain(x, g, ev, levels, feats): the net's geometry chain (VoteNetHotPath._geometry_chain)."""
         self.x = torch.empty_like(x)
         self.feats = torch.empty_like(feats) if feats is not None else None  # sa1's input features (a net with point_features): its narrow rows are built from them
         self.slots = torch.zeros(16, dtype=torch.int32).pin_memory()
@@ -52,9 +54,10 @@ class GeometryGraph:
         g = {}
         # thread_local: a process group's watchdog thread (RCCL, one rank per GPU) queries its events while this thread captures
         with M.layout_slots(self.slots), torch.cuda.graph(self.graph, stream=side, capture_error_mode="thread_local"):
-            net._geometry_chain(self.x, g, None, ("sa1", "sa2", "sa3", "sa4"), self.feats)
+            chain(self.x, g, None, ("sa1", "sa2", "sa3", "sa4"), self.feats)
         self.g = g
-        self.layouts = [t for v in g.values() if isinstance(v, tuple) for t in v if isinstance(t, M.HalfLayout)]
+        firsts = [v.first for v in g.values() if isinstance(v, P.SAGeometry) and v.first is not None]
+        self.layouts = [f.half for f in firsts if f.half is not None]
 
     def replay(self, x, side, feats=None):
         """On `side` (current): copy the points (and sa1's input features) in, run the chain -> (g, ev) as _geometry_chain leaves them."""
@@ -68,6 +71,124 @@ class GeometryGraph:
         for h in self.layouts:
             h.rearm(done)
         return self.g, {name: done for name in ("sa1", "sa2", "sa3", "sa4", "fp")}
+
+
+def _record_on_main(g, main):
+    """g: what a geometry chain left (SAGeometry / FPGeometry records, the proposal layer's FPS indices).  Tensors born on a side stream
+    are consumed on the main stream."""
+    for v in g.values():
+        for t in (v,) if isinstance(v, torch.Tensor) else v.tensors():
+            t.record_stream(main)
+
+
+class PrefetchEntry(NamedTuple):
+    """One prefetched batch: the tensors the chain saw (and their versions then), what it left (g, ev as _geometry_chain fills them),
+    the GeometryGraph that holds the result (None: launches) and that graph's generation at the hand-out."""
+    x: torch.Tensor
+    version: int
+    g: dict
+    ev: dict
+    graph: object
+    generation: int
+    feats: torch.Tensor = None
+    feats_version: int = 0
+
+
+class GeometryPrefetch:
+    """The prefetch state of one net (net._geometry): the pool of batches whose geometry is under way or done, the rings of
+    GeometryGraphs per input shape, the graph whose buffers the running pass reads, the two prefetch streams.
+    chain: the net's _geometry_chain; side_stream(): its geometry stream (the first of the two prefetch streams); prop_npoint: the
+    proposal layer's sample count (the chain runs its FPS: part of a ring's key)."""
+
+    def __init__(self, chain, side_stream, device, prop_npoint):
+        self.chain, self.side_stream, self.device, self.prop_npoint = chain, side_stream, device, prop_npoint
+        self.pool = {}           # id(x) -> PrefetchEntry, oldest first.  Cleared and mutated in place, NEVER rebound: the net's _prefetched is this dict
+        self.rings = {}          # (shape, configuration) -> dict(graphs=[GeometryGraph ...], turn, warm)
+        self.evictions = 0       # times a third shape / configuration threw the rings away
+        self.graphs_off = False  # too many of those: the chain is enqueued launch by launch from then on
+        self.current = None      # the GeometryGraph whose buffers serve the pass being enqueued (None: fresh tensors)
+        self.streams = None      # the two prefetch streams, used alternately; created on first use (a CPU-only net never gets there)
+        self.turn = 0
+
+    def prefetch(self, next_x, next_feats=None):
+        """VoteNetHotPath.prefetch_geometry (next_feats checked: None for a net without point features)."""
+        had = self.pool.get(id(next_x))
+        if had is not None and had.x is next_x and had.version == next_x._version and (
+                next_feats is None or (had.feats is next_feats and had.feats_version == next_feats._version)):
+            return
+        main = torch.cuda.current_stream()
+        if self.streams is None:
+            self.streams = [self.side_stream(), torch.cuda.Stream(device=self.device, priority=SIDE_PRIORITY)]
+        side = self.streams[self.turn]
+        self.turn ^= 1
+        gg = self.next_graph(next_x, side, next_feats)
+        g, ev = {}, {}
+        start = torch.cuda.Event()
+        start.record(main)  # next_x may have been produced on the main stream; a graph's buffers may still serve the step before
+        with torch.cuda.stream(side):
+            side.wait_event(start)
+            if gg is not None:
+                g, ev = gg.replay(next_x, side, next_feats)
+            else:
+                self.chain(next_x, g, ev, ("sa1", "sa2", "sa3", "sa4"), next_feats)
+        if gg is None:
+            _record_on_main(g, main)
+        while len(self.pool) >= (GEOMETRY_RING - 1 if gg is not None else 4):  # never picked up: drop the oldest
+            self.pool.pop(next(iter(self.pool)))
+        self.pool[id(next_x)] = PrefetchEntry(next_x, next_x._version, g, ev, gg, gg.generation if gg is not None else 0,
+                                              next_feats, next_feats._version if next_feats is not None else 0)
+
+    def next_graph(self, x, side, feats=None):
+        """The next graph of the ring for inputs shaped like x (captured on first use), or None when the chain is enqueued launch by
+        launch: graphs off, the deterministic mode (its inverse indices ride on tensors as attributes), a capture under way, per-launch
+        profiling events switched on."""
+        if not GEOMETRY_GRAPHS or M.DETERMINISTIC or self.graphs_off or torch.cuda.is_current_stream_capturing():
+            return None
+        if P.tf_sampling.PROFILE_EVENTS is not None or P.tf_grouping.PROFILE_EVENTS is not None:
+            return None  # HIP events around single launches of the chain are wanted (bench.py's roofline legs): they need the launches
+        key = (tuple(x.shape), x.dtype, P.HALF_GROUPS, P.ASSEMBLE_INLINE, self.prop_npoint) + ((tuple(feats.shape),) if feats is not None else ())
+        ring = self.rings.get(key)
+        if ring is None:
+            if len(self.rings) >= 2:  # another shape / configuration: the old graphs' buffers go
+                self.rings.clear()
+                self.evictions += 1
+                if self.evictions > GEOMETRY_MAX_EVICTIONS:  # shapes keep changing: every capture is a device synchronise
+                    import warnings
+                    warnings.warn("VoteNetHotPath: the input shape / configuration changed %d times: the prefetched geometry chain is "
+                                  "enqueued launch by launch from now on (model.GEOMETRY_GRAPHS)" % self.evictions)
+                    self.graphs_off = True
+                    return None
+            ring = self.rings[key] = dict(graphs=[], turn=0, warm=0)
+        if len(ring["graphs"]) < GEOMETRY_RING:
+            # the chain has run launch by launch before (sizes its scratch, loads its code objects): at least once per shape
+            if ring["warm"] < 1:
+                ring["warm"] += 1
+                return None
+            ring["graphs"].append(GeometryGraph(self.chain, x, side, *([feats] if feats is not None else [])))  # (without features: the three arguments it always took)
+            return ring["graphs"][-1]
+        gg = ring["graphs"][ring["turn"]]
+        ring["turn"] = (ring["turn"] + 1) % GEOMETRY_RING
+        if gg is self.current:  # its buffers serve the pass being enqueued (a lookahead beyond the ring)
+            return None
+        return gg
+
+    def take(self, x, feats=None):
+        """The (g, ev) prefetched for exactly this batch, or None: the point tensor AND the feature tensor must be the objects the
+        prefetch saw, unchanged since (_version) -- sa1's narrow rows were built from the features -- and the graph that holds the
+        result must not have served another batch.  Sets `current` to that graph (None otherwise)."""
+        pf = self.pool.pop(id(x), None)
+        self.current = None
+        if pf is not None and pf.x is x and pf.version == x._version and (pf.graph is None or pf.graph.generation == pf.generation) and \
+                pf.feats is feats and (feats is None or pf.feats_version == feats._version):
+            self.current = pf.graph
+            return pf.g, pf.ev
+        return None
+
+    def drop(self):
+        """Forget the captured graphs and what was prefetched on them."""
+        self.rings.clear()
+        self.pool.clear()
+        self.current = None
 
 
 GRAM_EARLY = ()          # levels whose Gram matrix is launched at the start of the levels' backward pass (see _grams_early): measured below
@@ -278,6 +399,8 @@ class VoteNetHotPath:
                                    mlp2=[128, 128, PROPOSAL_OUT])           # model.py:89-93
         s.materialize(seed)
         s.enable_split(SPLIT_BF16)  # forward() refreshes the images at its start, refresh_transposes() those of the copies
+        self._geometry = GeometryPrefetch(self._geometry_chain, lambda: self._side_stream(), device, self.proposal.npoint)
+        self._prefetched = self._geometry.pool  # (the benchmark's legs and the tools empty / refill the pool through this name)
 
     def _wgrad_side(self):
         """The weight-gradient stream; None with overlap_wgrad off: weight gradients then run on the chain's own stream."""
@@ -324,32 +447,21 @@ class VoteNetHotPath:
     def _geometry_chain(self, x, g, ev, levels, feats=None):
         """FPS / ball query of `levels`, the proposal layer's FPS (it samples the SEEDS, utils.py:42-43) and both three_nn on
         the current stream; an event per level so that a consumer waits only for what it needs."""
-        xyz = x if "sa1" in levels else g["sa1"][1]
+        xyz = x if "sa1" in levels else g["sa1"].new_xyz
         for name in levels:
             # sa1's input features are the coordinates (model.py:39), or the caller's feats (point_features)
             g[name] = getattr(self, name).geometry(xyz, points=(feats if feats is not None else x) if name == "sa1" else None)
-            xyz = g[name][1]
+            xyz = g[name].new_xyz
             if name == "sa2":  # seeds = l2_xyz: the proposal layer's FPS can start as soon as they exist
                 g["prop_fps"] = P.tf_sampling.farthest_point_sample(self.proposal.npoint, xyz)
             if ev is not None:  # None: the chain is being captured (GeometryGraph) -- one event after the replay stands for all
                 ev[name] = torch.cuda.Event()
                 ev[name].record()
-        g["fp1"] = P.FPModule.geometry(g["sa3"][1], g["sa4"][1])
-        g["fp2"] = P.FPModule.geometry(g["sa2"][1], g["sa3"][1])
+        g["fp1"] = P.FPModule.geometry(g["sa3"].new_xyz, g["sa4"].new_xyz)
+        g["fp2"] = P.FPModule.geometry(g["sa2"].new_xyz, g["sa3"].new_xyz)
         if ev is not None:
             ev["fp"] = torch.cuda.Event()
             ev["fp"].record()
-
-    @staticmethod
-    def _record_on_main(g, main):
-        for v in g.values():  # tensors born on the side stream are consumed on the main stream
-            for t in (v if isinstance(v, tuple) else (v,)):
-                for u in getattr(t, "tensors", tuple)() if not isinstance(t, torch.Tensor) else ():  # mlp.HalfLayout
-                    u.record_stream(main)
-                if isinstance(t, torch.Tensor):
-                    t.record_stream(main)
-                    for u in getattr(t, "_inv", None) or ():  # the grouping's inverse index rides on idx (mlp.attach_inverse)
-                        u.record_stream(main)
 
     def geometry_ahead(self, x, feats=None):
         """Every FPS / ball query / three_nn of the backbone depends on coordinates only, never on features.
@@ -365,7 +477,7 @@ class VoteNetHotPath:
         with torch.cuda.stream(side):
             side.wait_event(start)
             self._geometry_chain(x, g, ev, ("sa2", "sa3", "sa4"))
-        self._record_on_main(g, main)
+        _record_on_main(g, main)
         return g, ev
 
     def prefetch_geometry(self, next_x, next_feats=None):
@@ -378,83 +490,8 @@ class VoteNetHotPath:
         further batches have been prefetched (a training step consumes its tape before the next one starts).  Several batches may be in flight (two prefetch streams, used alternately): a forward-only pass is shorter
         than one geometry chain, so it wants a lookahead of two.  The input pipeline knows the next batches ahead (the
         reference prefetches them through QueueInput, run.py:121-122)."""
-        pool = self.__dict__.setdefault("_prefetched", {})
         pts = self._sa1_points(next_x, next_feats, "prefetch_geometry")
-        next_feats = pts if pts is not next_x else None  # (sa1's narrow rows and their moments are built ahead from the features)
-        had = pool.get(id(next_x))
-        if had is not None and had[0] is next_x and had[1] == next_x._version and (
-                next_feats is None or (had[6] is next_feats and had[7] == next_feats._version)):
-            return
-        main = torch.cuda.current_stream()
-        if getattr(self, "_pf_streams", None) is None:
-            self._pf_streams = [self._side_stream(), torch.cuda.Stream(device=self.device, priority=SIDE_PRIORITY)]
-            self._pf_turn = 0
-        side = self._pf_streams[self._pf_turn]
-        self._pf_turn ^= 1
-        gg = self._geometry_graph(next_x, side, next_feats)
-        g, ev = {}, {}
-        start = torch.cuda.Event()
-        start.record(main)  # next_x may have been produced on the main stream; a graph's buffers may still serve the step before
-        with torch.cuda.stream(side):
-            side.wait_event(start)
-            if gg is not None:
-                g, ev = gg.replay(next_x, side, next_feats)
-            else:
-                self._geometry_chain(next_x, g, ev, ("sa1", "sa2", "sa3", "sa4"), next_feats)
-        if gg is None:
-            self._record_on_main(g, main)
-        while len(pool) >= (GEOMETRY_RING - 1 if gg is not None else 4):  # never picked up: drop the oldest
-            pool.pop(next(iter(pool)))
-        pool[id(next_x)] = (next_x, next_x._version, g, ev, gg, gg.generation if gg is not None else 0,
-                            next_feats, next_feats._version if next_feats is not None else 0)
-
-    def _geometry_graph(self, x, side, feats=None):
-        """The next graph of the ring for inputs shaped like x (captured on first use), or None when the chain is enqueued launch by
-        launch: graphs off, the deterministic mode (its inverse indices ride on tensors as attributes), a capture under way, per-launch
-        profiling events switched on."""
-        if not GEOMETRY_GRAPHS or M.DETERMINISTIC or getattr(self, "_geometry_graphs_off", False) or torch.cuda.is_current_stream_capturing():
-            return None
-        if P.tf_sampling.PROFILE_EVENTS is not None or P.tf_grouping.PROFILE_EVENTS is not None:
-            return None  # HIP events around single launches of the chain are wanted (bench.py's roofline legs): they need the launches
-        key = (tuple(x.shape), x.dtype, P.HALF_GROUPS, P.ASSEMBLE_INLINE, self.proposal.npoint) + ((tuple(feats.shape),) if feats is not None else ())
-        rings = self.__dict__.setdefault("_geometry_rings", {})
-        ring = rings.get(key)
-        if ring is None:
-            if len(rings) >= 2:  # another shape / configuration: the old graphs' buffers go
-                rings.clear()
-                self._geometry_evictions = getattr(self, "_geometry_evictions", 0) + 1
-                if self._geometry_evictions > GEOMETRY_MAX_EVICTIONS:  # shapes keep changing: every capture is a device synchronise
-                    import warnings
-                    warnings.warn("VoteNetHotPath: the input shape / configuration changed %d times: the prefetched geometry chain is "
-                                  "enqueued launch by launch from now on (model.GEOMETRY_GRAPHS)" % self._geometry_evictions)
-                    self._geometry_graphs_off = True
-                    return None
-            ring = rings[key] = dict(graphs=[], turn=0)
-        if len(ring["graphs"]) < GEOMETRY_RING:
-            # the chain has run launch by launch before (sizes its scratch, loads its code objects): at least once per shape
-            if ring.setdefault("warm", 0) < 1:
-                ring["warm"] += 1
-                return None
-            ring["graphs"].append(GeometryGraph(self, x, side, *([feats] if feats is not None else [])))  # (without features: the three arguments it always took)
-            return ring["graphs"][-1]
-        gg = ring["graphs"][ring["turn"]]
-        ring["turn"] = (ring["turn"] + 1) % GEOMETRY_RING
-        if gg is getattr(self, "_geometry_current", None):  # its buffers serve the pass being enqueued (a lookahead beyond the ring)
-            return None
-        return gg
-
-    def _take_prefetched(self, x, feats=None):
-        """The geometry prefetched for exactly this batch, or None: the point tensor AND the feature tensor must be the objects the
-        prefetch saw, unchanged since (_version) -- sa1's narrow rows were built from the features -- and the graph that holds the
-        result must not have served another batch."""
-        pf = self.__dict__.setdefault("_prefetched", {}).pop(id(x), None)
-        self._geometry_current = None
-        pf_feats, pf_fver = (pf[6], pf[7]) if pf is not None and len(pf) > 6 else (None, 0)
-        if pf is not None and pf[0] is x and pf[1] == x._version and (pf[4] is None or pf[4].generation == pf[5]) and \
-                pf_feats is feats and (feats is None or pf_fver == feats._version):
-            self._geometry_current = pf[4]
-            return pf[2], pf[3]
-        return None
+        self._geometry.prefetch(next_x, pts if pts is not next_x else None)  # (sa1's narrow rows and their moments are built ahead from the features)
 
     def backbone(self, x, tape=None, overlap=True, next_x=None, feats=None, next_feats=None):
         """model.py:35-50.  x (B,n,3) -> seeds_xyz (B,1024,3), seeds_points (B,1024,256)."""
@@ -470,7 +507,7 @@ class VoteNetHotPath:
         main = torch.cuda.current_stream()
         pts = self._sa1_points(x, feats)
         feats = pts if pts is not x else None
-        pf = self._take_prefetched(x, feats)
+        pf = self._geometry.take(x, feats)
         if pf is not None:
             g, ev = pf
             main.wait_event(ev["sa1"])
@@ -483,7 +520,6 @@ class VoteNetHotPath:
             for nx, nf in nexts:
                 self.prefetch_geometry(nx, nf)
         overlap = overlap or pf is not None
-        self._prop_fps = g.get("prop_fps")
         def launch_prefetch(after):
             if PREFETCH_AFTER == after:
                 for nx, nf in nexts:
@@ -524,7 +560,7 @@ class VoteNetHotPath:
         M.row_segments(rows, segs)
         x = xp[:, :259]
         recs = []
-        off, _ = P.mlp_chain_forward(self.voting, rows, ("dense", x, xp) if pad > 259 else ("dense", x), recs)
+        off, _ = P.mlp_chain_forward(self.voting, rows, P.DenseInput(x, xp if pad > 259 else None), recs)
         v_xyz = torch.empty((b, n, 3), dtype=torch.float32, device=x.device)
         v_p = torch.empty((b, n, 256), dtype=torch.float32, device=x.device)
         M.row_segments(rows, [(v_xyz.view(rows, 3), x[:, :3], off[:, :3]), (v_p.view(rows, 256), x[:, 3:], off[:, 3:])])
@@ -532,11 +568,12 @@ class VoteNetHotPath:
             tape.append(dict(op="vote", recs=recs, b=b, n=n))
         return v_xyz, v_p
 
-    def propose(self, votes_xyz, votes_points, seeds_xyz, tape=None):
-        """model.py:89-93: SA on votes with FPS on the seeds -> proposals_xyz (B,256,3), output (B,256,79)."""
+    def propose(self, votes_xyz, votes_points, seeds_xyz, tape=None, prop_fps=None):
+        """model.py:89-93: SA on votes with FPS on the seeds -> proposals_xyz (B,256,3), output (B,256,79).
+        prop_fps: the FPS indices of THESE seeds when they were computed ahead (side stream); None: the seeds are sampled here."""
         geom = None
-        if getattr(self, "_prop_fps", None) is not None:  # FPS on the seeds was computed ahead (side stream)
-            geom = self.proposal.geometry(votes_xyz, fps_idx=self._prop_fps, ahead=False)  # the votes exist only now
+        if prop_fps is not None:
+            geom = self.proposal.geometry(votes_xyz, fps_idx=prop_fps, ahead=False)  # the votes exist only now
         p_xyz, p_out, _ = self.proposal.forward(votes_xyz, votes_points, sample_xyz=seeds_xyz, tape=tape, geom=geom)
         return p_xyz, p_out
 
@@ -551,7 +588,7 @@ class VoteNetHotPath:
             lv, g = self.backbone_levels(x, tape, next_x=next_x, feats=feats, next_feats=next_feats)
             self._stamp_tape(tape)
             out = self._head_forward(lv, g.get("fp1"), g.get("fp2"), g.get("prop_fps"), tape,
-                                     copy_seeds=getattr(self, "_geometry_current", None) is not None)
+                                     copy_seeds=self._geometry.current is not None)
         finally:
             M.arena_end()
         return out
@@ -559,7 +596,7 @@ class VoteNetHotPath:
     def _stamp_tape(self, tape):
         """The geometry of this pass lives in a GeometryGraph's fixed buffers, which a later replay overwrites: the tape is stamped with
         (graph, generation) so that backward() refuses a tape whose geometry is gone."""
-        gg = getattr(self, "_geometry_current", None)
+        gg = self._geometry.current
         if gg is not None and tape:
             tape[0]["geometry_stamp"] = (gg, gg.generation)
 
@@ -572,8 +609,7 @@ class VoteNetHotPath:
         seeds_xyz = lv["l2_xyz"]
         seeds_out = torch.empty_like(seeds_xyz) if copy_seeds else None
         v_xyz, v_p = self.vote(seeds_xyz, seeds_p, tape, seeds_copy=seeds_out)
-        self._prop_fps = prop_fps
-        p_xyz, p_out = self.propose(v_xyz, v_p, seeds_xyz, tape)
+        p_xyz, p_out = self.propose(v_xyz, v_p, seeds_xyz, tape, prop_fps)
         return dict(seeds_xyz=seeds_out if seeds_out is not None else seeds_xyz, seeds_points=seeds_p, votes_xyz=v_xyz, votes_points=v_p,
                     proposals_xyz=p_xyz, proposals_output=p_out)
 
@@ -850,8 +886,8 @@ class VoteNetHotPath:
         not among them: the loss runs as launches between two segments)."""
         ins = dict(lv)
         for name in ("fp1", "fp2"):
-            idx, w = g[name]
-            ins[name + "_idx"], ins[name + "_w"] = idx, w
+            idx = g[name].idx
+            ins[name + "_idx"], ins[name + "_w"] = idx, g[name].weight
             inv = getattr(idx, "_inv", None)
             if inv is not None:
                 ins[name + "_inv0"], ins[name + "_inv1"] = inv
@@ -868,7 +904,7 @@ class VoteNetHotPath:
             idx = I[name + "_idx"]
             if name + "_inv0" in I:
                 idx._inv = (I[name + "_inv0"], I[name + "_inv1"])
-            return idx, I[name + "_w"]
+            return P.FPGeometry(idx, I[name + "_w"])
         tail = []
         lv = {k: I[k] for k in ("l2_xyz", "l2_p", "l3_xyz", "l3_p", "l4_xyz", "l4_p")}
         out = self._head_forward(lv, geom("fp1"), geom("fp2"), I["prop_fps"], tail, copy_seeds=copy_seeds)
@@ -915,7 +951,7 @@ class VoteNetHotPath:
                 # (launch by launch on the live inputs: seeds_xyz would alias sa2's centres inside a GeometryGraph buffer that a later
                 # prefetch overwrites -- handed out as a copy, as forward() does)
                 out, self.last_losses, grads = self._stretch_body(ins, tape, self._wgrad_side(), gt=gt,
-                                                                  copy_seeds=getattr(self, "_geometry_current", None) is not None)
+                                                                  copy_seeds=self._geometry.current is not None)
                 self._stretch_demand[dkey] = (a.off - off0, a.want32 - want0)
                 self._backward_levels_pass(tape, grads)
                 return out
@@ -985,9 +1021,7 @@ class VoteNetHotPath:
         (library debug switches, hand-edited module state)."""
         self.__dict__.pop("_stretch_graphs", None)
         self.__dict__.pop("_stretch_demand", None)
-        self.__dict__.pop("_geometry_rings", None)
-        self.__dict__.setdefault("_prefetched", {}).clear()
-        self._geometry_current = None
+        self._geometry.drop()
 
     # ---- training summaries on the device (monitors.py): off unless asked for --------------------------------------------------
     monitors = None          # a monitors.Monitors while enable_monitors is in force

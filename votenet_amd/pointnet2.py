@@ -18,6 +18,7 @@ single RCCL all-reduce over one contiguous gradient buffer per step.
 """
 import math
 import threading
+from typing import NamedTuple
 
 import torch
 
@@ -383,8 +384,197 @@ class frozen_bn:
         return False
 
 
+# ---- what travels between geometry(), the prefetch ring, forward() and mlp_chain_forward: named records, told apart by type
+def _with_inverse(idx):
+    """idx and, where it rides on it, the grouping's inverse index (mlp.attach_inverse)."""
+    yield idx
+    yield from getattr(idx, "_inv", None) or ()
+
+
+class NarrowRows(NamedTuple):
+    """First-layer rows of a narrow module built ahead (csrc/narrow.hip).  half: the unresolved mlp.HalfLayout whose u8 holds the
+    compact rows (u8 is then the whole buffer they were written into), or None: the full layout."""
+    u8: torch.Tensor
+    mom: torch.Tensor
+    half: object = None
+
+    def tensors(self):
+        yield from (self.u8, self.mom)
+        if self.half is not None:
+            yield from self.half.tensors()
+
+
+class AssembledRows(NamedTuple):
+    """geo records and per-point sums of an assembled first layer built ahead (csrc/assemble.hip); half as in NarrowRows (its geo)."""
+    geo: torch.Tensor
+    cntv: torch.Tensor
+    mom: torch.Tensor
+    half: object = None
+
+    def tensors(self):
+        yield from (self.geo, self.cntv, self.mom)
+        if self.half is not None:
+            yield from self.half.tensors()
+
+
+class SAGeometry(NamedTuple):
+    """The coordinate-only part of one SA level (SAModule.geometry).  first: None -- the first layer's rows are built in place by
+    forward() --, NarrowRows or AssembledRows."""
+    fps_idx: torch.Tensor
+    new_xyz: torch.Tensor
+    idx: torch.Tensor
+    pts_cnt: torch.Tensor
+    first: object = None
+
+    def tensors(self):
+        """Every device tensor the record holds (a consumer on another stream tags them with record_stream)."""
+        yield from (self.fps_idx, self.new_xyz)
+        yield from _with_inverse(self.idx)
+        yield self.pts_cnt
+        if self.first is not None:
+            yield from self.first.tensors()
+
+
+class FPGeometry(NamedTuple):
+    """three_nn taps and their inverse-distance weights (FPModule.geometry)."""
+    idx: torch.Tensor
+    weight: torch.Tensor
+
+    def tensors(self):
+        yield from _with_inverse(self.idx)
+        yield self.weight
+
+
+class DenseInput(NamedTuple):
+    """Chain input: rows x (rows, cin).  padded: [x | 0] at the first layer's padded width, when the caller built it (x = padded[:, :cin])."""
+    x: torch.Tensor
+    padded: torch.Tensor = None
+
+
+class GatherInput(NamedTuple):
+    """Chain input: the sample_and_group concat [xyz[idx] - new_xyz | feat[idx]], never materialised."""
+    xyz: torch.Tensor
+    new_xyz: torch.Tensor
+    feat: torch.Tensor
+    idx: torch.Tensor
+
+
+class NarrowInput(NamedTuple):
+    """Chain input: the narrow form's 8 floats per row.  half: the resolved mlp.HalfLayout when u8 (and every row tensor of the chain)
+    holds compact rows, or None."""
+    u8: torch.Tensor
+    mom: torch.Tensor
+    half: object = None
+
+
+class AssembledInput(NamedTuple):
+    """Chain input: a first layer assembled inside its consumers from geo and the per-point GEMM.  half: as in NarrowInput (geo)."""
+    xyz: torch.Tensor
+    new_xyz: torch.Tensor
+    feat: torch.Tensor
+    idx: torch.Tensor
+    geo: torch.Tensor
+    cntv: torch.Tensor
+    mom: torch.Tensor
+    half: object = None
+
+
+def _close_layer(L, rows, rec, z, st, tape, pool=None):
+    """Behind a layer's launch: its BatchNorm as an mlp.PendingBN on the raw sums st (inference mode: the frozen table's entry; a
+    plain layer: None), the layer's record completed and appended to the tape.  -> that BatchNorm."""
+    if L.bn and _FROZEN.table is not None:
+        pend = _FROZEN.table[L.name]  # moving averages: the batch sums of this launch are ignored
+        rec.update(scale=pend.scale, shift=pend.shift)
+    elif L.bn:
+        blk = L.store._bn_views.get(L.name)
+        pend = M.PendingBN(st, L.p("gamma"), L.p("beta"), rows, out=blk)
+        rec.update(scale=pend.scale, shift=pend.shift, mean=pend.mean, var=pend.var, bn_out=pend.out)
+        if blk is not None:
+            # the block is PERSISTENT (one per layer, rewritten by every training-mode forward pass of the net): the record
+            # remembers which pass wrote it, and whoever reads it later through this record checks that no other pass has since
+            rec["bn_pass"] = L.store.bn_block_written(L.name)
+    else:
+        pend = None
+    rec.update(z=z, rows=rows, pool=pool)
+    tape.append(rec)
+    return pend
+
+
+# The first layer(s) of a chain per form of its input: (layers, rows, first, tape, keep_z) -> (z, pend, half, layers done).
+def _first_dense(layers, rows, first, tape, keep_z):
+    L = layers[0]
+    w, b = L.p("W"), L.p("b")
+    if L.cin_pad and PAD_RAGGED_IN and first.x.is_cuda:
+        # [x | 0] against [W ; 0]
+        xp = first.padded if first.padded is not None else torch.nn.functional.pad(first.x, (0, L.cin_pad - L.cin))
+        z, st = M.linear_dense(xp, L.store.padded_rows(L.name + "/W", L.cin_pad), b, want_stats=L.bn)
+        rec = dict(layer=L, kind="dense", x=xp, in_scale=None, in_shift=None, in_relu=False, cin_padded=True)
+    else:
+        z, st = M.linear_dense(first.x, w, b, want_stats=L.bn)
+        rec = dict(layer=L, kind="dense", x=first.x, in_scale=None, in_shift=None, in_relu=False)
+    return z, _close_layer(L, rows, rec, z, st, tape), None, 1
+
+
+def _first_gather(layers, rows, first, tape, keep_z):
+    # conv over the sample_and_group concat [xyz[idx]-new_xyz | feat[idx]] (utils.py:50-57,125-127).  A gather
+    # commutes with a per-point linear map, so the feature block is ONE GEMM over the b*n points (P = feat W[3:])
+    # and the layer output is assembled per grouped row: z = P[idx] + dxyz W[0:3] + bias (votenet_group_linear).
+    L = layers[0]
+    w, b = L.p("W"), L.p("b")
+    xyz, new_xyz, feat, idx = first.xyz, first.new_xyz, first.feat, first.idx
+    co = w.shape[1]
+    if feat is not None and PRE_LINEAR and co % 4 == 0 and co <= 1024 and 256 % (co // 4) == 0:
+        bb, nn, cc = feat.shape
+        P, _ = M.linear_dense(feat.reshape(bb * nn, cc), w[3:], None, want_stats=False)
+        z, st = M.group_linear(xyz, new_xyz, idx, P, w[:3], b, want_stats=L.bn)
+    else:
+        z, st = M.linear_gather(xyz, new_xyz, feat, idx, w, b, want_stats=L.bn)
+    rec = dict(layer=L, kind="gather", xyz=xyz, new_xyz=new_xyz, feat=feat, idx=idx)
+    return z, _close_layer(L, rows, rec, z, st, tape), None, 1
+
+
+def _first_narrow(layers, rows, first, tape, keep_z):
+    # narrow first layer (csrc/narrow.hip): no kernel writes z0 = u8 W0 + b0; its BatchNorm statistics follow from the moments
+    # of u8 and the next layer's GEMM rebuilds it in its operand loader
+    L0, L = layers[:2]
+    u8, mom, half = first.u8, first.mom, first.half
+    w0, b0 = L0.p("W"), L0.p("b")
+    st = M.narrow_stats(rows, mom, w0, b0) if (L0.bn and _FROZEN.table is None) else None
+    pend = _close_layer(L0, rows, dict(layer=L0, kind="narrow", u8=u8, mom=mom, half=half), None, st, tape)
+    # training on the piece layout: the GEMM also leaves the first layer's ReLU mask (2 bytes per row and 16 channels) for the
+    # backward pass, whose input-gradient epilogue then needs no rebuild of z0 (mlp.NARROW_MASK)
+    want_mask = bool(M.NARROW_MASK and keep_z and half is not None and L0.relu and _FROZEN.table is None and M.COEF_TAIL
+                     and M.narrow_mask_supported(u8.shape[0], L0.cout))
+    res = M.narrow_linear(u8, w0, b0, L.p("W"), L.p("b"), pend, L0.relu, want_stats=L.bn, half=half, want_mask=want_mask)
+    z, st = res[:2]
+    rec = dict(layer=L, kind="dense", x=None, narrow=True, in_scale=pend.scale if pend is not None else None,
+               in_shift=pend.shift if pend is not None else None, in_relu=L0.relu, half=half, mask0=res[2] if want_mask else None)
+    return z, _close_layer(L, rows, rec, z, st, tape), half, 2
+
+
+def _first_assembled(layers, rows, first, tape, keep_z):
+    # first layer assembled inside its consumers (csrc/assemble.hip): the per-point GEMM P = feat W[3:] + b is all that runs for it;
+    # the BatchNorm statistics of z0 = P[idx] + dxyz W[0:3] come from one pass over the points, the next layer's GEMM rebuilds z0
+    L0, L = layers[:2]
+    feat, geo, half = first.feat, first.geo, first.half
+    w0, b0 = L0.p("W"), L0.p("b")
+    bb, nn, cc = feat.shape
+    P, _ = M.linear_dense(feat.reshape(bb * nn, cc), w0[3:], b0, want_stats=False)
+    st = M.assemble_stats(P, first.cntv, w0[:3], first.mom) if (L0.bn and _FROZEN.table is None) else None
+    rec = dict(layer=L0, kind="assembled", xyz=first.xyz, new_xyz=first.new_xyz, feat=feat, idx=first.idx, geo=geo, P=P, wx=w0[:3],
+               half=half, cntv=first.cntv, mom=first.mom)
+    pend = _close_layer(L0, rows, rec, None, st, tape)
+    z, st = M.assembled_linear(geo, P, w0[:3], L.p("W"), L.p("b"), pend, L0.relu, want_stats=L.bn, half=half)
+    rec = dict(layer=L, kind="dense", x=None, assembled=True, in_scale=pend.scale if pend is not None else None,
+               in_shift=pend.shift if pend is not None else None, in_relu=L0.relu, half=half)
+    return z, _close_layer(L, rows, rec, z, st, tape), half, 2
+
+
+_FIRST_LAYERS = {DenseInput: _first_dense, GatherInput: _first_gather, NarrowInput: _first_narrow, AssembledInput: _first_assembled}
+
+
 def mlp_chain_forward(layers, rows, first, tape, pool_k=0, keep_z=True):
-    """Run a chain of layers over `rows` rows.  first = ('gather', xyz, new_xyz, feat, idx) or ('dense', x).
+    """Run a chain of layers over `rows` rows.  first: the chain's input, a DenseInput, GatherInput, NarrowInput or AssembledInput.
     Returns (z_last, pend): the last layer's RAW output and its BatchNorm as an mlp.PendingBN (None for a plain last
     layer) -- nobody has launched a finalize: every BatchNorm is derived from the raw sums in the prologue of the kernel
     that consumes it (the next GEMM inside the chain; the pooling / activation kernel of the caller for the last layer).
@@ -392,81 +582,25 @@ def mlp_chain_forward(layers, rows, first, tape, pool_k=0, keep_z=True):
     pool_k > 0: the chain is followed by a max over groups of pool_k rows (utils.py:132); where the shape allows, the last
     GEMM's epilogue starts the pool (raw max / min per group) and the last record carries 'pool' for bn_pool_finalize;
     keep_z=False then skips the store of the last layer's z altogether (nothing downstream reads it in inference)."""
-    z = None
-    pend = None  # BatchNorm of z whose finalize rides in the prologue of z's consumer (mlp.PendingBN)
-    prev_relu = False
-    for i, L in enumerate(layers):
+    # pend: BatchNorm of z whose finalize rides in the prologue of z's consumer (mlp.PendingBN); half: the chain's piece layout
+    z, pend, half, done = _FIRST_LAYERS[type(first)](layers, rows, first, tape, keep_z)
+    for i in range(done, len(layers)):
+        L, prev_relu = layers[i], layers[i - 1].relu
         w, b = L.p("W"), L.p("b")
         pool = None
         sc = pend.scale if pend is not None else None  # views: filled when the consumer below has run
         sh = pend.shift if pend is not None else None
-        if i == 0 and first[0] == "narrow":
-            # narrow first layer (csrc/narrow.hip): no kernel writes z0 = u8 W0 + b0; its BatchNorm statistics follow from the moments
-            # of u8 and the next layer's GEMM rebuilds it in its operand loader
-            _, u8, mom = first[:3]
-            half = first[3] if len(first) > 3 else None  # mlp.HalfLayout: u8 (and every row tensor of the chain) holds compact rows
-            zn = None
-            st = M.narrow_stats(rows, mom, w, b) if (L.bn and _FROZEN.table is None) else None
-            rec = dict(layer=L, kind="narrow", u8=u8, mom=mom, half=half)
-        elif i == 0 and first[0] == "assembled":
-            # first layer assembled inside its consumers (csrc/assemble.hip): the per-point GEMM P = feat W[3:] + b is all that runs here;
-            # the BatchNorm statistics of z0 = P[idx] + dxyz W[0:3] come from one pass over the points
-            _, xyz, new_xyz, feat, idx, geo, cntv, mom = first[:8]
-            half = first[8] if len(first) > 8 else None  # mlp.HalfLayout: geo (and every row tensor of the chain) holds compact rows
-            bb, nn, cc = feat.shape
-            P, _ = M.linear_dense(feat.reshape(bb * nn, cc), w[3:], b, want_stats=False)
-            zn = None
-            st = M.assemble_stats(P, cntv, w[:3], mom) if (L.bn and _FROZEN.table is None) else None
-            rec = dict(layer=L, kind="assembled", xyz=xyz, new_xyz=new_xyz, feat=feat, idx=idx, geo=geo, P=P, wx=w[:3], half=half,
-                       cntv=cntv, mom=mom)
-        elif i == 1 and first[0] == "assembled":
-            r0 = tape[-1]
-            zn, st = M.assembled_linear(r0["geo"], r0["P"], r0["wx"], w, b, pend, prev_relu, want_stats=L.bn, half=r0["half"])
-            rec = dict(layer=L, kind="dense", x=None, assembled=True, in_scale=sc, in_shift=sh, in_relu=prev_relu, half=r0["half"])
-        elif i == 1 and first[0] == "narrow":
-            half = tape[-1]["half"]
-            # training on the piece layout: the GEMM also leaves the first layer's ReLU mask (2 bytes per row and 16 channels) for the
-            # backward pass, whose input-gradient epilogue then needs no rebuild of z0 (mlp.NARROW_MASK)
-            want_mask = bool(M.NARROW_MASK and keep_z and half is not None and prev_relu and _FROZEN.table is None and M.COEF_TAIL
-                             and M.narrow_mask_supported(first[1].shape[0], layers[0].cout))
-            res = M.narrow_linear(first[1], layers[0].p("W"), layers[0].p("b"), w, b, pend, prev_relu, want_stats=L.bn, half=half,
-                                  want_mask=want_mask)
-            zn, st = res[0], res[1]
-            rec = dict(layer=L, kind="dense", x=None, narrow=True, in_scale=sc, in_shift=sh, in_relu=prev_relu, half=half,
-                       mask0=res[2] if want_mask else None)
-        elif i == 0 and first[0] == "gather":
-            # conv over the sample_and_group concat [xyz[idx]-new_xyz | feat[idx]] (utils.py:50-57,125-127).  A gather
-            # commutes with a per-point linear map, so the feature block is ONE GEMM over the b*n points (P = feat W[3:])
-            # and the layer output is assembled per grouped row: z = P[idx] + dxyz W[0:3] + bias (votenet_group_linear).
-            _, xyz, new_xyz, feat, idx = first
-            co = w.shape[1]
-            if feat is not None and PRE_LINEAR and co % 4 == 0 and co <= 1024 and 256 % (co // 4) == 0:
-                bb, nn, cc = feat.shape
-                P, _ = M.linear_dense(feat.reshape(bb * nn, cc), w[3:], None, want_stats=False)
-                zn, st = M.group_linear(xyz, new_xyz, idx, P, w[:3], b, want_stats=L.bn)
-            else:
-                zn, st = M.linear_gather(xyz, new_xyz, feat, idx, w, b, want_stats=L.bn)
-            rec = dict(layer=L, kind="gather", xyz=xyz, new_xyz=new_xyz, feat=feat, idx=idx)
-        elif i == 0 and L.cin_pad and PAD_RAGGED_IN and first[1].is_cuda:
-            # [x | 0] against [W ; 0]; first = ("dense", x, xp): the caller built the padded rows itself (x = xp[:, :cin])
-            xp = first[2] if len(first) > 2 else torch.nn.functional.pad(first[1], (0, L.cin_pad - L.cin))
-            zn, st = M.linear_dense(xp, L.store.padded_rows(L.name + "/W", L.cin_pad), b, want_stats=L.bn)
-            rec = dict(layer=L, kind="dense", x=xp, in_scale=None, in_shift=None, in_relu=False, cin_padded=True)
-        elif i == 0:
-            zn, st = M.linear_dense(first[1], w, b, want_stats=L.bn)
-            rec = dict(layer=L, kind="dense", x=first[1], in_scale=None, in_shift=None, in_relu=False)
-        elif pool_k and i == len(layers) - 1 and L.bn and POOL_IN_EPILOGUE and \
+        if pool_k and i == len(layers) - 1 and L.bn and POOL_IN_EPILOGUE and \
                 M.linear_pool_supported(rows, w.shape[0], w.shape[1], pool_k):
             # training does not store z of this layer either when its backward runs in Gram form (it never reads z)
             gram_form = POOL_GRAM_BACKWARD and pend is not None and M.pool_backward_supported(w.shape[0], w.shape[1], pool_k)
-            half = tape[0].get("half") if first[0] in ("assembled", "narrow") else None
             if half is not None and not (gram_form or not keep_z):
                 raise M.L.VotenetError("piece layout: the pooled layer's backward must be in Gram form")
             zn, st, pool = M.linear_dense_pool(z, w, pool_k, b, None, None, prev_relu, keep_z=keep_z and not gram_form, in_bn=pend, half=half,
                                                gamma=L.p("gamma") if half is not None else None)
             rec = dict(layer=L, kind="dense", x=z, in_scale=sc, in_shift=sh, in_relu=prev_relu, gram_form=gram_form,
                        in_affine=pend.out if pend is not None else None, cout=w.shape[1], half=half)
-        elif L.cout_pad and i > 0:
+        elif L.cout_pad:
             # ragged plain layer on zero-padded copies of W and b: the fast GEMM, output (rows, cout_pad), the layer's z = [:, :cout]
             zp, st = M.linear_dense(z, L.store.padded(L.name + "/W", L.cout_pad), L.store.padded(L.name + "/b", L.cout_pad), None, None,
                                     prev_relu, want_stats=False, in_bn=pend)
@@ -475,22 +609,8 @@ def mlp_chain_forward(layers, rows, first, tape, pool_k=0, keep_z=True):
         else:
             zn, st = M.linear_dense(z, w, b, None, None, prev_relu, want_stats=L.bn, in_bn=pend)
             rec = dict(layer=L, kind="dense", x=z, in_scale=sc, in_shift=sh, in_relu=prev_relu)
-        if L.bn and _FROZEN.table is not None:
-            pend = _FROZEN.table[L.name]  # moving averages: the batch sums of this launch are ignored
-            rec.update(scale=pend.scale, shift=pend.shift)
-        elif L.bn:
-            blk = L.store._bn_views.get(L.name)
-            pend = M.PendingBN(st, L.p("gamma"), L.p("beta"), rows, out=blk)
-            rec.update(scale=pend.scale, shift=pend.shift, mean=pend.mean, var=pend.var, bn_out=pend.out)
-            if blk is not None:
-                # the block is PERSISTENT (one per layer, rewritten by every training-mode forward pass of the net): the record
-                # remembers which pass wrote it, and whoever reads it later through this record checks that no other pass has since
-                rec["bn_pass"] = L.store.bn_block_written(L.name)
-        else:
-            pend = None
-        rec.update(z=zn, rows=rows, pool=pool)
-        tape.append(rec)
-        z, prev_relu = zn, L.relu
+        pend = _close_layer(L, rows, rec, zn, st, tape, pool)
+        z = zn
     return z, pend
 
 
@@ -897,55 +1017,52 @@ class SAModule:
         return bool(self.narrow(b * self.npoint * 64) or (m[1].cout == 128 and self.assembled(b, n)))
 
     def geometry(self, xyz, sample_xyz=None, fps_idx=None, points=None, ahead=True):
-        """The weight-independent part of the layer (FPS, centres, ball query): can run ahead on a side stream.
+        """The weight-independent part of the layer (FPS, centres, ball query) as an SAGeometry: can run ahead on a side stream.
         points: the module's input features; given for a narrow leaf module, the grouped rows u8 and their moments (which depend
-        on coordinates and input features only) are appended to the result."""
+        on coordinates and input features only) come with the result (first = NarrowRows)."""
         if fps_idx is None:
-            geom = sample_and_group(self.npoint, self.radius, self.nsample, xyz, sample_xyz, self.knn)
+            fps_idx, new_xyz, idx, pts_cnt = sample_and_group(self.npoint, self.radius, self.nsample, xyz, sample_xyz, self.knn)
         else:
             new_xyz = tf_sampling.gather_point(xyz, fps_idx)
             idx, pts_cnt = _group_indices(self.radius, self.nsample, xyz, new_xyz, self.knn)
-            geom = (fps_idx, new_xyz, idx, pts_cnt)
+        first = None
         if (points is not None or self.cin == 0) and self.narrow(xyz.shape[0] * self.npoint * self.nsample):
             if ahead and self.half_groups(xyz.shape[0], xyz.shape[1]):
-                half = M.half_groups(geom[3])
-                geom = tuple(geom) + M.narrow_rows_half(xyz, geom[1], points, geom[2], geom[3], half) + (half,)
+                half = M.half_groups(pts_cnt)
+                first = NarrowRows(*M.narrow_rows_half(xyz, new_xyz, points, idx, pts_cnt, half), half)
             else:
-                geom = tuple(geom) + M.narrow_rows(xyz, geom[1], points, geom[2])
+                first = NarrowRows(*M.narrow_rows(xyz, new_xyz, points, idx))
         elif (ahead or ASSEMBLE_INLINE) and self.half_groups(xyz.shape[0], xyz.shape[1]):
             # the layout and the count of its pieces: known on the host by the time the MLP runs when the geometry is computed ahead;
             # inside the step it serves (the proposal module: the votes exist only now) the count stays on the device -- waiting for it
             # would drain the queue -- and the kernels stop at it themselves
-            half = M.half_groups(geom[3], device_count=not ahead)
-            geom = tuple(geom) + M.assemble_rows_half(xyz, geom[1], geom[2], geom[3], half) + (half,)
+            half = M.half_groups(pts_cnt, device_count=not ahead)
+            first = AssembledRows(*M.assemble_rows_half(xyz, new_xyz, idx, pts_cnt, half), half)
             M.half_sort_rows(half, xyz.shape[0] * xyz.shape[1])  # the rows bucketed by point, for the first layer's backward
         elif self.assembled(xyz.shape[0], xyz.shape[1]) and (ahead or ASSEMBLE_INLINE):  # ahead=False: called inside the step it serves
-            geom = tuple(geom) + M.assemble_rows(xyz, geom[1], geom[2], pts_cnt=geom[3], in_pass=not ahead)  # geo records + per-point sums: coordinates only
-        return geom
+            first = AssembledRows(*M.assemble_rows(xyz, new_xyz, idx, pts_cnt=pts_cnt, in_pass=not ahead))  # geo records + per-point sums: coordinates only
+        return SAGeometry(fps_idx, new_xyz, idx, pts_cnt, first)
 
     def forward(self, xyz, points, sample_xyz=None, tape=None, geom=None):
         """xyz (B,n,3), points (B,n,C) or None -> new_xyz (B,m,3), new_points (B,m,C'), idx (B,m,K).
-        geom: the tuple returned by geometry() when it was computed ahead of time."""
+        geom: the SAGeometry returned by geometry() when it was computed ahead of time."""
         if self.plain_pool:
             return self._forward_plain_pool(xyz, points, sample_xyz, tape, geom)
         b = xyz.shape[0]
         geom = geom if geom is not None else self.geometry(xyz, sample_xyz, points=points)
-        fps_idx, new_xyz, idx, pts_cnt = geom[:4]
+        fps_idx, new_xyz, idx, pts_cnt, ahead = geom.fps_idx, geom.new_xyz, geom.idx, geom.pts_cnt, geom.first
         recs = []
         rows = b * self.npoint * self.nsample
-        first = ("gather", xyz, new_xyz, points, idx)
         if self.narrow(rows):
-            u8, mom = geom[4:6] if len(geom) >= 6 else M.narrow_rows(xyz, new_xyz, points, idx)
-            first = ("narrow", u8, mom)
-            if len(geom) >= 7:  # piece layout: the compact rows
-                half = geom[6].resolve()
-                first = ("narrow", half.u8, mom, half)
-        elif points is not None and self.assembled(b, xyz.shape[1]) and (len(geom) >= 7 or ASSEMBLE_INLINE):
-            geo, cntv, mom = geom[4:7] if len(geom) >= 7 else M.assemble_rows(xyz, new_xyz, idx, pts_cnt=pts_cnt, in_pass=True)
-            first = ("assembled", xyz, new_xyz, points, idx, geo, cntv, mom)
-            if len(geom) >= 8:  # piece layout: the compact rows
-                half = geom[7].resolve()
-                first = ("assembled", xyz, new_xyz, points, idx, half.geo, cntv, mom, half)
+            r = ahead if isinstance(ahead, NarrowRows) else NarrowRows(*M.narrow_rows(xyz, new_xyz, points, idx))
+            half = r.half.resolve() if r.half is not None else None  # piece layout: the compact rows
+            first = NarrowInput(half.u8 if half is not None else r.u8, r.mom, half)
+        elif points is not None and self.assembled(b, xyz.shape[1]) and (isinstance(ahead, AssembledRows) or ASSEMBLE_INLINE):
+            r = ahead if isinstance(ahead, AssembledRows) else AssembledRows(*M.assemble_rows(xyz, new_xyz, idx, pts_cnt=pts_cnt, in_pass=True))
+            half = r.half.resolve() if r.half is not None else None  # piece layout: the compact rows
+            first = AssembledInput(xyz, new_xyz, points, idx, half.geo if half is not None else r.geo, r.cntv, r.mom, half)
+        else:
+            first = GatherInput(xyz, new_xyz, points, idx)
         z, pend = mlp_chain_forward(self.mlp, rows, first, recs, pool_k=self.nsample, keep_z=tape is not None)
         if recs[-1]["pool"] is not None:  # utils.py:132, the pass over z already done by the GEMM epilogue
             res = M.bn_pool_finalize(recs[-1]["pool"], None, None, True, want_argmax=tape is not None, bn=pend,
@@ -958,7 +1075,7 @@ class SAModule:
         recs2 = []
         out = pooled
         if self.mlp2:
-            z2, _ = mlp_chain_forward(self.mlp2, b * self.npoint, ("dense", pooled), recs2)
+            z2, _ = mlp_chain_forward(self.mlp2, b * self.npoint, DenseInput(pooled), recs2)
             out = z2  # last conv_post layer has no activation (utils.py:153)
         if tape is not None:
             tape.append(dict(op="sa", module=self, recs=recs, recs2=recs2, argmax=argmax, zsel=zsel, fps_idx=fps_idx, idx=idx, pts_cnt=pts_cnt,
@@ -999,12 +1116,12 @@ class SAModule:
                 c = points.shape[2]
                 x = torch.empty((b * n, 3 + c), dtype=torch.float32, device=xyz.device)
                 M.row_segments(b * n, [(x[:, :3], xyz.reshape(b * n, 3), None), (x[:, 3:], points.reshape(b * n, c), None)])
-            first = ("dense", x)
+            first = DenseInput(x)
         else:
             geom = geom if geom is not None else self.geometry(xyz, sample_xyz)
-            fps_idx, new_xyz, idx, pts_cnt = geom[:4]
+            fps_idx, new_xyz, idx, pts_cnt = geom.fps_idx, geom.new_xyz, geom.idx, geom.pts_cnt
             m, k = self.npoint, self.nsample
-            first = ("gather", xyz, new_xyz, points, idx)
+            first = GatherInput(xyz, new_xyz, points, idx)
         rows = b * m * k
         recs = []
         z, pend = mlp_chain_forward(self.mlp, rows, first, recs)
@@ -1016,7 +1133,7 @@ class SAModule:
         recs2 = []
         out = pooled
         if self.mlp2:
-            out, _ = mlp_chain_forward(self.mlp2, b * m, ("dense", pooled), recs2)
+            out, _ = mlp_chain_forward(self.mlp2, b * m, DenseInput(pooled), recs2)
         if tape is not None:
             tape.append(dict(op="sa", module=self, recs=recs, recs2=recs2, argmax=argmax, zsel=None, fps_idx=fps_idx, idx=idx,
                              pts_cnt=pts_cnt, xyz=xyz, points=points, new_xyz=new_xyz, b=b, m=m, k=k, weights=w))
@@ -1178,20 +1295,21 @@ class FPModule:
 
     @staticmethod
     def geometry(xyz1, xyz2):
-        """three_nn + inverse-distance weights (utils.py:278-282): feature independent."""
+        """three_nn + inverse-distance weights (utils.py:278-282) as an FPGeometry: feature independent."""
         dist, idx = tf_interpolate.three_nn(xyz1, xyz2)
-        return M.attach_inverse(idx, xyz2.shape[1], always=tf_interpolate.GATHER_GRAD), tf_interpolate.three_nn_weights(dist)
+        return FPGeometry(M.attach_inverse(idx, xyz2.shape[1], always=tf_interpolate.GATHER_GRAD), tf_interpolate.three_nn_weights(dist))
 
     def forward(self, xyz1, xyz2, points1, points2, tape=None, geom=None):
         b, n1 = xyz1.shape[:2]
-        idx, weight = geom if geom is not None else self.geometry(xyz1, xyz2)  # utils.py:278-282
+        geom = geom if geom is not None else self.geometry(xyz1, xyz2)  # utils.py:278-282
+        idx, weight = geom.idx, geom.weight
         if points1 is not None:  # utils.py:283-286: the interpolation writes the concat [interpolated | points1] itself
             x = tf_interpolate.three_interpolate_concat(points2, idx, weight, points1)
         else:
             x = tf_interpolate.three_interpolate(points2, idx, weight)
         rows = b * n1
         recs = []
-        z, pend = mlp_chain_forward(self.mlp, rows, ("dense", x.view(rows, -1)), recs)
+        z, pend = mlp_chain_forward(self.mlp, rows, DenseInput(x.view(rows, -1)), recs)
         y = M.bn_relu(z, None, None, True, bn=pend)
         if tape is not None:
             tape.append(dict(op="fp", module=self, recs=recs, idx=idx, weight=weight, m=xyz2.shape[1],
