@@ -3,7 +3,7 @@ tower (decode -> 3D NMS) on held-out scenes and report mAP@0.25 / @0.5 with the 
 of the per-batch mAPs (the figure of every earlier log), "set mAP" the reference's own metric, detections ranked over the whole
 validation set (evaluator.evaluate).
     python tools/train_eval.py [steps] [train_batches] [--save PATH] [--resume PATH] [--monitor K] [--guard] [--height] [--per-class] [--min-points K]
-                                                      [--nms-overlap {rotated,aabb3d,bev}] [--nms-old-type]
+                                                      [--nms-overlap {rotated,aabb3d,bev}] [--nms-old-type] [--paper-votes]
 --save PATH: a checkpoint (VoteNetHotPath.save) at every evaluation and at the end.  --resume PATH: continue the run a checkpoint
 holds -- parameters, moving averages, Adam state and step count -- up to `steps` steps in all, on the batches it would have seen.  --monitor K: the reference's training summaries from the device
 (VoteNetHotPath.enable_monitors): every K steps the moving averages of obj_accuracy / sem_accuracy / total_cost over the last 100 steps
@@ -20,7 +20,10 @@ the device) in the set-level evaluations.
 --nms-overlap: the overlap the per-class protocol's NMS suppresses by (aabb_nms; --per-class only): rotated, the rotated-box IoU of the
 rest of the project (the default); aabb3d, the overlap of the boxes' axis-aligned hulls, the paper's; bev, the same on the ground plane.
 --nms-old-type: with aabb3d or bev, the paper's use_old_type_nms: intersection over the later box instead of IoU.
---per-class --min-points 5 --nms-overlap aabb3d is the paper's protocol."""
+--per-class --min-points 5 --nms-overlap aabb3d is the paper's protocol.
+--paper-votes: train with the paper's vote supervision (VoteNetHotPath.enable_vote_supervision("paper"), vote_supervision.py): a seed votes
+for the centres of the boxes that contain it, the closest of up to three is charged, the mean is over the supervised seeds; the printed
+vote_reg_loss and total cost are then the paper's.  A setting of the run, not of the checkpoint: give it again with --resume."""
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import importlib.util
@@ -43,6 +46,7 @@ ap.add_argument("--per-class", action="store_true", help="print the set-level mA
 ap.add_argument("--min-points", metavar="K", type=int, default=0, help="drop predicted boxes that hold fewer than K points of the cloud (the paper: 5)")
 ap.add_argument("--nms-overlap", choices=("rotated", "aabb3d", "bev"), default="rotated", help="the overlap of the per-class protocol's NMS (the paper: aabb3d)")
 ap.add_argument("--nms-old-type", action="store_true", help="with aabb3d / bev: intersection over the later box instead of IoU (the paper's use_old_type_nms)")
+ap.add_argument("--paper-votes", action="store_true", help="supervise the votes as the VoteNet paper does (one launch more behind the loss)")
 args = ap.parse_args()
 if (args.nms_overlap != "rotated" or args.nms_old_type) and not args.per_class:
     ap.error("--nms-overlap / --nms-old-type need --per-class: the reference's protocol suppresses by the rotated-box IoU")
@@ -60,6 +64,8 @@ if args.monitor > 0:
     net.enable_monitors(window=100, tensors_every=10 * args.monitor)
 if args.guard:
     net.enable_step_guard()  # (after the resume: its snapshot is of the restored moving averages)
+if args.paper_votes:
+    net.enable_vote_supervision("paper")
 xs = [torch.from_numpy(synth.room_batch(B, n, 5000 + B * i)).to(dev) for i in range(nb)]
 gts = [VL.gt_to_device(synth.room_gt(B, n, 5000 + B * i), dev) for i in range(nb)]
 val_x = [torch.from_numpy(synth.room_batch(B, n, 90000 + B * i)).to(dev) for i in range(4)]

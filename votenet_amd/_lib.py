@@ -24,6 +24,7 @@ SIDE_LIBS = {
     "boxpts": "votenet_box_points.h",        # points inside predicted boxes, the empty-box gate
     "aabb": "votenet_aabb_nms.h",            # the axis-aligned overlaps of the paper's NMS
     "depth": "votenet_depth_scan.h",         # the raw scan from the depth image
+    "votesup": "votenet_vote_supervision.h",  # the paper's vote supervision, one launch behind the loss
 }
 _side = {}  # name -> (the loaded library, its *_last_error function)
 

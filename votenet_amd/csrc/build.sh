@@ -61,6 +61,9 @@ SIDE_LIBS=(
   "aabb     aabb_nms.hip       aabb     -fno-slp-vectorize"
   # the raw scan from the depth image.  No contraction: tests/depth_scan_ref.py restates the rule operation for operation in double
   "depth    depth_scan.hip     depth"
+  # the paper's vote supervision, one launch behind the loss.  No contraction: tests/vote_supervision_ref.py restates the rule operation
+  # for operation; -fno-slp-vectorize as box_points.hip: the seed slots' rotations would pack likewise
+  "votesup  vote_supervision.hip votesup -fno-slp-vectorize"
 )
 side_lib() { # directory, source, library name, extra flags ...
   local dir="$HERE/$1" src="$HERE/$1/$2" lib="libvotenet_$3.so" obj="$HERE/$1/obj/$(basename "${2%.hip}").o" tmp

@@ -910,8 +910,10 @@ class VoteNetHotPath:
         out = self._head_forward(lv, geom("fp1"), geom("fp2"), I["prop_fps"], tail, copy_seeds=copy_seeds)
         self.update_moving_averages(list(tape_levels) + tail)
         losses, cot = loss_hook(out) if loss_hook is not None else VL.votenet_loss(out, gt)
-        if loss_hook is None and self.monitors is not None:
-            self.last_accuracies = self.monitors.after_loss(out, gt, losses)
+        if loss_hook is None:
+            self._paper_votes(out, gt, losses, cot["votes_xyz"])
+            if self.monitors is not None:
+                self.last_accuracies = self.monitors.after_loss(out, gt, losses)
         with P.WGRAD.on(wgrad_stream):
             grads = self._head_backward(tail, cot, cut=cut)
             if cut is None:
@@ -962,8 +964,14 @@ class VoteNetHotPath:
         sg.last_used = self._stretch_clock
         self.store._fresh_wait()
         mon = self.monitors
+        after_loss = mon.after_loss if mon is not None else None
+        if self.vote_supervision == "paper":  # into the buffer the next segment reads, then the monitors: their ring records the new total
+            def after_loss(out, gt, losses):
+                self._paper_votes(out, gt, losses, sg.loss_bufs[1][:out["votes_xyz"].numel()].view_as(out["votes_xyz"]))
+                if mon is not None:
+                    mon.after_loss(out, gt, losses)
         out, self.last_losses, grads = sg.replay(ins, gt, self._wgrad_side(),  # (a vector of the graph's ring: rewritten eight replays later)
-                                                 after_loss=mon.after_loss if mon is not None else None)
+                                                 after_loss=after_loss)
         if mon is not None:
             self.last_accuracies = mon.accuracies
         self._ema_version += 1  # (the replay ran votenet_ema_update: inference_bn() must not serve a table built before it)
@@ -1042,6 +1050,36 @@ class VoteNetHotPath:
         """Back to the launches of an unmonitored step (the default)."""
         self.monitors = None
         self.last_accuracies = None
+
+    # ---- vote supervision as in the VoteNet paper (vote_supervision.py): off unless asked for ------------------------------------
+    vote_supervision = None  # the mode while enable_vote_supervision is in force (vote_supervision.MODES); a setting of the run, not checkpoint state
+
+    def enable_vote_supervision(self, mode="paper"):
+        """From now on every train_step(..., gt=...) supervises the votes by `mode`.  "paper": one more launch behind the loss launch
+        (vote_supervision.paper_vote_loss) overwrites the whole vote cotangent, last_losses[1] (vote_reg_loss) and re-forms
+        last_losses[0]: a seed votes for the centres of the boxes that contain it, up to three targets, the closest is charged, the
+        mean is over the supervised seeds.  "reference": the rule of votenet_loss itself, no launch.  Everything else of the step --
+        the other ten loss values, the other two cotangents, the graphs (none is captured again), the guard, the data-parallel
+        exchange, the optimizer -- is what it was.  A step with fixed cotangents (cot=) has no loss and is not touched."""
+        from . import vote_supervision as VS
+        if mode not in VS.MODES:
+            raise M.L.InvalidArgumentError("enable_vote_supervision: mode must be one of %s, got %r" % (", ".join(VS.MODES), mode))
+        self.vote_supervision = mode
+
+    def disable_vote_supervision(self):
+        """Back to the launches of a step with the reference's vote supervision (the default)."""
+        self.vote_supervision = None
+
+    def _paper_votes(self, out, gt, losses, d_votes):
+        """Behind votenet_loss, before the monitors' launch: the paper's vote term in place of the reference's (mode "paper" only)."""
+        if self.vote_supervision != "paper":
+            return
+        from . import vote_supervision as VS  # (the only place of a train step that loads libvotenet_votesup.so)
+        b = d_votes.shape[0]
+        work = self.__dict__.setdefault("_votesup_work", {})
+        if b not in work:  # zero once: every launch leaves it zero
+            work[b] = (VS.workspace(b, self.device), torch.empty(1, dtype=torch.int32, device=self.device))
+        VS.paper_vote_loss(out, gt, losses, d_votes=d_votes, supervised=work[b][1], work=work[b][0])
 
     # ---- the step guard (step_guard.py): off unless asked for ------------------------------------------------------------------
     step_guard = None        # a step_guard.StepGuard while enable_step_guard is in force
@@ -1129,6 +1167,7 @@ class VoteNetHotPath:
                 if gt is not None:
                     from . import loss as VL
                     self.last_losses, cot = VL.votenet_loss(out, gt)
+                    self._paper_votes(out, gt, self.last_losses, cot["votes_xyz"])
                     if self.monitors is not None:
                         self.last_accuracies = self.monitors.after_loss(out, gt, self.last_losses)
                 self._gsync.begin()
