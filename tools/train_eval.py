@@ -3,7 +3,7 @@ tower (decode -> 3D NMS) on held-out scenes and report mAP@0.25 / @0.5 with the 
 of the per-batch mAPs (the figure of every earlier log), "set mAP" the reference's own metric, detections ranked over the whole
 validation set (evaluator.evaluate).
     python tools/train_eval.py [steps] [train_batches] [--save PATH] [--resume PATH] [--monitor K] [--guard] [--height] [--per-class] [--min-points K]
-                                                      [--nms-overlap {rotated,aabb3d,bev}] [--nms-old-type] [--paper-votes]
+                                                      [--nms-overlap {rotated,aabb3d,bev}] [--nms-old-type] [--paper-votes] [--paper-proposals]
 --save PATH: a checkpoint (VoteNetHotPath.save) at every evaluation and at the end.  --resume PATH: continue the run a checkpoint
 holds -- parameters, moving averages, Adam state and step count -- up to `steps` steps in all, on the batches it would have seen.  --monitor K: the reference's training summaries from the device
 (VoteNetHotPath.enable_monitors): every K steps the moving averages of obj_accuracy / sem_accuracy / total_cost over the last 100 steps
@@ -23,7 +23,13 @@ rest of the project (the default); aabb3d, the overlap of the boxes' axis-aligne
 --per-class --min-points 5 --nms-overlap aabb3d is the paper's protocol.
 --paper-votes: train with the paper's vote supervision (VoteNetHotPath.enable_vote_supervision("paper"), vote_supervision.py): a seed votes
 for the centres of the boxes that contain it, the closest of up to three is charged, the mean is over the supervised seeds; the printed
-vote_reg_loss and total cost are then the paper's.  A setting of the run, not of the checkpoint: give it again with --resume."""
+vote_reg_loss and total cost are then the paper's.  A setting of the run, not of the checkpoint: give it again with --resume.
+--paper-proposals: train with the paper's objectness and centre supervision (VoteNetHotPath.enable_proposal_supervision("paper"),
+proposal_supervision.py): one cross-entropy weighted 0.2 / 0.8 over all proposals outside the grey zone, and a Chamfer distance between
+the predicted centres and the real ground-truth centres; the printed obj_cls_loss, center_loss, box loss and total cost are then the
+paper's.  Independent of --paper-votes; likewise a setting of the run.  With both, the two terms whose RULE differed from the paper's
+follow it; its size-residual mean over the axes (1/3), its overall x 10, FPS on the votes and the BatchNorm momentum schedule are not
+taken over."""
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import importlib.util
@@ -47,6 +53,7 @@ ap.add_argument("--min-points", metavar="K", type=int, default=0, help="drop pre
 ap.add_argument("--nms-overlap", choices=("rotated", "aabb3d", "bev"), default="rotated", help="the overlap of the per-class protocol's NMS (the paper: aabb3d)")
 ap.add_argument("--nms-old-type", action="store_true", help="with aabb3d / bev: intersection over the later box instead of IoU (the paper's use_old_type_nms)")
 ap.add_argument("--paper-votes", action="store_true", help="supervise the votes as the VoteNet paper does (one launch more behind the loss)")
+ap.add_argument("--paper-proposals", action="store_true", help="supervise objectness and centre as the VoteNet paper does (one launch more behind the loss)")
 args = ap.parse_args()
 if (args.nms_overlap != "rotated" or args.nms_old_type) and not args.per_class:
     ap.error("--nms-overlap / --nms-old-type need --per-class: the reference's protocol suppresses by the rotated-box IoU")
@@ -66,6 +73,8 @@ if args.guard:
     net.enable_step_guard()  # (after the resume: its snapshot is of the restored moving averages)
 if args.paper_votes:
     net.enable_vote_supervision("paper")
+if args.paper_proposals:
+    net.enable_proposal_supervision("paper")
 xs = [torch.from_numpy(synth.room_batch(B, n, 5000 + B * i)).to(dev) for i in range(nb)]
 gts = [VL.gt_to_device(synth.room_gt(B, n, 5000 + B * i), dev) for i in range(nb)]
 val_x = [torch.from_numpy(synth.room_batch(B, n, 90000 + B * i)).to(dev) for i in range(4)]

@@ -25,6 +25,7 @@ SIDE_LIBS = {
     "aabb": "votenet_aabb_nms.h",            # the axis-aligned overlaps of the paper's NMS
     "depth": "votenet_depth_scan.h",         # the raw scan from the depth image
     "votesup": "votenet_vote_supervision.h",  # the paper's vote supervision, one launch behind the loss
+    "propsup": "votenet_proposal_supervision.h",  # the paper's objectness and centre supervision, one launch behind the loss
 }
 _side = {}  # name -> (the loaded library, its *_last_error function)
 

@@ -64,6 +64,9 @@ SIDE_LIBS=(
   # the paper's vote supervision, one launch behind the loss.  No contraction: tests/vote_supervision_ref.py restates the rule operation
   # for operation; -fno-slp-vectorize as box_points.hip: the seed slots' rotations would pack likewise
   "votesup  vote_supervision.hip votesup -fno-slp-vectorize"
+  # the paper's objectness and centre supervision, one launch behind the loss.  No contraction: tests/proposal_supervision_ref.py restates
+  # the rule operation for operation; -fno-slp-vectorize as loss.hip, whose assignment loop (nearest_box.h) it shares
+  "propsup  proposal_supervision.hip propsup -fno-slp-vectorize"
 )
 side_lib() { # directory, source, library name, extra flags ...
   local dir="$HERE/$1" src="$HERE/$1/$2" lib="libvotenet_$3.so" obj="$HERE/$1/obj/$(basename "${2%.hip}").o" tmp

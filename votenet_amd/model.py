@@ -912,6 +912,7 @@ class VoteNetHotPath:
         losses, cot = loss_hook(out) if loss_hook is not None else VL.votenet_loss(out, gt)
         if loss_hook is None:
             self._paper_votes(out, gt, losses, cot["votes_xyz"])
+            self._paper_proposals(out, gt, losses, cot["proposals_xyz"], cot["proposals_output"])
             if self.monitors is not None:
                 self.last_accuracies = self.monitors.after_loss(out, gt, losses)
         with P.WGRAD.on(wgrad_stream):
@@ -965,9 +966,13 @@ class VoteNetHotPath:
         self.store._fresh_wait()
         mon = self.monitors
         after_loss = mon.after_loss if mon is not None else None
-        if self.vote_supervision == "paper":  # into the buffer the next segment reads, then the monitors: their ring records the new total
+        if self.vote_supervision == "paper" or self.proposal_supervision == "paper":
+            # into the buffers the next segment reads, then the monitors: their ring records the new total
             def after_loss(out, gt, losses):
-                self._paper_votes(out, gt, losses, sg.loss_bufs[1][:out["votes_xyz"].numel()].view_as(out["votes_xyz"]))
+                flat, nv, npx = sg.loss_bufs[1], out["votes_xyz"].numel(), out["proposals_xyz"].numel()
+                self._paper_votes(out, gt, losses, flat[:nv].view_as(out["votes_xyz"]))
+                self._paper_proposals(out, gt, losses, flat[nv:nv + npx].view_as(out["proposals_xyz"]),
+                                      flat[nv + npx:nv + npx + out["proposals_output"].numel()].view_as(out["proposals_output"]))
                 if mon is not None:
                     mon.after_loss(out, gt, losses)
         out, self.last_losses, grads = sg.replay(ins, gt, self._wgrad_side(),  # (a vector of the graph's ring: rewritten eight replays later)
@@ -1081,6 +1086,39 @@ class VoteNetHotPath:
             work[b] = (VS.workspace(b, self.device), torch.empty(1, dtype=torch.int32, device=self.device))
         VS.paper_vote_loss(out, gt, losses, d_votes=d_votes, supervised=work[b][1], work=work[b][0])
 
+    # ---- objectness and centre supervision as in the VoteNet paper (proposal_supervision.py): off unless asked for ----------------
+    proposal_supervision = None  # the mode while enable_proposal_supervision is in force (proposal_supervision.MODES); a setting of the run, not checkpoint state
+
+    def enable_proposal_supervision(self, mode="paper"):
+        """From now on every train_step(..., gt=...) supervises objectness and centre by `mode`.  "paper": one more launch behind the
+        loss launch (proposal_supervision.paper_proposal_loss; after the paper-vote launch when that mode is on too, before the
+        monitors') overwrites columns 0..4 of the proposals_output cotangent, the whole proposals_xyz cotangent, last_losses[2]
+        (obj_cls_loss) and last_losses[3] (center_loss) and re-forms last_losses[9] and last_losses[0]: one cross-entropy weighted 0.2 /
+        0.8 over all proposals outside the grey zone, and a Chamfer distance between the predicted and the real ground-truth centres.
+        "reference": the rule of votenet_loss itself, no launch.  Everything else of the step -- the other loss values, the other
+        columns, the vote cotangent, the graphs (none is captured again), the guard, the data-parallel exchange, the optimizer -- is
+        what it was.  A step with fixed cotangents (cot=) has no loss and is not touched."""
+        from . import proposal_supervision as PS
+        if mode not in PS.MODES:
+            raise M.L.InvalidArgumentError("enable_proposal_supervision: mode must be one of %s, got %r" % (", ".join(PS.MODES), mode))
+        self.proposal_supervision = mode
+
+    def disable_proposal_supervision(self):
+        """Back to the launches of a step with the reference's objectness and centre terms (the default)."""
+        self.proposal_supervision = None
+
+    def _paper_proposals(self, out, gt, losses, d_xyz, d_out):
+        """Behind votenet_loss and _paper_votes, before the monitors' launch: the paper's objectness and centre terms in place of the
+        reference's (mode "paper" only)."""
+        if self.proposal_supervision != "paper":
+            return
+        from . import proposal_supervision as PS  # (the only place of a train step that loads libvotenet_propsup.so)
+        b = d_xyz.shape[0]
+        work = self.__dict__.setdefault("_propsup_work", {})
+        if b not in work:  # zero once: every launch leaves it zero
+            work[b] = (PS.workspace(b, self.device), torch.empty(3, dtype=torch.int32, device=self.device))
+        PS.paper_proposal_loss(out, gt, losses, d_xyz=d_xyz, d_out=d_out, counts=work[b][1], work=work[b][0])
+
     # ---- the step guard (step_guard.py): off unless asked for ------------------------------------------------------------------
     step_guard = None        # a step_guard.StepGuard while enable_step_guard is in force
 
@@ -1168,6 +1206,7 @@ class VoteNetHotPath:
                     from . import loss as VL
                     self.last_losses, cot = VL.votenet_loss(out, gt)
                     self._paper_votes(out, gt, self.last_losses, cot["votes_xyz"])
+                    self._paper_proposals(out, gt, self.last_losses, cot["proposals_xyz"], cot["proposals_output"])
                     if self.monitors is not None:
                         self.last_accuracies = self.monitors.after_loss(out, gt, self.last_losses)
                 self._gsync.begin()
