@@ -3,7 +3,7 @@ tower (decode -> 3D NMS) on held-out scenes and report mAP@0.25 / @0.5 with the 
 of the per-batch mAPs (the figure of every earlier log), "set mAP" the reference's own metric, detections ranked over the whole
 validation set (evaluator.evaluate).
     python tools/train_eval.py [steps] [train_batches] [--save PATH] [--resume PATH] [--monitor K] [--guard] [--height] [--per-class] [--min-points K]
-                                                      [--nms-overlap {rotated,aabb3d,bev}] [--nms-old-type] [--paper-votes] [--paper-proposals]
+                                                      [--nms-overlap {rotated,aabb3d,bev}] [--nms-old-type] [--paper-votes] [--paper-proposals] [--vote-fps]
 --save PATH: a checkpoint (VoteNetHotPath.save) at every evaluation and at the end.  --resume PATH: continue the run a checkpoint
 holds -- parameters, moving averages, Adam state and step count -- up to `steps` steps in all, on the batches it would have seen.  --monitor K: the reference's training summaries from the device
 (VoteNetHotPath.enable_monitors): every K steps the moving averages of obj_accuracy / sem_accuracy / total_cost over the last 100 steps
@@ -28,8 +28,11 @@ vote_reg_loss and total cost are then the paper's.  A setting of the run, not of
 proposal_supervision.py): one cross-entropy weighted 0.2 / 0.8 over all proposals outside the grey zone, and a Chamfer distance between
 the predicted centres and the real ground-truth centres; the printed obj_cls_loss, center_loss, box loss and total cost are then the
 paper's.  Independent of --paper-votes; likewise a setting of the run.  With both, the two terms whose RULE differed from the paper's
-follow it; its size-residual mean over the axes (1/3), its overall x 10, FPS on the votes and the BatchNorm momentum schedule are not
-taken over."""
+follow it; its size-residual mean over the axes (1/3), its overall x 10 and the BatchNorm momentum schedule are not taken over.
+--vote-fps: the proposal module's cluster centres are sampled by farthest-point sampling on the VOTES, the paper's rule
+(VoteNetHotPath.enable_proposal_sampling("vote_fps"), vote_sampling.py), in training and in every evaluation of the run; the default
+samples the seeds, as the reference does.  Independent of --paper-votes / --paper-proposals; likewise a setting of the run, not of the
+checkpoint: evaluate a network under the mode it was trained in."""
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import importlib.util
@@ -54,6 +57,7 @@ ap.add_argument("--nms-overlap", choices=("rotated", "aabb3d", "bev"), default="
 ap.add_argument("--nms-old-type", action="store_true", help="with aabb3d / bev: intersection over the later box instead of IoU (the paper's use_old_type_nms)")
 ap.add_argument("--paper-votes", action="store_true", help="supervise the votes as the VoteNet paper does (one launch more behind the loss)")
 ap.add_argument("--paper-proposals", action="store_true", help="supervise objectness and centre as the VoteNet paper does (one launch more behind the loss)")
+ap.add_argument("--vote-fps", action="store_true", help="sample the proposal module's centres by FPS on the votes, as the VoteNet paper does (one launch in the stretch)")
 args = ap.parse_args()
 if (args.nms_overlap != "rotated" or args.nms_old_type) and not args.per_class:
     ap.error("--nms-overlap / --nms-old-type need --per-class: the reference's protocol suppresses by the rotated-box IoU")
@@ -75,6 +79,8 @@ if args.paper_votes:
     net.enable_vote_supervision("paper")
 if args.paper_proposals:
     net.enable_proposal_supervision("paper")
+if args.vote_fps:
+    net.enable_proposal_sampling("vote_fps")
 xs = [torch.from_numpy(synth.room_batch(B, n, 5000 + B * i)).to(dev) for i in range(nb)]
 gts = [VL.gt_to_device(synth.room_gt(B, n, 5000 + B * i), dev) for i in range(nb)]
 val_x = [torch.from_numpy(synth.room_batch(B, n, 90000 + B * i)).to(dev) for i in range(4)]

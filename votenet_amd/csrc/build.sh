@@ -67,6 +67,10 @@ SIDE_LIBS=(
   # the paper's objectness and centre supervision, one launch behind the loss.  No contraction: tests/proposal_supervision_ref.py restates
   # the rule operation for operation; -fno-slp-vectorize as loss.hip, whose assignment loop (nearest_box.h) it shares
   "propsup  proposal_supervision.hip propsup -fno-slp-vectorize"
+  # the proposal module's clusters sampled on the votes, one launch.  No contraction: the picks and hits are fps.hip's and grouping.hip's,
+  # decided by the same un-fused expressions (ball_threshold.h is the text of votenet_query_ball_point's threshold);
+  # -fno-slp-vectorize as box_points.hip: the three axes' products would pack likewise
+  "votesamp vote_sampling.hip  votesamp -fno-slp-vectorize"
 )
 side_lib() { # directory, source, library name, extra flags ...
   local dir="$HERE/$1" src="$HERE/$1/$2" lib="libvotenet_$3.so" obj="$HERE/$1/obj/$(basename "${2%.hip}").o" tmp

@@ -18,6 +18,7 @@
 // exactly equivalent for r > 1e-20 (sqrtf is monotone) and is NOT the same as s < r*r
 // (SURVEY.md appendix A.3).
 #include "common.h"
+#include "ball_threshold.h" // ball_threshold: T(r), shared with libvotenet_votesamp.so
 #include <cmath>
 
 namespace votenet {
@@ -194,15 +195,6 @@ __global__ void group_point_grad_kernel(long rows, int n, int c, long rows_per_s
         const int ii = idx[row];
         unsafeAtomicAdd(&grad_points[((size_t)s * n + ii) * c + l], grad_out[e]);
     }
-}
-
-// smallest fp32 T with sqrtf(T) >= r (host, correctly rounded sqrtf)
-float ball_threshold(float r)
-{
-    float t = r * r;
-    while (t > 0.0f && sqrtf(t) >= r) t = nextafterf(t, 0.0f);
-    while (sqrtf(t) < r) t = nextafterf(t, INFINITY);
-    return t;
 }
 
 static inline int grid_for(long total, int block)

@@ -570,9 +570,15 @@ class VoteNetHotPath:
 
     def propose(self, votes_xyz, votes_points, seeds_xyz, tape=None, prop_fps=None):
         """model.py:89-93: SA on votes with FPS on the seeds -> proposals_xyz (B,256,3), output (B,256,79).
-        prop_fps: the FPS indices of THESE seeds when they were computed ahead (side stream); None: the seeds are sampled here."""
+        prop_fps: the FPS indices of THESE seeds when they were computed ahead (side stream); None: the seeds are sampled here.
+        With enable_proposal_sampling("vote_fps") in force seeds_xyz and prop_fps are not read: the votes themselves are sampled
+        (vote_sampling.cluster_votes, one launch), and the tape carries their fps_idx."""
         geom = None
-        if prop_fps is not None:
+        if self.proposal_sampling == "vote_fps":
+            from . import vote_sampling as VSAMP  # (the only place of a pass that loads libvotenet_votesamp.so)
+            pr = self.proposal
+            geom = pr.geometry(votes_xyz, grouped=VSAMP.cluster_votes(votes_xyz, pr.npoint, pr.radius, pr.nsample))
+        elif prop_fps is not None:
             geom = self.proposal.geometry(votes_xyz, fps_idx=prop_fps, ahead=False)  # the votes exist only now
         p_xyz, p_out, _ = self.proposal.forward(votes_xyz, votes_points, sample_xyz=seeds_xyz, tape=tape, geom=geom)
         return p_xyz, p_out
@@ -937,7 +943,8 @@ class VoteNetHotPath:
         ins = self._stretch_inputs(lv, g)
         key = tuple((k, tuple(v.shape), v.dtype) for k, v in ins.items()) + (P.HALF_GROUPS, P.ASSEMBLE_FIRST, P.ASSEMBLE_INLINE, P.POOL_GRAM_BACKWARD, P.ASSEMBLED_DECOMPOSED,
                                                                              self.overlap_wgrad, STRETCH_SEGMENTS, M.SPLIT_K, M.COEF_TAIL, P.WGRAD_BATCH, P.POOL_IN_EPILOGUE,
-                                                                             self.store.split, bool(getattr(self, "inline_wgrad_tail", INLINE_WGRAD_TAIL)), M.FORWARD_H2, M.ADHOC_H2, M.CONFIG_EPOCH)
+                                                                             self.store.split, bool(getattr(self, "inline_wgrad_tail", INLINE_WGRAD_TAIL)), M.FORWARD_H2, M.ADHOC_H2,
+                                                                             self.proposal_sampling or "seed_fps", M.CONFIG_EPOCH)  # (the mode before the epoch: dkey below carries it too)
         graphs = self.__dict__.setdefault("_stretch_graphs", {})
         sg = graphs.get(key)
         self._gsync.begin()
@@ -1118,6 +1125,39 @@ class VoteNetHotPath:
         if b not in work:  # zero once: every launch leaves it zero
             work[b] = (PS.workspace(b, self.device), torch.empty(3, dtype=torch.int32, device=self.device))
         PS.paper_proposal_loss(out, gt, losses, d_xyz=d_xyz, d_out=d_out, counts=work[b][1], work=work[b][0])
+
+    # ---- proposals sampled on the votes as in the VoteNet paper (vote_sampling.py): off unless asked for ---------------------------
+    proposal_sampling = None  # the mode while enable_proposal_sampling is in force (vote_sampling.MODES); a setting of the run, not checkpoint state
+
+    def enable_proposal_sampling(self, mode="vote_fps"):
+        """From now on every pass -- forward, predict, evaluate, train_step (launch path and replayed graphs) and their backward --
+        picks the proposal module's cluster centres by `mode`.  "vote_fps": farthest-point sampling on the VOTES, the paper's rule: one
+        launch (vote_sampling.cluster_votes) between the voting MLP and the proposal MLP samples the votes, gathers the centres and
+        runs the ball query; propose() no longer reads seeds_xyz or prop_fps, and the tape carries the votes' fps_idx, so a
+        proposals_xyz cotangent is scattered to the sampled votes.  "seed_fps": the reference's rule (the votes of the seeds that
+        farthest-point sampling picks among the seeds), the default, no launch of this library.
+        The geometry chain, its ring and its prop_fps stay what they were: with the mode on the seeds' sampling still runs a batch
+        ahead on the side stream and is not read -- the seeds are in farthest-point order, so it is the confirmed-prefix case and runs
+        no round --, and the captured geometry graphs need no second form.  The stretch graphs key on the mode: the first step in a
+        new mode runs launch by launch, each mode keeps its own capture, switching back replays the old one.
+        The mode is a setting of the run, not checkpoint state, and it applies to inference as much as to training: evaluate a network
+        under the mode it was trained in.  "vote_fps" on a network whose seed count or proposal shape the kernel refuses
+        (vote_sampling.supported) is an InvalidArgumentError here, not in the step."""
+        from . import vote_sampling as VSAMP
+        if mode not in VSAMP.MODES:
+            raise M.L.InvalidArgumentError("enable_proposal_sampling: mode must be one of %s, got %r" % (", ".join(VSAMP.MODES), mode))
+        if mode == "vote_fps":
+            n, pr = self.sa2.npoint, self.proposal
+            if pr.knn or pr.group_all or not VSAMP.supported(n, pr.npoint, pr.nsample):
+                raise M.L.InvalidArgumentError(
+                    "enable_proposal_sampling: vote_fps takes 1 to %d votes, 1 to %d clusters and 1 to %d votes per ball-query cluster; "
+                    "this network has %d seeds and a proposal module of npoint %r, nsample %r, knn %r, group_all %r"
+                    % (VSAMP.MAX_N, VSAMP.MAX_M, VSAMP.MAX_NSAMPLE, n, pr.npoint, pr.nsample, pr.knn, pr.group_all))
+        self.proposal_sampling = mode
+
+    def disable_proposal_sampling(self):
+        """Back to the launches of a pass with the reference's proposal sampling (the default)."""
+        self.proposal_sampling = None
 
     # ---- the step guard (step_guard.py): off unless asked for ------------------------------------------------------------------
     step_guard = None        # a step_guard.StepGuard while enable_step_guard is in force

@@ -1016,11 +1016,17 @@ class SAModule:
             return False
         return bool(self.narrow(b * self.npoint * 64) or (m[1].cout == 128 and self.assembled(b, n)))
 
-    def geometry(self, xyz, sample_xyz=None, fps_idx=None, points=None, ahead=True):
+    def geometry(self, xyz, sample_xyz=None, fps_idx=None, points=None, ahead=True, grouped=None):
         """The weight-independent part of the layer (FPS, centres, ball query) as an SAGeometry: can run ahead on a side stream.
         points: the module's input features; given for a narrow leaf module, the grouped rows u8 and their moments (which depend
-        on coordinates and input features only) come with the result (first = NarrowRows)."""
-        if fps_idx is None:
+        on coordinates and input features only) come with the result (first = NarrowRows).
+        grouped: (fps_idx, new_xyz, idx, pts_cnt) already made for xyz (vote_sampling.cluster_votes): no gather, no ball query here;
+        the rest as with ahead=False -- the caller is inside the step it serves."""
+        if grouped is not None:
+            fps_idx, new_xyz, idx, pts_cnt = grouped
+            idx = M.attach_inverse(idx, xyz.shape[1])  # (the deterministic mode's inverse, as _group_indices attaches it)
+            ahead = False
+        elif fps_idx is None:
             fps_idx, new_xyz, idx, pts_cnt = sample_and_group(self.npoint, self.radius, self.nsample, xyz, sample_xyz, self.knn)
         else:
             new_xyz = tf_sampling.gather_point(xyz, fps_idx)

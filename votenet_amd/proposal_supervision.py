@@ -15,8 +15,8 @@ re-forms losses[9] and losses[0]; everything else of the step is what it was.  V
 it in every train step.  The rule is stated once, in the header; tests/proposal_supervision_ref.py restates it in numpy.
 
 Not taken over from the paper (out of scope here): its size-residual term as the mean, not the sum, over the three axes (a factor of
-1/3); its overall x 10; proposals sampled by FPS on the votes instead of on the seeds; the BatchNorm momentum schedule; its matching
-against zero-padded box slots."""
+1/3); its overall x 10; the BatchNorm momentum schedule; its matching against zero-padded box slots.  (Proposals sampled by FPS on the
+votes instead of on the seeds are a mode of their own: vote_sampling.py, VoteNetHotPath.enable_proposal_sampling.)"""
 import torch
 
 from . import _lib as L
