@@ -248,7 +248,7 @@ def test_plain_path_a_paper_step_changes_the_vote_term_and_nothing_else(hiplib, 
         assert not torch.equal(bits(off.store.grad), bits(on.store.grad))
     finally:
         M.set_deterministic(prev)
-    assert off.vote_supervision is None and not hasattr(off, "_votesup_work")
+    assert off.vote_supervision is None and not hasattr(off, "_loss_tail_work")
 
 
 def test_graph_path_every_replayed_step_carries_the_paper_term(hiplib, dev):

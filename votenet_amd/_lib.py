@@ -267,6 +267,18 @@ def dev_f32(t, name, rank=None, last=None):
     return t.contiguous()
 
 
+def pitched_rows(t):
+    """Whether t is 3-D rows with unit column stride at one uniform pitch: what a kernel that takes a row pitch reads in place."""
+    return t.dim() == 3 and t.stride(2) == 1 and t.stride(1) >= t.shape[2] and t.stride(0) == t.shape[1] * t.stride(1)
+
+
+def dev_f32_rows(t, name):
+    """A 3-D float32 device tensor for a kernel that takes a row pitch: t itself where pitched_rows(t), else dev_f32's errors or copy."""
+    if isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and pitched_rows(t):
+        return t
+    return dev_f32(t, name, 3)
+
+
 def dev_i32(t, name, rank=None):
     if not isinstance(t, torch.Tensor):
         raise InvalidArgumentError("%s must be a torch.Tensor" % name)

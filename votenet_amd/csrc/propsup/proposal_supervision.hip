@@ -13,6 +13,7 @@
 #include "../common.h"
 #include "../error_text.h"
 #include "../nearest_box.h" // nearest_box, LOSS_MAXBOX: the labels are votenet_loss's, decided with the same instructions
+#include "../scene_fold.h"
 
 #pragma GCC visibility push(default)
 #include "../../../include/votenet_proposal_supervision.h"
@@ -28,8 +29,7 @@ constexpr int PS_MAX_B = 65535;          // scenes: a grid extent
 constexpr int PS_MAX_P = 1024;           // proposals per scene: one per lane of one workgroup
 constexpr int PS_WAVES = PS_MAX_P / 64;
 constexpr int PS_MAXC = 32;              // nh, ns, nc <= 32, as votenet_loss
-constexpr int PS_WS_INTS = 4;            // the workspace: [ticket, pad x 3], then PS_SUMS floats per scene
-constexpr int PS_SUMS = 3;               // per scene: sum of w * ce, sum of e_i over the positives, sum of f_j over the real boxes
+constexpr int PS_SUMS = 3;               // per scene (scene_fold.h): sum of w * ce, sum of e_i over the positives, sum of f_j over the real boxes
 constexpr float PS_W0 = 0.2f, PS_W1 = 0.8f;
 
 struct SceneLds {
@@ -166,8 +166,7 @@ struct PropLossArgs {
     float pos_thr, neg_thr;
     float *losses, *d_pxyz, *d_pout;
     int *counts;
-    int *ticket;    // zero on entry, zeroed again by the last workgroup
-    float *partial; // b x PS_SUMS per-scene sums, likewise
+    int *ticket; // the workspace of scene_fold (PS_SUMS sums per scene): zero on entry, left zero
 };
 
 // One workgroup per scene.  Pass 1: Np, Nn and G of the WHOLE batch, counted by every workgroup for itself (b * p nearest_box calls over
@@ -277,22 +276,9 @@ __global__ __launch_bounds__(PS_MAX_P) void paper_proposal_loss_kernel(PropLossA
     if ((tid & 63) == 0) s_sum[tid >> 6][0] = obj, s_sum[tid >> 6][1] = esum;
     __syncthreads();
     if (tid != 0) return;
-    float v0 = 0.0f, v1 = 0.0f;
-    for (int w = 0; w < nwaves; w++) v0 += s_sum[w][0], v1 += s_sum[w][1];
-    float *part = A.partial + (size_t)own * PS_SUMS;
-    __hip_atomic_store(&part[0], v0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(&part[1], v1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(&part[2], fsum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __threadfence(); // the scene's sums are visible device-wide before the ticket is taken
-    if (__hip_atomic_fetch_add(A.ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != B - 1) return;
-    __threadfence();
-    float t[PS_SUMS] = {0.0f, 0.0f, 0.0f};
-    for (int sc = 0; sc < B; sc++)
-        for (int k = 0; k < PS_SUMS; k++) {
-            t[k] += __hip_atomic_load(&A.partial[(size_t)sc * PS_SUMS + k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(&A.partial[(size_t)sc * PS_SUMS + k], 0.0f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); // left zero
-        }
-    __hip_atomic_store(A.ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    float v[PS_SUMS] = {0.0f, 0.0f, fsum}, t[PS_SUMS];
+    for (int w = 0; w < nwaves; w++) v[0] += s_sum[w][0], v[1] += s_sum[w][1];
+    if (!scene_fold(A.ticket, own, B, v, t)) return;
     float *L = A.losses;
     const float objl = t[0] * inv_m;
     const float center = t[1] * inv_p + t[2] * inv_g;
@@ -310,7 +296,7 @@ using namespace votenet;
 
 extern "C" const char *votenet_propsup_last_error(void) { return g_ps_err.text; }
 
-extern "C" size_t votenet_propsup_workspace_bytes(int b) { return (PS_WS_INTS + (size_t)(b > 0 ? b : 0) * PS_SUMS) * sizeof(float); }
+extern "C" size_t votenet_propsup_workspace_bytes(int b) { return scene_fold_bytes(b, PS_SUMS); }
 
 static int check_shape(const char *who, int b, int p, int bb)
 {
@@ -361,9 +347,8 @@ extern "C" int votenet_paper_proposal_loss(int b, int p, int bb, int nh, int ns,
                         ((rows - 1) * (size_t)output_pitch + width) * sizeof(float)),
                "paper_proposal_loss: d_proposals_output may not overlap proposals_output");
     PS_REQUIRE(reinterpret_cast<uintptr_t>(workspace) % 4 == 0, "paper_proposal_loss: the workspace must be 4-byte aligned");
-    int *ticket = static_cast<int *>(workspace);
     PropLossArgs a = {b, p, bb, width, proposals_xyz, proposals_output, output_pitch, bboxes_xyz, pos_thr, neg_thr, losses,
-                      d_proposals_xyz, d_proposals_output, counts, ticket, reinterpret_cast<float *>(ticket + PS_WS_INTS)};
+                      d_proposals_xyz, d_proposals_output, counts, static_cast<int *>(workspace)};
     hipLaunchKernelGGL(paper_proposal_loss_kernel, dim3(b), dim3((p + 63) / 64 * 64), 0, as_stream(stream), a);
     return g_ps_err.check_launch("paper_proposal_loss");
 }

@@ -11,6 +11,7 @@
 #include "../common.h"
 #include "../error_text.h"
 #include "../nearest_box.h" // LOSS_MAXBOX: the boxes per scene votenet_loss takes
+#include "../scene_fold.h"
 
 #pragma GCC visibility push(default)
 #include "../../../include/votenet_vote_supervision.h"
@@ -27,7 +28,6 @@ constexpr int VS_THREADS = 256;              // four waves
 constexpr int VS_SPT = 4;                    // seeds a lane keeps in registers
 constexpr int VS_TILE = VS_THREADS * VS_SPT; // 1024 seeds: the training shape is one tile per scene
 constexpr int VS_WAVES = VS_THREADS / 64;
-constexpr int VS_WS_INTS = 4;                // the workspace: [ticket, pad x 3], then one float per scene
 
 // The constants of scene `sc`'s boxes into LDS: {cx, cy, cz, c}, {s, hl, hh, hw}.  The trigonometry in double, rounded once.
 __device__ __forceinline__ void stage_boxes(float4 (*s_box)[2], int bb, const float *__restrict__ xyz, const float *__restrict__ lwh,
@@ -125,8 +125,7 @@ struct VoteLossArgs {
     const float *seeds, *votes, *xyz, *lwh, *roty;
     float *losses, *d_votes;
     int *supervised;
-    int *ticket;    // zero on entry, zeroed again by the last workgroup
-    float *partial; // b per-scene sums, likewise
+    int *ticket; // the workspace of scene_fold (one sum per scene): zero on entry, left zero
 };
 
 // One workgroup per scene.  Pass 1: the supervised seeds of the WHOLE batch, counted by every workgroup for itself (b * n * bb closed-box
@@ -211,20 +210,11 @@ __global__ __launch_bounds__(VS_THREADS) void paper_vote_loss_kernel(VoteLossArg
     if ((tid & 63) == 0) s_sum[tid >> 6] = sum;
     __syncthreads();
     if (tid != 0) return;
-    float v = 0.0f;
+    float v[1] = {0.0f}, total[1];
 #pragma unroll
-    for (int w = 0; w < VS_WAVES; w++) v += s_sum[w];
-    __hip_atomic_store(&A.partial[own], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __threadfence(); // the scene's sum is visible device-wide before the ticket is taken
-    if (__hip_atomic_fetch_add(A.ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != B - 1) return;
-    __threadfence();
-    float total = 0.0f;
-    for (int sc = 0; sc < B; sc++) {
-        total += __hip_atomic_load(&A.partial[sc], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(&A.partial[sc], 0.0f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); // the workspace is left zero
-    }
-    __hip_atomic_store(A.ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const float vote = total * inv;
+    for (int w = 0; w < VS_WAVES; w++) v[0] += s_sum[w];
+    if (!scene_fold(A.ticket, own, B, v, total)) return;
+    const float vote = total[0] * inv;
     float *L = A.losses;
     L[0] = vote + 0.5f * L[2] + L[9] + 0.1f * L[8]; // votenet_loss's total (loss.hip), from the components it stored
     L[1] = vote;
@@ -237,7 +227,7 @@ using namespace votenet;
 
 extern "C" const char *votenet_votesup_last_error(void) { return g_vs_err.text; }
 
-extern "C" size_t votenet_votesup_workspace_bytes(int b) { return (VS_WS_INTS + (size_t)(b > 0 ? b : 0)) * sizeof(float); }
+extern "C" size_t votenet_votesup_workspace_bytes(int b) { return scene_fold_bytes(b, 1); }
 
 static int check_shape(const char *who, int b, int n, int bb)
 {
@@ -266,9 +256,7 @@ extern "C" int votenet_paper_vote_loss(int b, int n, int bb, const float *seeds,
     const uintptr_t src = reinterpret_cast<uintptr_t>(votes), dst = reinterpret_cast<uintptr_t>(d_votes);
     VS_REQUIRE(dst + bytes <= src || src + bytes <= dst, "paper_vote_loss: d_votes may not overlap votes");
     VS_REQUIRE(reinterpret_cast<uintptr_t>(workspace) % 4 == 0, "paper_vote_loss: the workspace must be 4-byte aligned");
-    int *ticket = static_cast<int *>(workspace);
-    VoteLossArgs a = {b, n, bb, seeds, votes, xyz, lwh, roty, losses, d_votes, supervised, ticket,
-                      reinterpret_cast<float *>(ticket + VS_WS_INTS)};
+    VoteLossArgs a = {b, n, bb, seeds, votes, xyz, lwh, roty, losses, d_votes, supervised, static_cast<int *>(workspace)};
     hipLaunchKernelGGL(paper_vote_loss_kernel, dim3(b), dim3(VS_THREADS), 0, as_stream(stream), a);
     return g_vs_err.check_launch("paper_vote_loss");
 }

@@ -29,6 +29,22 @@ def loss_buffers(out, losses=None):
     return losses, M._zeros_f32((votes.numel() + pxyz.numel() + pout.numel() + nws,), votes.device)
 
 
+def cotangent_views(votes, pxyz, pout, flat):
+    """The layout of flat (loss_buffers), stated once: votes | proposals_xyz | proposals_output | workspace.  votes, pxyz, pout: tensors
+    of the cotangents' shapes.  -> the three cotangents as views of flat, keyed like out, and the workspace tail."""
+    nv, npx, npo = votes.numel(), pxyz.numel(), pout.numel()
+    cot = dict(votes_xyz=flat[:nv].view_as(votes), proposals_xyz=flat[nv:nv + npx].view_as(pxyz),
+               proposals_output=flat[nv + npx:nv + npx + npo].view_as(pout))
+    return cot, flat[nv + npx + npo:]
+
+
+def check_losses(losses, dev, who):
+    """losses must be the 12 contiguous float32 values of votenet_loss on device dev (the launches behind it change them in place)."""
+    if not (isinstance(losses, torch.Tensor) and losses.is_cuda and losses.dtype == torch.float32 and losses.numel() == 12
+            and losses.is_contiguous() and losses.device == dev):
+        raise L.InvalidArgumentError("%s: losses must be the 12 floats of votenet_loss on the device" % who)
+
+
 def votenet_loss(out, gt, nh=NH, ns=NS, nc=NC, buffers=None):
     """out: the dict VoteNetHotPath.forward returns; gt: device tensors (gt_to_device).
     -> losses (12,) f32 on the device (NAMES), cotangents dict(votes_xyz, proposals_xyz, proposals_output).
@@ -36,10 +52,7 @@ def votenet_loss(out, gt, nh=NH, ns=NS, nc=NC, buffers=None):
     seeds = L.dev_f32(out["seeds_xyz"], "loss seeds_xyz", 3, 3)
     votes = L.dev_f32(out["votes_xyz"], "loss votes_xyz", 3, 3)
     pxyz = L.dev_f32(out["proposals_xyz"], "loss proposals_xyz", 3, 3)
-    pout = out["proposals_output"]
-    if not (isinstance(pout, torch.Tensor) and pout.is_cuda and pout.dtype == torch.float32 and pout.dim() == 3 and pout.stride(2) == 1
-            and pout.stride(1) >= pout.shape[2] and pout.stride(0) == pout.shape[1] * pout.stride(1)):
-        pout = L.dev_f32(pout, "loss proposals_output", 3)  # anything but rows with unit column stride: a contiguous copy
+    pout = L.dev_f32_rows(out["proposals_output"], "loss proposals_output")
     b, n = seeds.shape[:2]
     p = pxyz.shape[1]
     bb = gt["bboxes_xyz"].shape[1]
@@ -47,24 +60,24 @@ def votenet_loss(out, gt, nh=NH, ns=NS, nc=NC, buffers=None):
         raise L.InvalidArgumentError("loss: proposals_output has %d channels, expected %d" % (pout.shape[2], 5 + 2 * nh + 4 * ns + nc))
     dev = seeds.device
     # the three cotangents and the kernel's workspace are ONE buffer cleared by ONE fill
-    nv, npx, npo, nws = votes.numel(), pxyz.numel(), pout.numel(), int(L.lib().votenet_loss_workspace_floats(b))
+    total = votes.numel() + pxyz.numel() + pout.numel() + int(L.lib().votenet_loss_workspace_floats(b))
     from . import mlp as M
     if buffers is not None:
         losses, flat = buffers
-        if flat.numel() != nv + npx + npo + nws or losses.numel() != 12:
+        if flat.numel() != total or losses.numel() != 12:
             raise L.InvalidArgumentError("loss: the buffers were made for other shapes (loss_buffers(out))")
     else:
         losses = torch.empty(12, dtype=torch.float32, device=dev)
-        flat = M._zeros_f32((nv + npx + npo + nws,), dev)  # inside a train step: a carve-out of the pass's one zero fill
-    d_votes, d_pxyz = flat[:nv].view_as(votes), flat[nv:nv + npx].view_as(pxyz)
-    d_pout, ws = flat[nv + npx:nv + npx + npo].view_as(pout), flat[nv + npx + npo:]
+        flat = M._zeros_f32((total,), dev)  # inside a train step: a carve-out of the pass's one zero fill
+    cot, ws = cotangent_views(votes, pxyz, pout, flat)
     with L.device_guard(dev):
         L.check(L.lib().votenet_loss_pitched(b, n, p, bb, nh, ns, nc, L.ptr(seeds), L.ptr(votes), L.ptr(pxyz), L.ptr(pout), pout.stride(1),
                                      L.ptr(gt["bboxes_xyz"]), L.ptr(gt["bboxes_lwh"]), L.ptr(gt["bboxes_roty"]),
                                      L.ptr(gt["semantic_labels"]), L.ptr(gt["heading_labels"]), L.ptr(gt["heading_residuals"]),
                                      L.ptr(gt["size_labels"]), L.ptr(gt["size_residuals"]), POSITIVE_THRES, NEGATIVE_THRES,
-                                     L.ptr(losses), L.ptr(d_votes), L.ptr(d_pxyz), L.ptr(d_pout), L.ptr(ws), L.stream_ptr()))
-    return losses, dict(votes_xyz=d_votes, proposals_xyz=d_pxyz, proposals_output=d_pout)
+                                     L.ptr(losses), L.ptr(cot["votes_xyz"]), L.ptr(cot["proposals_xyz"]), L.ptr(cot["proposals_output"]),
+                                     L.ptr(ws), L.stream_ptr()))
+    return losses, cot
 
 
 ACCURACY_COUNTS = ("n_obj_correct", "n_sem_correct", "n_pos", "n_neg")
@@ -79,10 +92,7 @@ def votenet_accuracies(out, gt, nh=NH, ns=NS, nc=NC, losses=None, ring=None, rin
     (obj_accuracy, sem_accuracy, losses[0], n_pos, n_neg).  buffers: (accuracies, counts, workspace) of a caller that keeps them
     (monitors.Monitors; the workspace is 8 int32 zeros, left zero by every launch)."""
     pxyz = L.dev_f32(out["proposals_xyz"], "accuracies proposals_xyz", 3, 3)
-    pout = out["proposals_output"]
-    if not (isinstance(pout, torch.Tensor) and pout.is_cuda and pout.dtype == torch.float32 and pout.dim() == 3 and pout.stride(2) == 1
-            and pout.stride(1) >= pout.shape[2] and pout.stride(0) == pout.shape[1] * pout.stride(1)):
-        pout = L.dev_f32(pout, "accuracies proposals_output", 3)
+    pout = L.dev_f32_rows(out["proposals_output"], "accuracies proposals_output")
     b, p = pxyz.shape[:2]
     if pout.shape[2] != 5 + 2 * nh + 4 * ns + nc or tuple(pout.shape[:2]) != (b, p):
         raise L.InvalidArgumentError("accuracies: proposals_output has shape %s, expected (%d, %d, %d)"

@@ -319,13 +319,10 @@ class StretchGraph:
             end()
             self.loss_bufs = VL.loss_buffers(out, losses=self._losses)  # (the losses vector: allocated on the caller's stream, below)
             self.loss_at = len(self.segments)  # the loss runs before this segment
-            losses, flat = self.loss_bufs
-            nv, npx = out["votes_xyz"].numel(), out["proposals_xyz"].numel()
-            npo = out["proposals_output"].numel()
-            cot = dict(votes_xyz=flat[:nv].view_as(out["votes_xyz"]), proposals_xyz=flat[nv:nv + npx].view_as(out["proposals_xyz"]),
-                       proposals_output=flat[nv + npx:nv + npx + npo].view_as(out["proposals_output"]))
+            # the cotangents at their fixed addresses: what every replay's loss launch and the launches behind it write
+            self.cot, _ = VL.cotangent_views(out["votes_xyz"], out["proposals_xyz"], out["proposals_output"], self.loss_bufs[1])
             begin()
-            return losses, cot
+            return self.loss_bufs[0], self.cot
         cs.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(cs), P.WGRAD.capturing(keep, defer if STRETCH_SEGMENTS else None):
             begin()
@@ -345,8 +342,8 @@ class StretchGraph:
     def replay(self, ins, gt, wgrad_stream=None, after_loss=None):
         """One copy launch, then the segments in order -- the loss graph on gt as launches where it belongs --; a segment's
         weight-gradient thunks go to wgrad_stream (None: the current one) behind its graph.  The caller joins the weight-gradient stream
-        (pointnet2.wgrad_join) before it reads the gradient bucket.  after_loss(out, gt, losses): called behind the loss launch (the
-        monitors' accuracy launch: a launch between two segments like the loss, no graph is captured again or gets a node)."""
+        (pointnet2.wgrad_join) before it reads the gradient bucket.  after_loss(out, gt, losses, self.cot): called behind the loss launch
+        (VoteNetHotPath._after_loss: launches between two segments like the loss, no graph is captured again or gets a node)."""
         from . import loss as VL
         self.copy_inputs(ins)
         with P.WGRAD.on(wgrad_stream):
@@ -357,7 +354,7 @@ class StretchGraph:
                     losses = self._loss_ring[self.replays % len(self._loss_ring)]
                     VL.votenet_loss(self.out, gt, buffers=(losses, self.loss_bufs[1]))
                     if after_loss is not None:
-                        after_loss(self.out, gt, losses)
+                        after_loss(self.out, gt, losses, self.cot)
                 graph.replay()
                 if thunks and wgrad_stream is not None:
                     P.WGRAD.hand_over([f for f, _ in thunks])  # (their tensors live in the graphs' pool: nothing for the allocator to track)
@@ -916,11 +913,8 @@ class VoteNetHotPath:
         out = self._head_forward(lv, geom("fp1"), geom("fp2"), I["prop_fps"], tail, copy_seeds=copy_seeds)
         self.update_moving_averages(list(tape_levels) + tail)
         losses, cot = loss_hook(out) if loss_hook is not None else VL.votenet_loss(out, gt)
-        if loss_hook is None:
-            self._paper_votes(out, gt, losses, cot["votes_xyz"])
-            self._paper_proposals(out, gt, losses, cot["proposals_xyz"], cot["proposals_output"])
-            if self.monitors is not None:
-                self.last_accuracies = self.monitors.after_loss(out, gt, losses)
+        if loss_hook is None:  # (captured: the loss and what runs behind it are launches of every replay, StretchGraph.replay)
+            self._after_loss(out, gt, losses, cot)
         with P.WGRAD.on(wgrad_stream):
             grads = self._head_backward(tail, cot, cut=cut)
             if cut is None:
@@ -971,21 +965,8 @@ class VoteNetHotPath:
         self._stretch_clock = getattr(self, "_stretch_clock", 0) + 1
         sg.last_used = self._stretch_clock
         self.store._fresh_wait()
-        mon = self.monitors
-        after_loss = mon.after_loss if mon is not None else None
-        if self.vote_supervision == "paper" or self.proposal_supervision == "paper":
-            # into the buffers the next segment reads, then the monitors: their ring records the new total
-            def after_loss(out, gt, losses):
-                flat, nv, npx = sg.loss_bufs[1], out["votes_xyz"].numel(), out["proposals_xyz"].numel()
-                self._paper_votes(out, gt, losses, flat[:nv].view_as(out["votes_xyz"]))
-                self._paper_proposals(out, gt, losses, flat[nv:nv + npx].view_as(out["proposals_xyz"]),
-                                      flat[nv + npx:nv + npx + out["proposals_output"].numel()].view_as(out["proposals_output"]))
-                if mon is not None:
-                    mon.after_loss(out, gt, losses)
         out, self.last_losses, grads = sg.replay(ins, gt, self._wgrad_side(),  # (a vector of the graph's ring: rewritten eight replays later)
-                                                 after_loss=after_loss)
-        if mon is not None:
-            self.last_accuracies = mon.accuracies
+                                                 after_loss=self._after_loss)
         self._ema_version += 1  # (the replay ran votenet_ema_update: inference_bn() must not serve a table built before it)
         self._backward_levels_pass(tape, grads)
         return out
@@ -1082,17 +1063,6 @@ class VoteNetHotPath:
         """Back to the launches of a step with the reference's vote supervision (the default)."""
         self.vote_supervision = None
 
-    def _paper_votes(self, out, gt, losses, d_votes):
-        """Behind votenet_loss, before the monitors' launch: the paper's vote term in place of the reference's (mode "paper" only)."""
-        if self.vote_supervision != "paper":
-            return
-        from . import vote_supervision as VS  # (the only place of a train step that loads libvotenet_votesup.so)
-        b = d_votes.shape[0]
-        work = self.__dict__.setdefault("_votesup_work", {})
-        if b not in work:  # zero once: every launch leaves it zero
-            work[b] = (VS.workspace(b, self.device), torch.empty(1, dtype=torch.int32, device=self.device))
-        VS.paper_vote_loss(out, gt, losses, d_votes=d_votes, supervised=work[b][1], work=work[b][0])
-
     # ---- objectness and centre supervision as in the VoteNet paper (proposal_supervision.py): off unless asked for ----------------
     proposal_supervision = None  # the mode while enable_proposal_supervision is in force (proposal_supervision.MODES); a setting of the run, not checkpoint state
 
@@ -1114,17 +1084,28 @@ class VoteNetHotPath:
         """Back to the launches of a step with the reference's objectness and centre terms (the default)."""
         self.proposal_supervision = None
 
-    def _paper_proposals(self, out, gt, losses, d_xyz, d_out):
-        """Behind votenet_loss and _paper_votes, before the monitors' launch: the paper's objectness and centre terms in place of the
-        reference's (mode "paper" only)."""
-        if self.proposal_supervision != "paper":
-            return
-        from . import proposal_supervision as PS  # (the only place of a train step that loads libvotenet_propsup.so)
-        b = d_xyz.shape[0]
-        work = self.__dict__.setdefault("_propsup_work", {})
-        if b not in work:  # zero once: every launch leaves it zero
-            work[b] = (PS.workspace(b, self.device), torch.empty(3, dtype=torch.int32, device=self.device))
-        PS.paper_proposal_loss(out, gt, losses, d_xyz=d_xyz, d_out=d_out, counts=work[b][1], work=work[b][0])
+    # ---- the launches behind the loss: the launch path, the eager first step of a shape and every replay come here --------------------
+    def _after_loss(self, out, gt, losses, cot):
+        """Behind votenet_loss(out, gt) -> losses, cot and before the backward pass reads cot, in this order, each only while its mode is on
+        (a mode that is off imports and loads nothing): the paper's vote term, the paper's objectness and centre terms (both overwrite
+        their parts of cot and losses in place), the monitors' accuracy launch (last: its ring records the re-formed total)."""
+        if self.vote_supervision == "paper":
+            from . import vote_supervision as VS  # (the only place of a train step that loads libvotenet_votesup.so)
+            work, supervised = self._loss_tail_buffers(VS, out["votes_xyz"].shape[0], 1)
+            VS.paper_vote_loss(out, gt, losses, d_votes=cot["votes_xyz"], supervised=supervised, work=work)
+        if self.proposal_supervision == "paper":
+            from . import proposal_supervision as PS  # (the only place of a train step that loads libvotenet_propsup.so)
+            work, counts = self._loss_tail_buffers(PS, out["proposals_xyz"].shape[0], 3)
+            PS.paper_proposal_loss(out, gt, losses, d_xyz=cot["proposals_xyz"], d_out=cot["proposals_output"], counts=counts, work=work)
+        if self.monitors is not None:
+            self.last_accuracies = self.monitors.after_loss(out, gt, losses)
+
+    def _loss_tail_buffers(self, mod, b, ncounts):
+        """-> (workspace, count tensor) of supervision module mod for b scenes; zeroed once, every launch leaves the workspace zero."""
+        work = self.__dict__.setdefault("_loss_tail_work", {})  # (a net that never ran a paper mode has none)
+        if (mod, b) not in work:
+            work[mod, b] = (mod.workspace(b, self.device), torch.empty(ncounts, dtype=torch.int32, device=self.device))
+        return work[mod, b]
 
     # ---- proposals sampled on the votes as in the VoteNet paper (vote_sampling.py): off unless asked for ---------------------------
     proposal_sampling = None  # the mode while enable_proposal_sampling is in force (vote_sampling.MODES); a setting of the run, not checkpoint state
@@ -1245,10 +1226,7 @@ class VoteNetHotPath:
                 if gt is not None:
                     from . import loss as VL
                     self.last_losses, cot = VL.votenet_loss(out, gt)
-                    self._paper_votes(out, gt, self.last_losses, cot["votes_xyz"])
-                    self._paper_proposals(out, gt, self.last_losses, cot["proposals_xyz"], cot["proposals_output"])
-                    if self.monitors is not None:
-                        self.last_accuracies = self.monitors.after_loss(out, gt, self.last_losses)
+                    self._after_loss(out, gt, self.last_losses, cot)
                 self._gsync.begin()
                 if PREFETCH_AFTER >= 5:  # the next batch's geometry chain under the BACKWARD pass
                     for nx, nf in self._pair_next(next_x, next_feats):

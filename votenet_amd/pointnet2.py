@@ -933,7 +933,7 @@ def add_rows(a, b):
     def two_d(t):
         if t.is_contiguous():
             return t.view(rows, c)
-        if t.dim() == 3 and t.stride(2) == 1 and t.stride(0) == t.shape[1] * t.stride(1):
+        if M.L.pitched_rows(t):
             return t.as_strided((rows, c), (t.stride(1), 1), t.storage_offset())
         return t.contiguous().view(rows, c)
     M.row_segments(rows, [(out.view(rows, c), two_d(a), two_d(b))])

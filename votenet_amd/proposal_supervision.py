@@ -20,7 +20,7 @@ votes instead of on the seeds are a mode of their own: vote_sampling.py, VoteNet
 import torch
 
 from . import _lib as L
-from .loss import NEGATIVE_THRES, POSITIVE_THRES
+from .loss import NEGATIVE_THRES, POSITIVE_THRES, check_losses
 from .synth import NC, NH, NS
 
 MODES = ("reference", "paper")  # "reference": the rule of votenet_loss itself, no launch of this library
@@ -30,10 +30,7 @@ OBJ_WEIGHTS = (0.2, 0.8)        # the class weights of the objectness cross-entr
 def _scene(out, gt, who, width=None):
     """-> proposals_xyz, proposals_output (rows with unit column stride, read in place), bboxes_xyz, (b, p, bb): validated, on one device."""
     pxyz = L.dev_f32(out["proposals_xyz"], "%s proposals_xyz" % who, 3, 3)
-    pout = out["proposals_output"]
-    if not (isinstance(pout, torch.Tensor) and pout.is_cuda and pout.dtype == torch.float32 and pout.dim() == 3 and pout.stride(2) == 1
-            and pout.stride(1) >= pout.shape[2] and pout.stride(0) == pout.shape[1] * pout.stride(1)):
-        pout = L.dev_f32(pout, "%s proposals_output" % who, 3)  # anything but rows with unit column stride: a contiguous copy
+    pout = L.dev_f32_rows(out["proposals_output"], "%s proposals_output" % who)
     b, p = pxyz.shape[:2]
     if tuple(pout.shape[:2]) != (b, p) or (width is not None and pout.shape[2] != width) or pout.shape[2] < 5:
         raise L.InvalidArgumentError("%s: proposals_output has shape %s, expected (%d, %d, %s)"
@@ -80,9 +77,7 @@ def paper_proposal_loss(out, gt, losses, d_xyz=None, d_out=None, counts=None, wo
     width = 5 + 2 * nh + 4 * ns + nc
     pxyz, pout, gxyz, (b, p, bb) = _scene(out, gt, "paper_proposal_loss", width)
     dev = pxyz.device
-    if not (isinstance(losses, torch.Tensor) and losses.is_cuda and losses.dtype == torch.float32 and losses.numel() == 12
-            and losses.is_contiguous() and losses.device == dev):
-        raise L.InvalidArgumentError("paper_proposal_loss: losses must be the 12 floats of votenet_loss on the device")
+    check_losses(losses, dev, "paper_proposal_loss")
     if d_xyz is None:
         d_xyz = torch.empty((b, p, 3), dtype=torch.float32, device=dev)
     if d_out is None:

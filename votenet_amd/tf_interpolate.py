@@ -72,7 +72,7 @@ def three_interpolate_grad_raw(m, idx, weight, grad_out):
         grad_out = L.dev_f32(grad_out, "ThreeInterpolateGrad expects (b,n,c) grad_out shape", 3)
     b, n, c = grad_out.shape
     strided = not grad_out.is_contiguous()
-    if strided and not (grad_out.stride(2) == 1 and grad_out.stride(0) == n * grad_out.stride(1) and grad_out.stride(1) >= c):
+    if strided and not L.pitched_rows(grad_out):
         grad_out, strided = grad_out.contiguous(), False
     from . import mlp as M
     if (M.DETERMINISTIC or GATHER_GRAD) and c <= 256 and getattr(idx, "_inv", None) is not None:

@@ -12,6 +12,7 @@ losses[1] (vote_reg_loss) and re-forms losses[0]; everything else of the step is
 import torch
 
 from . import _lib as L
+from .loss import check_losses
 
 MODES = ("reference", "paper")  # "reference": the rule of votenet_loss itself, no launch of this library
 MAX_BOXES = 256                 # LOSS_MAXBOX, as votenet_loss
@@ -62,9 +63,7 @@ def paper_vote_loss(out, gt, losses, d_votes=None, supervised=None, work=None):
     dev = seeds.device
     if tuple(votes.shape) != (b, n, 3) or votes.device != dev:
         raise L.InvalidArgumentError("paper_vote_loss: votes_xyz of shape %s for seeds of shape %s" % (tuple(votes.shape), tuple(seeds.shape)))
-    if not (isinstance(losses, torch.Tensor) and losses.is_cuda and losses.dtype == torch.float32 and losses.numel() == 12
-            and losses.is_contiguous() and losses.device == dev):
-        raise L.InvalidArgumentError("paper_vote_loss: losses must be the 12 floats of votenet_loss on the device")
+    check_losses(losses, dev, "paper_vote_loss")
     if d_votes is None:
         d_votes = torch.empty_like(votes)
     if not (isinstance(d_votes, torch.Tensor) and d_votes.is_cuda and d_votes.dtype == torch.float32 and d_votes.is_contiguous()
