@@ -27,6 +27,7 @@ SIDE_LIBS = {
     "votesup": "votenet_vote_supervision.h",  # the paper's vote supervision, one launch behind the loss
     "propsup": "votenet_proposal_supervision.h",  # the paper's objectness and centre supervision, one launch behind the loss
     "votesamp": "votenet_vote_sampling.h",   # the proposal module's clusters sampled on the votes, one launch
+    "instbox": "votenet_instance_boxes.h",   # ground-truth boxes from instance-labelled points
 }
 _side = {}  # name -> (the loaded library, its *_last_error function)
 

@@ -71,6 +71,9 @@ SIDE_LIBS=(
   # decided by the same un-fused expressions (ball_threshold.h is the text of votenet_query_ball_point's threshold);
   # -fno-slp-vectorize as box_points.hip: the three axes' products would pack likewise
   "votesamp vote_sampling.hip  votesamp -fno-slp-vectorize"
+  # ground-truth boxes from instance-labelled points.  No contraction, as everywhere: tests/instance_boxes_ref.py restates the rule and
+  # every output is compared by bit pattern (the combinations are integer atomics; the only float arithmetic is the rows' in double)
+  "instbox  instance_boxes.hip instbox"
 )
 side_lib() { # directory, source, library name, extra flags ...
   local dir="$HERE/$1" src="$HERE/$1/$2" lib="libvotenet_$3.so" obj="$HERE/$1/obj/$(basename "${2%.hip}").o" tmp

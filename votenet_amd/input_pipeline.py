@@ -6,6 +6,8 @@ side) and pads the ragged ground truth in BatchData2Biggest (run.py:14-24,60-64)
 reference's order, and the work is two kernels over the whole batch (votenet_subsample_augment, votenet_augment_boxes).
 Which labelled objects a scene trains on (dataset.py:237-283,300: image frustum, 3D box, at least 5 points) is decided on
 the device too (votenet_select_boxes); build_batch chains the three from parsed scene files (sunrgbd.py) to the model's inputs.
+Scenes without annotated boxes -- an instance id and a semantic label per point -- go through build_batch_from_labels, whose boxes are
+the extents of the instances in the augmented points (instance_boxes.py; beyond the reference).
 There is no CPU path: without libvotenet_hip.so these functions raise.
 """
 import ctypes
@@ -292,6 +294,60 @@ def build_batch(raw, raw_offset, calib, objects, aug=None, choice=None, seed=0, 
             aug = Augmentation(aug.flip_x[scene_index], aug.flip_z[scene_index], aug.angle[scene_index], aug.scale[scene_index])
     box_offset = np.concatenate([[0], np.cumsum(cnt[scene_index])]).astype(np.int64)
     gt = augment_boxes(sel["center"], sel["size"], sel["heading"], sel["cls"], box_offset, aug)
+    if feats is not None:
+        gt["features"] = feats
+    return points, gt, scene_index
+
+
+def _ragged_labels(t, total, dev, name):
+    """(sum n_s) int32 labels beside raw's rows, host or device -> on the device."""
+    t = t if torch.is_tensor(t) else torch.from_numpy(np.ascontiguousarray(t))
+    if t.dim() != 1 or t.shape[0] != total or t.dtype != torch.int32:
+        raise L.InvalidArgumentError("build_batch_from_labels: %s must be %d int32 labels, one per row of raw, got %s %s"
+                                     % (name, total, t.dtype, tuple(t.shape)))
+    return t.to(dev)
+
+
+def build_batch_from_labels(raw, raw_offset, instance, semantic, class_map, choice, aug=None, n_out=POINT_NUM, k=256, min_points=1,
+                            height=False, extra_cols=0):
+    """Scenes without annotated boxes -> model inputs: raw, raw_offset, aug, n_out, height, extra_cols as for build_batch; instance,
+    semantic (sum n_s) int32, host or device: an instance id (negative: none) and a semantic label per row of raw; class_map (n_sem)
+    int32: label -> class of the network, or -1; choice (b, n_out), host or device (draw_choice makes one): the rows
+    subsample_augment picks, by which the labels are gathered on the device.  The boxes are the extents of the instances in the
+    AUGMENTED points (instance_boxes.boxes_from_labels: ids in [0, k), at least min_points points), so they are axis-aligned in the
+    frame the network sees, and augment_boxes encodes them without a draw.
+    -> (points, gt, scene_index) with build_batch's contract; a scene that keeps no box is dropped."""
+    from . import instance_boxes as IB  # (the only place of this module that loads libvotenet_instbox.so)
+    if choice is None:
+        raise L.InvalidArgumentError("build_batch_from_labels: choice is required (draw_choice makes one): the labels follow its rows")
+    raw, off, b, ch = _check_raw(raw, raw_offset, n_out, choice, "build_batch_from_labels")
+    if aug is not None and aug.b != b:
+        raise L.InvalidArgumentError("build_batch_from_labels: %d scenes but %d augmentation draws" % (b, aug.b))
+    if np.any(np.diff(off) < 1):
+        raise L.InvalidArgumentError("build_batch_from_labels: a scene has no points")
+    dev = raw.device
+    instance = _ragged_labels(instance, raw.shape[0], dev, "instance")
+    semantic = _ragged_labels(semantic, raw.shape[0], dev, "semantic")
+    feats = None
+    if height or extra_cols:
+        points, feats, _ = subsample_augment_features(raw, raw_offset, n_out, aug, ch, height=height, extra_cols=extra_cols)
+    else:
+        points = subsample_augment(raw, raw_offset, n_out, aug, ch)
+    # the rows the point kernel reads: raw_offset[s] + the choice clamped into the scene, as the kernel clamps it
+    start = torch.from_numpy(off[:-1].copy()).to(dev)[:, None]
+    last = torch.from_numpy(np.diff(off) - 1).to(dev)[:, None]
+    rows = start + torch.minimum(ch.to(torch.int64).clamp(min=0), last)
+    boxes = IB.boxes_from_labels(points, instance[rows], semantic[rows], class_map, k=k, min_points=min_points)
+    cnt = np.diff(boxes["box_offset"])
+    scene_index = np.nonzero(cnt > 0)[0].astype(np.int64)
+    if len(scene_index) == 0:
+        return None, None, scene_index
+    if len(scene_index) < b:
+        keep = torch.from_numpy(scene_index).to(dev)
+        points = points[keep]
+        feats = feats[keep] if feats is not None else None
+    box_offset = np.concatenate([[0], np.cumsum(cnt[scene_index])]).astype(np.int64)  # (the rows are compact: a dropped scene has none)
+    gt = augment_boxes(boxes["center"], boxes["size"], boxes["heading"], boxes["cls"], box_offset, None)
     if feats is not None:
         gt["features"] = feats
     return points, gt, scene_index
