@@ -445,6 +445,23 @@ class FPGeometry(NamedTuple):
         yield self.weight
 
 
+class FirstLayerGrad(NamedTuple):
+    """What mlp_chain_backward hands to SAModule._first_layer_backward where the chain stops at a gather or an assembled first layer.
+    Which fields are set says which of three cases it is:
+      dz                   the first layer's dz (rows, cout), written out;
+      da, coef, relu       the fused first-layer kernels form dz themselves from the gradient da of the layer's activation and the
+                           layer's BatchNorm-backward coefficients (coef set, dz not);
+      da, relu, bn, tail   the pass decomposed over the points (piece layout) reduces the layer's BatchNorm backward itself: it takes
+                           the layer's (scale, shift, mean, var) and the tail of tail_of() and produces the coefficients (neither dz
+                           nor coef set)."""
+    dz: torch.Tensor = None
+    da: torch.Tensor = None
+    coef: torch.Tensor = None
+    relu: bool = None
+    bn: tuple = None
+    tail: tuple = None
+
+
 class DenseInput(NamedTuple):
     """Chain input: rows x (rows, cin).  padded: [x | 0] at the first layer's padded width, when the caller built it (x = padded[:, :cin])."""
     x: torch.Tensor
@@ -479,6 +496,25 @@ class AssembledInput(NamedTuple):
     half: object = None
 
 
+# ---- a layer's record: a plain dict, one per layer on the chain's tape.  Who sets which key, and who reads it:
+#   every record (_close_layer)   layer, rows, z (the raw output; None: never stored), pool (the epilogue's raw max / min, for
+#                                 bn_pool_finalize); a BatchNorm'ed layer also scale, shift, mean, var (bn_of), bn_out (the block the
+#                                 finalize writes: model.py reads it) and bn_pass (check_bn_block); inference mode: scale, shift only
+#   kind                          'dense' | 'gather' | 'narrow' | 'assembled': the form of the layer's INPUT (backward: _bn_arm,
+#                                 _bwd_written_out; SAModule.backward and _first_layer_backward on the first record)
+#   kind 'dense'                  x (the input as the GEMM read it, None above a narrow / assembled first layer), in_scale, in_shift,
+#                                 in_relu: the BatchNorm + ReLU of the layer below, folded into this layer's loads
+#     cin_padded                  x is [x | 0] at Layer.cin_pad (_first_dense -> _bwd_padded_input)
+#     padded                      a plain layer on the copies padded to Layer.cout_pad, z = z_p[:, :cout] (-> _bwd_plain)
+#     gram_form, in_affine,       the pooled last layer (mlp_chain_forward -> _bwd_pooled_gram; model.py reads gram_form / in_affine
+#       cout, half                and leaves the Gram matrix it launched ahead in gram_ahead, which the lane's thunk pops)
+#     narrow, mask0, half         the second layer above a narrow first layer (_first_narrow -> _bwd_above_narrow)
+#     assembled, half             the second layer above an assembled first layer (_first_assembled -> _bwd_above_assembled)
+#   kind 'gather'                 xyz, new_xyz, feat, idx (_first_gather -> _bn_arm, _first_layer_backward)
+#   kind 'narrow'                 u8, mom, half (_first_narrow -> _bwd_above_narrow); z is None
+#   kind 'assembled'              xyz, new_xyz, feat, idx, geo, P, wx, half, cntv, mom (_first_assembled -> _bwd_above_assembled and the
+#                                 _first_piece_layout / _first_full_layout arms of _first_layer_backward); z is None
+#   half                          the chain's resolved mlp.HalfLayout (piece layout) or None; bench.py reads it off the first record
 def _close_layer(L, rows, rec, z, st, tape, pool=None):
     """Behind a layer's launch: its BatchNorm as an mlp.PendingBN on the raw sums st (inference mode: the frozen table's entry; a
     plain layer: None), the layer's record completed and appended to the tape.  -> that BatchNorm."""
@@ -764,162 +800,209 @@ def check_bn_block(rec):
                                "the same net)" % (rec["layer"].name, n))
 
 
+# ---- backward of a chain: one handler per form of a layer's record r (below: the record of the layer below, None at the first),
+# mirroring _first_dense ... _first_assembled.  -> (the gradient that goes on, the BatchNorm-backward coefficients its kernel already
+# produced for the layer below or None, True when the chain ends here).  Weight gradients go to the lane as closures over the handler's
+# locals: they run LATER, so a handler never rebinds a name its closure reads (the gradient it computes gets a name of its own).
+def bn_of(rec):
+    """A record's BatchNorm quadruple."""
+    return rec["scale"], rec["shift"], rec["mean"], rec["var"]
+
+
+def below_of(rec, with_z=False):
+    """The 'layer below' tuple of the kernels that reduce that layer's BatchNorm backward in their epilogue: (scale, shift, mean, var,
+    relu) for pool_dgrad / assembled_dgrad_bn_reduce / narrow_dgrad_bn_reduce, with the layer's z in front for dgrad_bn."""
+    if with_z:
+        return rec["z"], rec["scale"], rec["shift"], rec["mean"], rec["var"], rec["layer"].relu
+    return rec["scale"], rec["shift"], rec["mean"], rec["var"], rec["layer"].relu
+
+
+def tail_of(rec):
+    """What a kernel's tail needs to turn a layer's BatchNorm-backward sums into its coefficient vector (and d gamma, d beta)."""
+    Lr = rec["layer"]
+    return (rec["rows"], Lr.p("gamma"), Lr.gp("gamma"), Lr.gp("beta"))
+
+
+def _bwd_pooled_gram(r, below, gout, argmax, zsel, k, want_da):
+    # Gram form (pool_bwd.hip).  The short dependent chain reduce -> coef -> prepare goes first, alone on the GPU; the
+    # weight-gradient stream (x^T x, arg-max rows, finish) starts beside the dense GEMM that follows it
+    L = r["layer"]
+    x, aff, W, b, half = r["x"], r["in_affine"], L.p("W"), L.p("b"), r.get("half")
+    coef = M.bn_backward_reduce_pool(gout, zsel, *bn_of(r), L.relu, tail=tail_of(r))
+    mm = M.pool_dgrad_prepare(W, b, coef, x.shape[0]) if want_da else None
+
+    def wgrad():
+        G = r.pop("gram_ahead", None)  # the Gram matrix depends on forward data only: train_step may have launched it ahead
+        if G is None:
+            G = M.gram(x, aff[:2], r["in_relu"], half=half)
+        M.pool_wgrad(x, r["in_scale"], r["in_shift"], r["in_relu"], G, W, b, coef, L.relu, gout, argmax, zsel, k, L.gp("W"), half=half)
+    on_wgrad_stream(wgrad, x, aff, coef, gout, argmax, zsel)
+    if not want_da:
+        return None, None, False
+    if below is not None and below["layer"].bn and below["z"] is x:
+        da_below, coef_below = M.pool_dgrad(x, r["in_scale"], r["in_shift"], r["in_relu"], W, b, L.wT(), coef, L.relu, gout, argmax, zsel, k,
+                                            below=below_of(below), mm=mm, below_tail=tail_of(below), half=half)
+        return da_below, coef_below, False
+    return M.pool_dgrad(x, r["in_scale"], r["in_shift"], r["in_relu"], W, b, L.wT(), coef, L.relu, gout, argmax, zsel, k, mm=mm,
+                        half=half), None, False
+
+
+# The BatchNorm'ed arms: (r, below, da, coef, pool, want_da); coef: the layer's own coefficients, pool: (argmax, k) when da is the
+# pooled gout.  d bias of a BatchNorm'ed layer is identically zero (BN removes the mean): left at 0.
+def _bwd_above_assembled(r, r0, da, coef, pool, want_da):
+    # second layer above an ASSEMBLED first layer (i == 1): both GEMMs rebuild z0 from geo + P; the input-gradient GEMM's
+    # epilogue reduces the first layer's BatchNorm backward on the rebuilt z0
+    L, z = r["layer"], r["z"]
+    geo, Pt, wx, half = r0["geo"], r0["P"], r0["wx"], r0["half"]
+    on_wgrad_stream(lambda: M.assembled_wgrad_bn(geo, Pt, wx, r["in_scale"], r["in_shift"], r["in_relu"], z, coef, L.relu, da, L.gp("W"),
+                                                 half=half), geo, Pt, z, coef, da)
+    if ASSEMBLED_DECOMPOSED and half is not None and r0["layer"].bn and r0.get("cntv") is not None:
+        # the first layer's backward decomposed over the points (csrc/half.hip): a PLAIN input-gradient GEMM here -- no epilogue
+        # that gathers the per-point table --; the pass over the rows bucketed by point that follows (SAModule.
+        # _first_layer_backward) reduces the first layer's BatchNorm backward itself
+        da0 = M.dgrad_bn_half(z, coef, L.relu, L.wT(), da, half)
+        return FirstLayerGrad(da=da0, relu=r0["layer"].relu, bn=bn_of(r0), tail=tail_of(r0)), None, True
+    da0, coef0 = M.assembled_dgrad_bn_reduce(z, coef, L.relu, L.wT(), da, geo, Pt, wx, below_of(r0), below_tail=tail_of(r0), half=half)
+    return da0, coef0, False
+
+
+def _bwd_above_narrow(r, r0, da, coef, pool, want_da):
+    # second layer above a NARROW first layer (i == 1): both GEMMs rebuild z0 from u8; the input-gradient GEMM stores
+    # nothing -- its epilogue leaves the first layer's BatchNorm-backward sums and the data term of its weight gradient
+    L, z = r["layer"], r["z"]
+    L0, u8, mom, half = r0["layer"], r0["u8"], r0["mom"], r0["half"]
+    w0, b0 = L0.p("W"), L0.p("b")
+    on_wgrad_stream(lambda: M.narrow_wgrad_bn(u8, w0, b0, r["in_scale"], r["in_shift"], r["in_relu"], z, coef, L.relu, da, L.gp("W"),
+                                              half=half), u8, z, coef, da)
+    coef0, ug = M.narrow_dgrad_bn_reduce(z, coef, L.relu, L.wT(), da, u8, w0, b0, below_of(r0), tail=tail_of(r0), half=half,
+                                         mask=r.get("mask0") if M.NARROW_MASK else None)
+    M.narrow_wgrad_first(mom, ug, coef0, w0, b0, L0.gp("W"))
+    return None, None, True  # a leaf: nothing upstream takes a gradient
+
+
+def _bwd_padded_input(r, below, da, coef, pool, want_da):
+    # the layer on [x | 0] and [W ; 0]: dW through a padded scratch (its rows >= cin multiply zeros), da = dz [W ; 0]^T
+    L, z = r["layer"], r["z"]
+
+    def wgrad():
+        G = M._zeros_f32((L.cin_pad, L.cout), z.device)
+        M.wgrad_dense_bn(r["x"], z, coef, L.relu, G, da=da)
+        gw = L.gp("W")
+        M.row_segments(L.cin, [(gw, gw, G[:L.cin])])  # dW += the scratch's first cin rows (in place, one launch)
+    on_wgrad_stream(wgrad, r["x"], z, coef, da)
+    if not want_da:
+        return None, None, False
+    return M.dgrad_bn(z, coef, L.relu, L.store.padded_rows(L.name + "/W", L.cin_pad, transpose=True), da=da)[:, :L.cin], None, False
+
+
+def _bwd_fused_dense(r, below, da, coef, pool, want_da):
+    # dz never materialised: both GEMMs rebuild it from (da | gout, z, coef) in their loaders
+    L, z = r["layer"], r["z"]
+    src = dict(gout=da, argmax=pool[0], k=pool[1]) if pool else dict(da=da)
+    on_wgrad_stream(lambda: M.wgrad_dense_bn(r["x"], z, coef, L.relu, L.gp("W"), in_scale=r["in_scale"], in_shift=r["in_shift"],
+                                             in_relu=r["in_relu"], **src), r["x"], z, coef, da, pool[0] if pool else None)
+    if not want_da:
+        return None, None, False
+    if FUSE_BN_REDUCE and not pool and below is not None and below["layer"].bn and below["z"] is r["x"]:
+        # the layer below's BatchNorm-backward sums come out of this GEMM's store epilogue
+        da_below, coef_below = M.dgrad_bn(z, coef, L.relu, L.wT(), da=da, below=below_of(below, with_z=True), below_tail=tail_of(below))
+        return da_below, coef_below, False
+    return M.dgrad_bn(z, coef, L.relu, L.wT(), **src), None, False
+
+
+def _bwd_first_fused(r, below, da, coef, pool, want_da):
+    # an assembled or gather first layer whose dz is formed inside votenet_group_linear_backward[_assembled]: the module finishes it
+    return FirstLayerGrad(da=da, coef=coef, relu=r["layer"].relu), None, True
+
+
+def _bwd_unfused(r, below, da, coef, pool, want_da):
+    dz = M.bn_backward_apply(r["z"], coef, r["layer"].relu, da, argmax=pool[0] if pool else None, k=pool[1] if pool else 0)
+    return _bwd_written_out(r, below, dz, want_da)
+
+
+def _bwd_written_out(r, below, dz, want_da):
+    """The plain GEMMs on a dz that exists in memory (unfused BatchNorm'ed layer, plain layer)."""
+    L = r["layer"]
+    if below is None and r["kind"] == "gather":
+        return FirstLayerGrad(dz=dz), None, True  # the module finishes the first layer: it owns idx / pts_cnt / the tables
+    on_wgrad_stream(lambda: M.wgrad_dense(r["x"], dz, L.gp("W"), r["in_scale"], r["in_shift"], r["in_relu"]), dz, r.get("x"))
+    return (M.linear_dense(dz, L.wT(), want_stats=False)[0] if want_da else None), None, False  # da_prev = dz W^T
+
+
+def _bwd_plain(r, below, dz, want_da, g_padded):
+    """A layer without BatchNorm: dz is the gradient that arrived.  g_padded: the caller's [dz | 0] (last layer only), or None."""
+    L = r["layer"]
+    # (a weight gradient like the others: on their stream -- the two launches of a column sum were 31 us of the main chain per step)
+    on_wgrad_stream(lambda: M.bias_grad(dz, L.gp("b")), dz)
+    if not r.get("padded"):
+        return _bwd_written_out(r, below, dz, want_da)
+    # the layer on the padded copies: dz -> [dz | 0] (rows, cout_pad); dW through a padded scratch, da = dz_p [W | 0]^T
+    if g_padded is not None and g_padded.shape[1] == L.cout_pad:
+        dzp = g_padded
+    else:
+        dzp = torch.empty((dz.shape[0], L.cout_pad), dtype=torch.float32, device=dz.device)
+        M.row_segments(dz.shape[0], [(dzp[:, :L.cout], dz, None), (dzp[:, L.cout:], None, None)])
+
+    def wgrad():
+        G = M._zeros_f32((L.cin, L.cout_pad), dzp.device)
+        M.wgrad_dense(r["x"], dzp, G, r["in_scale"], r["in_shift"], r["in_relu"])
+        gw = L.gp("W")
+        M.row_segments(L.cin, [(gw, gw, G[:, :L.cout])])  # dW += the scratch's first cout columns (in place, one launch)
+    on_wgrad_stream(wgrad, dzp, r.get("x"))
+    if not want_da:
+        return None, None, False
+    return M.linear_dense(dzp, L.store.padded(L.name + "/W", L.cout_pad, transpose=True), want_stats=False)[0], None, False
+
+
 def mlp_chain_backward(recs, g, mode, argmax=None, k=0, need_input_grad=True, zsel=None, g_padded=None):
     """Backward of mlp_chain_forward.  g / mode describe the gradient arriving at the LAST layer:
          'pool'  : g = gout (rows/k, c) of the max over k of relu(bn(z))      (SA layers, utils.py:132)
          'act'   : g = dy (rows, c) of y = relu(bn(z))                         (FP layers)
          'plain' : g = dz (rows, c) of a last layer without BN / activation    (mlp2, voting)
-    Accumulates parameter gradients into the store's gradient bucket.  Returns the gradient with respect to the
-    chain's input (rows, cin) for a dense input.  For a gather input it stops at the first layer and returns either
-    dict(dz=...) (rows, cout) or dict(da=, coef=, relu=) when the fused first-layer backward kernel will form dz itself:
-    SAModule.backward finishes the layer (weight gradient, point gradients)."""
-    da = g
-    coef_ahead = None  # BatchNorm-backward coefficients of layer i already produced by the layer above (the reduce rides in its
-    #                    scatter pass / GEMM epilogue, the coefficient vector in that kernel's tail)
-
-    def tail_of(rec):
-        Lr = rec["layer"]
-        return (rec["rows"], Lr.p("gamma"), Lr.gp("gamma"), Lr.gp("beta"))
+    Accumulates parameter gradients into the store's gradient bucket.  Returns
+         a tensor         : the gradient with respect to the chain's dense input (rows, cin), when need_input_grad;
+         None             : a dense input with need_input_grad=False, or a narrow first layer (a leaf: its weight gradient is done);
+         a FirstLayerGrad : a gather or an assembled first layer -- the chain stops there and SAModule._first_layer_backward
+                            finishes the layer (weight gradient, point gradients)."""
     for r in recs:
         check_bn_block(r)
-    for i in range(len(recs) - 1, -1, -1):
-        r = recs[i]
+    last = len(recs) - 1
+    da = g
+    coef_from_above = None  # BatchNorm-backward coefficients of layer i that the kernel of layer i + 1 already produced (the reduce
+    #                         rides in its scatter pass / GEMM epilogue, the coefficient vector in that kernel's tail)
+    for i in range(last, -1, -1):
+        r, below = recs[i], recs[i - 1] if i > 0 else None
         L = r["layer"]
-        z = r["z"]
-        pooled = (mode == "pool" and i == len(recs) - 1)
+        pooled = mode == "pool" and i == last
         want_da = i > 0 or need_input_grad
         if pooled and r.get("gram_form") and zsel is not None:
-            # Gram form (pool_bwd.hip).  The short dependent chain reduce -> coef -> prepare goes first, alone on the GPU; the
-            # weight-gradient stream (x^T x, arg-max rows, finish) starts beside the dense GEMM that follows it
-            x, aff, W, b = r["x"], r["in_affine"], L.p("W"), L.p("b")
-            bn = (r["scale"], r["shift"], r["mean"], r["var"])
-            coef = M.bn_backward_reduce_pool(da, zsel, *bn, L.relu, tail=tail_of(r))
-            mm = M.pool_dgrad_prepare(W, b, coef, x.shape[0]) if want_da else None
-            half = r.get("half")
-            def _pooled_wgrad(x=x, aff=aff, r=r, W=W, b=b, coef=coef, L=L, da=da, half=half):
-                G = r.pop("gram_ahead", None)  # the Gram matrix depends on forward data only: train_step may have launched it ahead
-                if G is None:
-                    G = M.gram(x, aff[:2], r["in_relu"], half=half)
-                M.pool_wgrad(x, r["in_scale"], r["in_shift"], r["in_relu"], G, W, b, coef, L.relu, da, argmax, zsel, k, L.gp("W"), half=half)
-            on_wgrad_stream(_pooled_wgrad, x, aff, coef, da, argmax, zsel)
-            if not want_da:
-                return None
-            below = recs[i - 1]
-            if below["layer"].bn and below["z"] is x:
-                da, coef_ahead = M.pool_dgrad(x, r["in_scale"], r["in_shift"], r["in_relu"], W, b, L.wT(), coef, L.relu, da, argmax,
-                                              zsel, k, below=(below["scale"], below["shift"], below["mean"], below["var"],
-                                                              below["layer"].relu), mm=mm, below_tail=tail_of(below), half=half)
-            else:
-                da = M.pool_dgrad(x, r["in_scale"], r["in_shift"], r["in_relu"], W, b, L.wT(), coef, L.relu, da, argmax, zsel, k, mm=mm,
-                                  half=half)
-            continue
-        rows, c = r["rows"], L.cout  # z is None for a first layer that is never stored (narrow / assembled)
-        if L.bn:
-            bn = (r["scale"], r["shift"], r["mean"], r["var"])
-            if coef_ahead is not None:
-                coef, coef_ahead = coef_ahead, None
-            else:
-                coef = M.bn_backward_reduce(z, *bn, L.relu, da, argmax=argmax if pooled else None, k=k if pooled else 0,
+            step = _bwd_pooled_gram(r, below, da, argmax, zsel, k, want_da)
+        elif not L.bn:
+            step = _bwd_plain(r, below, da, want_da, g_padded if i == last else None)
+        else:
+            coef = coef_from_above
+            if coef is None:  # (z is None for a first layer that is never stored: its coefficients always come from above)
+                coef = M.bn_backward_reduce(r["z"], *bn_of(r), L.relu, da, argmax=argmax if pooled else None, k=k if pooled else 0,
                                             tail=tail_of(r))
-            # d bias of a BatchNorm'ed layer is identically zero (BN removes the mean): left at 0
             if r.get("assembled"):
-                # second layer above an ASSEMBLED first layer (i == 1): both GEMMs rebuild z0 from geo + P; the input-gradient GEMM's
-                # epilogue reduces the first layer's BatchNorm backward on the rebuilt z0
-                r0 = recs[0]
-                geo, Pt, wx, half = r0["geo"], r0["P"], r0["wx"], r0["half"]
-                on_wgrad_stream(lambda r=r, z=z, coef=coef, L=L, da=da: M.assembled_wgrad_bn(
-                    geo, Pt, wx, r["in_scale"], r["in_shift"], r["in_relu"], z, coef, L.relu, da, L.gp("W"), half=half), geo, Pt, z, coef, da)
-                if ASSEMBLED_DECOMPOSED and half is not None and r0["layer"].bn and r0.get("cntv") is not None:
-                    # the first layer's backward decomposed over the points (csrc/half.hip): a PLAIN input-gradient GEMM here -- no epilogue
-                    # that gathers the per-point table --; the pass over the rows bucketed by point that follows (SAModule.
-                    # _first_layer_backward) reduces the first layer's BatchNorm backward itself
-                    da = M.dgrad_bn_half(z, coef, L.relu, L.wT(), da, half)
-                    return dict(da=da, decomposed=True, relu=r0["layer"].relu, tail=tail_of(r0),
-                                bn=(r0["scale"], r0["shift"], r0["mean"], r0["var"]))
-                da, coef_ahead = M.assembled_dgrad_bn_reduce(z, coef, L.relu, L.wT(), da, geo, Pt, wx,
-                                                              (r0["scale"], r0["shift"], r0["mean"], r0["var"], r0["layer"].relu),
-                                                              below_tail=tail_of(r0), half=half)
-                continue
-            if r.get("narrow"):
-                # second layer above a NARROW first layer (i == 1): both GEMMs rebuild z0 from u8; the input-gradient GEMM stores
-                # nothing -- its epilogue leaves the first layer's BatchNorm-backward sums and the data term of its weight gradient
-                r0 = recs[0]
-                L0, u8, mom, half = r0["layer"], r0["u8"], r0["mom"], r0["half"]
-                w0, b0 = L0.p("W"), L0.p("b")
-                on_wgrad_stream(lambda r=r, z=z, coef=coef, L=L, da=da: M.narrow_wgrad_bn(
-                    u8, w0, b0, r["in_scale"], r["in_shift"], r["in_relu"], z, coef, L.relu, da, L.gp("W"), half=half), u8, z, coef, da)
-                coef0, ug = M.narrow_dgrad_bn_reduce(z, coef, L.relu, L.wT(), da, u8, w0, b0,
-                                                     (r0["scale"], r0["shift"], r0["mean"], r0["var"], L0.relu), tail=tail_of(r0), half=half,
-                                                     mask=r.get("mask0") if M.NARROW_MASK else None)
-                M.narrow_wgrad_first(mom, ug, coef0, w0, b0, L0.gp("W"))
-                return None  # a leaf: nothing upstream takes a gradient
-            if r.get("cin_padded") and not pooled and M.dgrad_bn_supported(rows, c, L.cin_pad):
-                # the same layer on [x | 0] and [W ; 0]: dW through a padded scratch (its rows >= cin multiply zeros), da = dz [W ; 0]^T
-                def _padded_in_wgrad(r=r, z=z, coef=coef, L=L, da=da):
-                    G = M._zeros_f32((L.cin_pad, L.cout), z.device)
-                    M.wgrad_dense_bn(r["x"], z, coef, L.relu, G, da=da)
-                    gw = L.gp("W")
-                    M.row_segments(L.cin, [(gw, gw, G[:L.cin])])  # dW += the scratch's first cin rows (in place, one launch)
-                on_wgrad_stream(_padded_in_wgrad, r["x"], z, coef, da)
-                if not want_da:
-                    return None
-                da = M.dgrad_bn(z, coef, L.relu, L.store.padded_rows(L.name + "/W", L.cin_pad, transpose=True), da=da)[:, :L.cin]
-                continue
-            if r["kind"] == "dense" and (not want_da or M.dgrad_bn_supported(rows, c, r["x"].shape[1])):
-                # dz never materialised: both GEMMs rebuild it from (da | gout, z, coef) in their loaders
-                src = dict(gout=da, argmax=argmax, k=k) if pooled else dict(da=da)
-                on_wgrad_stream(lambda r=r, z=z, coef=coef, L=L, src=src: M.wgrad_dense_bn(
-                    r["x"], z, coef, L.relu, L.gp("W"), in_scale=r["in_scale"], in_shift=r["in_shift"], in_relu=r["in_relu"], **src),
-                    r["x"], z, coef, da, argmax if pooled else None)
-                if not want_da:
-                    return None
-                below = recs[i - 1] if i > 0 else None
-                if FUSE_BN_REDUCE and not pooled and below is not None and below["layer"].bn and below["z"] is r["x"]:
-                    # the layer below's BatchNorm-backward sums come out of this GEMM's store epilogue
-                    da, coef_ahead = M.dgrad_bn(z, coef, L.relu, L.wT(), da=da, below=(
-                        below["z"], below["scale"], below["shift"], below["mean"], below["var"], below["layer"].relu),
-                        below_tail=tail_of(below))
-                else:
-                    da = M.dgrad_bn(z, coef, L.relu, L.wT(), **src)
-                continue
-            if i == 0 and r["kind"] == "assembled":
-                return dict(da=da, coef=coef, relu=L.relu)  # dz is formed inside votenet_group_linear_backward_assembled
-            if i == 0 and r["kind"] == "gather" and PRE_LINEAR and not pooled and r["feat"] is not None and \
-                    M.group_linear_backward_supported(c, r["idx"].shape[2]):
-                return dict(da=da, coef=coef, relu=L.relu)  # dz is formed inside votenet_group_linear_backward
-            dz = M.bn_backward_apply(z, coef, L.relu, da, argmax=argmax if pooled else None, k=k if pooled else 0)
-        else:
-            dz = da
-            # (a weight gradient like the others: on their stream -- the two launches of a column sum were 31 us of the main chain per step)
-            on_wgrad_stream(lambda dz=dz, L=L: M.bias_grad(dz, L.gp("b")), dz)
-            if r.get("padded"):
-                # the same layer on the padded copies: dz -> [dz | 0] (rows, cout_pad); dW through a padded scratch, da = dz_p [W | 0]^T
-                # (g_padded: the caller already holds the last layer's gradient as [g | 0], g = g_padded[:, :cout])
-                if g_padded is not None and i == len(recs) - 1 and g_padded.shape[1] == L.cout_pad:
-                    dzp = g_padded
-                else:
-                    dzp = torch.empty((dz.shape[0], L.cout_pad), dtype=torch.float32, device=dz.device)
-                    M.row_segments(dz.shape[0], [(dzp[:, :L.cout], dz, None), (dzp[:, L.cout:], None, None)])
-
-                def _padded_wgrad(r=r, dzp=dzp, L=L):
-                    G = M._zeros_f32((L.cin, L.cout_pad), dzp.device)
-                    M.wgrad_dense(r["x"], dzp, G, r["in_scale"], r["in_shift"], r["in_relu"])
-                    gw = L.gp("W")
-                    M.row_segments(L.cin, [(gw, gw, G[:, :L.cout])])  # dW += the scratch's first cout columns (in place, one launch)
-                on_wgrad_stream(_padded_wgrad, dzp, r.get("x"))
-                if want_da:
-                    da, _ = M.linear_dense(dzp, L.store.padded(L.name + "/W", L.cout_pad, transpose=True), want_stats=False)
-                else:
-                    da = None
-                continue
-        if i == 0 and r["kind"] == "gather":
-            return dict(dz=dz)  # the caller (SAModule.backward) finishes the first layer: it owns idx / pts_cnt / the tables
-        on_wgrad_stream(lambda r=r, dz=dz, L=L: M.wgrad_dense(r["x"], dz, L.gp("W"), r["in_scale"], r["in_shift"], r["in_relu"]),
-                        dz, r.get("x"))
-        if want_da:
-            da, _ = M.linear_dense(dz, L.wT(), want_stats=False)  # da_prev = dz W^T
-        else:
-            da = None
+                arm = _bwd_above_assembled
+            elif r.get("narrow"):
+                arm = _bwd_above_narrow
+            elif r.get("cin_padded") and not pooled and M.dgrad_bn_supported(r["rows"], L.cout, L.cin_pad):
+                arm = _bwd_padded_input
+            elif r["kind"] == "dense" and (not want_da or M.dgrad_bn_supported(r["rows"], L.cout, r["x"].shape[1])):
+                arm = _bwd_fused_dense
+            elif i == 0 and r["kind"] == "assembled":
+                arm = _bwd_first_fused
+            elif i == 0 and r["kind"] == "gather" and PRE_LINEAR and not pooled and r["feat"] is not None and \
+                    M.group_linear_backward_supported(L.cout, r["idx"].shape[2]):
+                arm = _bwd_first_fused
+            else:
+                arm = _bwd_unfused
+            step = arm(r, below, da, coef, (argmax, k) if pooled else None, want_da)
+        da, coef_from_above, done = step
+        if done:
+            break
     return da
 
 
@@ -1181,13 +1264,13 @@ class SAModule:
         return d_feat, d_xyz
 
     def _first_layer_backward(self, rec, h, need_feat, need_xyz_grad, d_rows_xyz_extra=None):
-        """Backward of z = P[idx] + dxyz W[0:3] (P = feat W[3:]) given dz (rows, cout):
+        """Backward of z = P[idx] + dxyz W[0:3] (P = feat W[3:]) from the chain's FirstLayerGrad h:
              dW[0:3] += dxyz^T dz                     (over the grouped rows)
              S = scatter-add of dz rows by idx        (b, n, cout)  -- GroupPointGrad on the layer OUTPUT width
              dW[3:]  += feat^T S ,  d_feat = S W[3:]^T                (two GEMMs over the b*n points, not the grouped rows)
              d_xyz / d_new_xyz from dz W[0:3]^T       (proposal layer only)
-        h = dict(dz=) or dict(da=, coef=, relu=): in the second form one kernel forms dz from (z, da), scatters it and
-        reduces the xyz rows of dW in a single pass (votenet_group_linear_backward)."""
+        Four ways to S and dz -- dz written out, assembled on the piece layout, assembled on the full layout, gather fused: one
+        kernel forms dz from (z, da), scatters it and reduces the xyz rows of dW in a single pass --, then the common tail."""
         r0 = rec["recs"][0]
         L0 = r0["layer"]
         W, gW = L0.p("W"), L0.gp("W")
@@ -1195,34 +1278,15 @@ class SAModule:
         b, n = xyz.shape[:2]
         cout = W.shape[1]
         d_feat = d_xyz = None
-        S = None
-        if "dz" in h:
-            dz = h["dz"]
-            if feat is None or PRE_LINEAR:
-                on_wgrad_stream(lambda: M.wgrad_gather(xyz, new_xyz, None, idx, dz, gW), dz)  # rows 0..2 of dW (no feature block)
-            if feat is not None and PRE_LINEAR:
-                S, _, _ = M.group_concat_grad(dz, None, idx, pts_cnt, n, cout)
+        if h.dz is not None:
+            S, dz = _first_written_out(rec, h.dz, gW), h.dz
         elif r0["kind"] == "assembled" and r0.get("half") is not None:
-            half = r0["half"]
-            if h.get("decomposed"):
-                S, coef0 = M.group_linear_backward_decomposed(half, b, n, r0["P"], r0["wx"], h["da"], h["bn"], h["relu"], h["tail"],
-                                                              r0["cntv"], r0["mom"], gW[:3], defer=on_wgrad_stream)
-                h = dict(h, coef=coef0)
-                dz = None
-            else:
-                S, dz = M.group_linear_backward_half(half, b, n, r0["P"], r0["wx"], h["da"], h["coef"], h["relu"], gW[:3]), None
-            if need_xyz_grad:
-                # dz0 W[0:3]^T is linear in dz0: the points receive S W[0:3]^T, a centre minus the sum of its rows' dz0 times W[0:3]^T
-                d_xyz = M.rows_dot3(S.view(b * n, cout), W[:3]).view(b, n, 3)
-                d_new = M.rows_dot3(M.half_centre_sums(half, r0["P"], r0["wx"], h["da"], h["coef"], h["relu"]), W[:3]).view(b, -1, 3)
-                d_xyz = tf_sampling.gather_point_grad_raw(n, rec["fps_idx"], d_new, into=d_xyz)
-                need_xyz_grad = False  # done
+            S, dz, d_xyz = _first_piece_layout(rec, h, W, gW, need_xyz_grad)  # d_xyz: finished there
         elif r0["kind"] == "assembled":
-            S, dz = M.group_linear_backward_assembled(xyz, new_xyz, idx, pts_cnt, r0["P"], r0["wx"], h["da"], h["coef"], h["relu"],
-                                                      gW[:3], want_dz=need_xyz_grad)
+            S, dz = M.group_linear_backward_assembled(xyz, new_xyz, idx, pts_cnt, r0["P"], r0["wx"], h.da, h.coef, h.relu, gW[:3],
+                                                      want_dz=need_xyz_grad)
         else:
-            S, dz = M.group_linear_backward(xyz, new_xyz, idx, pts_cnt, r0["z"], h["da"], h["coef"], h["relu"], gW[:3],
-                                            want_dz=need_xyz_grad)
+            S, dz = M.group_linear_backward(xyz, new_xyz, idx, pts_cnt, r0["z"], h.da, h.coef, h.relu, gW[:3], want_dz=need_xyz_grad)
         if feat is not None:
             c = feat.shape[2]
             if PRE_LINEAR:
@@ -1236,13 +1300,44 @@ class SAModule:
                 if need_feat:
                     d_rows_feat, _ = M.linear_dense(dz, L0.wT(3, None), want_stats=False)
                     d_feat, _, _ = M.group_concat_grad(d_rows_feat, None, idx, pts_cnt, n, c)
-        if need_xyz_grad:
+        if need_xyz_grad and d_xyz is None:
             d_rows_xyz = M.rows_dot3(dz, W[:3])  # dz W[0:3]^T, three columns: a streaming kernel, not a 128-wide GEMM tile
             if d_rows_xyz_extra is not None:  # weighted_avg: the gradient through the pooling weights, also per grouped row
                 d_rows_xyz = add_rows(d_rows_xyz, d_rows_xyz_extra)
             _, d_xyz, d_new = M.group_concat_grad(None, d_rows_xyz, idx, pts_cnt, n, 0)
             d_xyz = tf_sampling.gather_point_grad_raw(n, rec["fps_idx"], d_new, into=d_xyz)  # new_xyz = gather(xyz, fps_idx): accumulated in place
         return d_feat, d_xyz
+
+
+def _first_written_out(rec, dz, gW):
+    """_first_layer_backward on a dz (rows, cout) in memory: the xyz rows of dW on the lane -> S (b, n, cout), or None: no feature block."""
+    r0 = rec["recs"][0]
+    xyz, new_xyz, feat, idx = r0["xyz"], r0["new_xyz"], r0["feat"], r0["idx"]
+    if feat is None or PRE_LINEAR:
+        on_wgrad_stream(lambda: M.wgrad_gather(xyz, new_xyz, None, idx, dz, gW), dz)  # rows 0..2 of dW (no feature block)
+    if feat is not None and PRE_LINEAR:
+        return M.group_concat_grad(dz, None, idx, rec["pts_cnt"], xyz.shape[1], gW.shape[1])[0]
+    return None
+
+
+def _first_piece_layout(rec, h, W, gW, need_xyz_grad):
+    """_first_layer_backward of a layer assembled on the piece layout (csrc/half.hip): decomposed over the points -- the pass produces the
+    layer's coefficients itself -- or from the coefficients the layer above produced.  -> (S (b, n, cout), None: dz is never written,
+    d_xyz (b, n, 3) or None: it comes from S and the centre sums)."""
+    r0 = rec["recs"][0]
+    half = r0["half"]
+    b, n = r0["xyz"].shape[:2]
+    if h.coef is None:
+        S, coef = M.group_linear_backward_decomposed(half, b, n, r0["P"], r0["wx"], h.da, h.bn, h.relu, h.tail, r0["cntv"], r0["mom"],
+                                                     gW[:3], defer=on_wgrad_stream)
+    else:
+        S, coef = M.group_linear_backward_half(half, b, n, r0["P"], r0["wx"], h.da, h.coef, h.relu, gW[:3]), h.coef
+    if not need_xyz_grad:
+        return S, None, None
+    # dz0 W[0:3]^T is linear in dz0: the points receive S W[0:3]^T, a centre minus the sum of its rows' dz0 times W[0:3]^T
+    d_xyz = M.rows_dot3(S.view(b * n, W.shape[1]), W[:3]).view(b, n, 3)
+    d_new = M.rows_dot3(M.half_centre_sums(half, r0["P"], r0["wx"], h.da, coef, h.relu), W[:3]).view(b, -1, 3)
+    return S, None, tf_sampling.gather_point_grad_raw(n, rec["fps_idx"], d_new, into=d_xyz)
 
 
 class SAModuleMSG:
