@@ -28,6 +28,7 @@ SIDE_LIBS = {
     "propsup": "votenet_proposal_supervision.h",  # the paper's objectness and centre supervision, one launch behind the loss
     "votesamp": "votenet_vote_sampling.h",   # the proposal module's clusters sampled on the votes, one launch
     "instbox": "votenet_instance_boxes.h",   # ground-truth boxes from instance-labelled points
+    "instvote": "votenet_instance_votes.h",  # vote supervision from instance labels, one launch behind the loss
 }
 _side = {}  # name -> (the loaded library, its *_last_error function)
 

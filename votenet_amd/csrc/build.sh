@@ -74,6 +74,9 @@ SIDE_LIBS=(
   # ground-truth boxes from instance-labelled points.  No contraction, as everywhere: tests/instance_boxes_ref.py restates the rule and
   # every output is compared by bit pattern (the combinations are integer atomics; the only float arithmetic is the rows' in double)
   "instbox  instance_boxes.hip instbox"
+  # vote supervision from instance labels, one launch behind the loss.  No contraction: tests/instance_votes_ref.py restates the rule
+  # operation for operation; -fno-slp-vectorize as votesup, whose loss and cotangent these are: the three axes' differences would pack
+  "instvote instance_votes.hip instvote -fno-slp-vectorize"
 )
 side_lib() { # directory, source, library name, extra flags ...
   local dir="$HERE/$1" src="$HERE/$1/$2" lib="libvotenet_$3.so" obj="$HERE/$1/obj/$(basename "${2%.hip}").o" tmp

@@ -309,14 +309,17 @@ def _ragged_labels(t, total, dev, name):
 
 
 def build_batch_from_labels(raw, raw_offset, instance, semantic, class_map, choice, aug=None, n_out=POINT_NUM, k=256, min_points=1,
-                            height=False, extra_cols=0):
+                            height=False, extra_cols=0, point_box=False):
     """Scenes without annotated boxes -> model inputs: raw, raw_offset, aug, n_out, height, extra_cols as for build_batch; instance,
     semantic (sum n_s) int32, host or device: an instance id (negative: none) and a semantic label per row of raw; class_map (n_sem)
     int32: label -> class of the network, or -1; choice (b, n_out), host or device (draw_choice makes one): the rows
     subsample_augment picks, by which the labels are gathered on the device.  The boxes are the extents of the instances in the
     AUGMENTED points (instance_boxes.boxes_from_labels: ids in [0, k), at least min_points points), so they are axis-aligned in the
     frame the network sees, and augment_boxes encodes them without a draw.
-    -> (points, gt, scene_index) with build_batch's contract; a scene that keeps no box is dropped."""
+    -> (points, gt, scene_index) with build_batch's contract; a scene that keeps no box is dropped.
+    point_box: the dict also holds "point_box" (k, n_out) int32, the row of every point's box within its scene's ground truth, -1 where
+    the point has none (one more launch, instance_boxes.boxes_from_labels(want_point_box=True)): what
+    VoteNetHotPath.enable_instance_votes() supervises the votes by.  False: the launches and the keys of a call without it."""
     from . import instance_boxes as IB  # (the only place of this module that loads libvotenet_instbox.so)
     if choice is None:
         raise L.InvalidArgumentError("build_batch_from_labels: choice is required (draw_choice makes one): the labels follow its rows")
@@ -337,7 +340,9 @@ def build_batch_from_labels(raw, raw_offset, instance, semantic, class_map, choi
     start = torch.from_numpy(off[:-1].copy()).to(dev)[:, None]
     last = torch.from_numpy(np.diff(off) - 1).to(dev)[:, None]
     rows = start + torch.minimum(ch.to(torch.int64).clamp(min=0), last)
-    boxes = IB.boxes_from_labels(points, instance[rows], semantic[rows], class_map, k=k, min_points=min_points)
+    boxes = IB.boxes_from_labels(points, instance[rows], semantic[rows], class_map, k=k, min_points=min_points,
+                                 **(dict(want_point_box=True) if point_box else {}))
+    rows_of = boxes["point_box"] if point_box else None  # (of the un-dropped batch: a dropped scene's rows are all -1)
     cnt = np.diff(boxes["box_offset"])
     scene_index = np.nonzero(cnt > 0)[0].astype(np.int64)
     if len(scene_index) == 0:
@@ -346,8 +351,11 @@ def build_batch_from_labels(raw, raw_offset, instance, semantic, class_map, choi
         keep = torch.from_numpy(scene_index).to(dev)
         points = points[keep]
         feats = feats[keep] if feats is not None else None
+        rows_of = rows_of[keep] if rows_of is not None else None
     box_offset = np.concatenate([[0], np.cumsum(cnt[scene_index])]).astype(np.int64)  # (the rows are compact: a dropped scene has none)
     gt = augment_boxes(boxes["center"], boxes["size"], boxes["heading"], boxes["cls"], box_offset, None)
     if feats is not None:
         gt["features"] = feats
+    if rows_of is not None:  # (augment_boxes keeps the row order and pads at the end: the rows index the padded ground truth)
+        gt["point_box"] = rows_of
     return points, gt, scene_index

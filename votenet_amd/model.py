@@ -928,6 +928,7 @@ class VoteNetHotPath:
         self.store.refresh_split()
         lv, g = self.backbone_levels(x, tape, next_x=next_x, feats=feats, next_feats=next_feats)
         self._stamp_tape(tape)
+        self._keep_seed_levels(tape)
         self._grams_ahead(tape)
         if not all(k in g for k in ("fp1", "fp2", "prop_fps")):  # geometry computed without the taps (overlap off): the launch path
             g = dict(g)
@@ -1057,11 +1058,66 @@ class VoteNetHotPath:
         from . import vote_supervision as VS
         if mode not in VS.MODES:
             raise M.L.InvalidArgumentError("enable_vote_supervision: mode must be one of %s, got %r" % (", ".join(VS.MODES), mode))
+        if mode == "paper" and self.instance_votes == "instance":
+            raise M.L.InvalidArgumentError("enable_vote_supervision: \"paper\" and enable_instance_votes() both write the vote term: "
+                                           "disable_instance_votes() first")
         self.vote_supervision = mode
 
     def disable_vote_supervision(self):
         """Back to the launches of a step with the reference's vote supervision (the default)."""
         self.vote_supervision = None
+
+    # ---- vote supervision from instance labels (instance_votes.py): off unless asked for -----------------------------------------
+    instance_votes = None  # the mode while enable_instance_votes is in force (instance_votes.MODES); a setting of the run, not checkpoint state
+
+    def enable_instance_votes(self, mode="instance"):
+        """From now on every train_step(..., gt=...) supervises the votes by `mode`.  "instance": one more launch behind the loss launch
+        (instance_votes.instance_vote_loss, in the place the paper-vote launch has) overwrites the whole vote cotangent, last_losses[1]
+        (vote_reg_loss) and re-forms last_losses[0]: a seed votes for the centre of the box of ITS OWN instance, a seed on an unlabelled
+        point is not supervised, the mean is over the supervised seeds.  gt["point_box"] (B, n points) int32 on the device is required
+        then (input_pipeline.build_batch_from_labels(..., point_box=True)); the link from a seed to its cloud point is the fps_idx of
+        sa1 and sa2, which the step keeps from its tape.  "reference": the rule of votenet_loss itself, no launch.  Everything else of
+        the step -- the other ten loss values, the other two cotangents, the graphs (none is captured again), the guard, the
+        data-parallel exchange, the optimizer -- is what it was.  "instance" and enable_vote_supervision("paper") exclude each other
+        (both write the vote term).  A step with fixed cotangents (cot=) has no loss and is not touched."""
+        from . import instance_votes as IV
+        if mode not in IV.MODES:
+            raise M.L.InvalidArgumentError("enable_instance_votes: mode must be one of %s, got %r" % (", ".join(IV.MODES), mode))
+        if mode == "instance" and self.vote_supervision == "paper":
+            raise M.L.InvalidArgumentError("enable_instance_votes: enable_vote_supervision(\"paper\") is in force and both write the vote "
+                                           "term: disable_vote_supervision() first")
+        self.instance_votes = mode
+
+    def disable_instance_votes(self):
+        """Back to the launches of a step with the reference's vote supervision (the default)."""
+        self.instance_votes = None
+        self.__dict__.pop("_seed_levels", None)
+
+    def _check_point_box(self, x, gt):
+        """train_step with the instance mode on: gt must carry the cloud's box rows (before anything is zeroed or enqueued)."""
+        pb = gt.get("point_box") if hasattr(gt, "get") else None
+        want = tuple(x.shape[:2])
+        if not (torch.is_tensor(pb) and pb.dtype == torch.int32 and pb.device == x.device and tuple(pb.shape) == want and pb.is_contiguous()):
+            raise M.L.InvalidArgumentError(
+                "train_step: enable_instance_votes() is in force: gt[\"point_box\"] must be a contiguous int32 tensor of shape %s on %s "
+                "(input_pipeline.build_batch_from_labels(..., point_box=True)), got %s"
+                % (want, x.device, (tuple(pb.shape), pb.dtype, pb.device) if torch.is_tensor(pb) else type(pb).__name__))
+
+    def _keep_seed_levels(self, tape):
+        """The link from a seed to the cloud point it is: the fps_idx of the tape's first two sa records (sa1's picks into the cloud,
+        sa2's picks into sa1's centres), kept on the net for the launch behind the loss (_after_loss's signature stays what it was).
+        With prefetched geometry both tensors live in a GeometryGraph's buffers, which that graph's next replay overwrites.  They are
+        still THIS step's when the launch runs: the launch is enqueued on the main stream inside this step; the graph is next replayed
+        for the batch GEOMETRY_RING = 3 prefetches on (GeometryPrefetch.next_graph never hands out the graph that serves the pass being
+        enqueued), that prefetch is issued from a later step, and its stream first waits for an event recorded on the main stream
+        then -- behind every launch of this step.  The graph and its generation are kept beside them and compared at the launch."""
+        if self.instance_votes != "instance":
+            return
+        sa = [t for t in tape[:2] if t.get("op") == "sa" and t.get("fps_idx") is not None]
+        if len(sa) != 2:
+            raise M.L.VotenetError("enable_instance_votes: the tape does not start with sa1's and sa2's records")
+        gg = self._geometry.current
+        self._seed_levels = (sa[0]["fps_idx"], sa[1]["fps_idx"], gg, gg.generation if gg is not None else 0)
 
     # ---- objectness and centre supervision as in the VoteNet paper (proposal_supervision.py): off unless asked for ----------------
     proposal_supervision = None  # the mode while enable_proposal_supervision is in force (proposal_supervision.MODES); a setting of the run, not checkpoint state
@@ -1087,12 +1143,20 @@ class VoteNetHotPath:
     # ---- the launches behind the loss: the launch path, the eager first step of a shape and every replay come here --------------------
     def _after_loss(self, out, gt, losses, cot):
         """Behind votenet_loss(out, gt) -> losses, cot and before the backward pass reads cot, in this order, each only while its mode is on
-        (a mode that is off imports and loads nothing): the paper's vote term, the paper's objectness and centre terms (both overwrite
-        their parts of cot and losses in place), the monitors' accuracy launch (last: its ring records the re-formed total)."""
+        (a mode that is off imports and loads nothing): the paper's vote term or the instance labels' (they exclude each other), the
+        paper's objectness and centre terms (all overwrite their parts of cot and losses in place), the monitors' accuracy launch (last:
+        its ring records the re-formed total)."""
         if self.vote_supervision == "paper":
             from . import vote_supervision as VS  # (the only place of a train step that loads libvotenet_votesup.so)
             work, supervised = self._loss_tail_buffers(VS, out["votes_xyz"].shape[0], 1)
             VS.paper_vote_loss(out, gt, losses, d_votes=cot["votes_xyz"], supervised=supervised, work=work)
+        if self.instance_votes == "instance":
+            from . import instance_votes as IV  # (the only place of a train step that loads libvotenet_instvote.so)
+            idx1, idx2, gg, generation = self._seed_levels  # (this step's: _keep_seed_levels)
+            if gg is not None and gg.generation != generation:
+                raise M.L.VotenetError("instance votes: the geometry buffers that hold this step's fps_idx have been overwritten by a later prefetch")
+            work, counts = self._loss_tail_buffers(IV, out["votes_xyz"].shape[0], 2)
+            IV.instance_vote_loss(out, gt, losses, (idx1, idx2), d_votes=cot["votes_xyz"], counts=counts, work=work)
         if self.proposal_supervision == "paper":
             from . import proposal_supervision as PS  # (the only place of a train step that loads libvotenet_propsup.so)
             work, counts = self._loss_tail_buffers(PS, out["proposals_xyz"].shape[0], 3)
@@ -1206,6 +1270,8 @@ class VoteNetHotPath:
         pass, its components are left in self.last_losses (device, loss.NAMES).  cot: fixed cotangents instead (tests).
         feats / next_feats: sa1's input features of x / next_x, for a network built with point_features (forward())."""
         self._sa1_points(x, feats, "train_step")  # (before anything is zeroed or enqueued)
+        if self.instance_votes == "instance" and gt is not None:
+            self._check_point_box(x, gt)
         if not hasattr(self, "_seg"):
             self.init_optimizer()
         self.store.grad.zero_()
@@ -1225,6 +1291,7 @@ class VoteNetHotPath:
                 self.update_moving_averages(tape)
                 if gt is not None:
                     from . import loss as VL
+                    self._keep_seed_levels(tape)
                     self.last_losses, cot = VL.votenet_loss(out, gt)
                     self._after_loss(out, gt, self.last_losses, cot)
                 self._gsync.begin()

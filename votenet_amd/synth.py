@@ -56,6 +56,36 @@ def room_scene(n, seed, size=(5.0, 3.0, 5.0), nbox=(6, 10)):
     return pts.astype(np.float32), np.array(boxes, np.float32)
 
 
+def room_scene_labels(n, seed, size=(5.0, 3.0, 5.0), nbox=(6, 10)):
+    """The labels of room_scene(n, seed, size, nbox)'s points -> (instance (n,) int32: the index of the box a point was drawn on, -1
+    for the floor and the walls; semantic (n,) int32: that box's SUN RGB-D class, -1 likewise).  room_scene's draws are replayed in
+    its order, so the generator is in room_scene's state when the rows are shuffled, and the labels -- shuffled as rows of a 2-D array,
+    as the points are -- take the points' permutation."""
+    rng = np.random.default_rng(seed)
+    n_struct = int(n * 0.6)
+    n_obj = n - n_struct
+    rng.integers(0, 3, n_struct)
+    rng.random(n_struct), rng.random(n_struct)
+    k = int(rng.integers(nbox[0], nbox[1] + 1))
+    per = np.full(k, n_obj // k)
+    per[: n_obj - per.sum()] += 1
+    labels = np.full((n, 2), -1, np.int32)
+    o = n_struct
+    for i in range(k):
+        cls = int(rng.integers(0, 10))
+        rng.uniform(0.8, 1.2, 3)                               # l, w, h
+        rng.uniform(0, 2 * np.pi)                              # ang
+        rng.uniform(0.0, 1.0), rng.uniform(0.0, 1.0)           # cx, cz (one double each, whatever the bounds)
+        rng.uniform(-0.5, 0.5, (per[i], 3))
+        rng.integers(0, 3, per[i])
+        rng.choice([-0.5, 0.5], per[i])
+        labels[o:o + per[i]] = (i, cls)
+        o += per[i]
+    rng.normal(0, 0.005, (n, 3))
+    rng.shuffle(labels)
+    return labels[:, 0].copy(), labels[:, 1].copy()
+
+
 def room_batch(b, n, seed0=1000, **kw):
     return np.stack([room_scene(n, seed0 + i, **kw)[0] for i in range(b)])
 
