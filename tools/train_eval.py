@@ -4,6 +4,7 @@ of the per-batch mAPs (the figure of every earlier log), "set mAP" the reference
 validation set (evaluator.evaluate).
     python tools/train_eval.py [steps] [train_batches] [--save PATH] [--resume PATH] [--monitor K] [--guard] [--height] [--per-class] [--min-points K]
                                                       [--nms-overlap {rotated,aabb3d,bev}] [--nms-old-type] [--paper-votes] [--paper-proposals] [--vote-fps]
+                                                      [--unit-votes]
 --save PATH: a checkpoint (VoteNetHotPath.save) at every evaluation and at the end.  --resume PATH: continue the run a checkpoint
 holds -- parameters, moving averages, Adam state and step count -- up to `steps` steps in all, on the batches it would have seen.  --monitor K: the reference's training summaries from the device
 (VoteNetHotPath.enable_monitors): every K steps the moving averages of obj_accuracy / sem_accuracy / total_cost over the last 100 steps
@@ -32,7 +33,12 @@ follow it; its size-residual mean over the axes (1/3), its overall x 10 and the 
 --vote-fps: the proposal module's cluster centres are sampled by farthest-point sampling on the VOTES, the paper's rule
 (VoteNetHotPath.enable_proposal_sampling("vote_fps"), vote_sampling.py), in training and in every evaluation of the run; the default
 samples the seeds, as the reference does.  Independent of --paper-votes / --paper-proposals; likewise a setting of the run, not of the
-checkpoint: evaluate a network under the mode it was trained in."""
+checkpoint: evaluate a network under the mode it was trained in.
+--unit-votes: each vote's features are divided by their L2 norm before the proposal module reads them, as the authors' VoteNet does
+(VoteNetHotPath.enable_vote_features("unit"), unit_votes.py), in training and in every evaluation of the run; the default hands the sum
+on as it is, as the reference does.  Independent of the other flags; likewise a setting of the run, not of the checkpoint.
+--paper-votes --paper-proposals --vote-fps --unit-votes is the paper's training rule as far as this project follows it.  The run's
+modes are printed in its first line."""
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import importlib.util
@@ -58,6 +64,7 @@ ap.add_argument("--nms-old-type", action="store_true", help="with aabb3d / bev: 
 ap.add_argument("--paper-votes", action="store_true", help="supervise the votes as the VoteNet paper does (one launch more behind the loss)")
 ap.add_argument("--paper-proposals", action="store_true", help="supervise objectness and centre as the VoteNet paper does (one launch more behind the loss)")
 ap.add_argument("--vote-fps", action="store_true", help="sample the proposal module's centres by FPS on the votes, as the VoteNet paper does (one launch in the stretch)")
+ap.add_argument("--unit-votes", action="store_true", help="divide each vote's features by their L2 norm, as the authors' VoteNet does (in place of two glue launches)")
 args = ap.parse_args()
 if (args.nms_overlap != "rotated" or args.nms_old_type) and not args.per_class:
     ap.error("--nms-overlap / --nms-old-type need --per-class: the reference's protocol suppresses by the rotated-box IoU")
@@ -81,6 +88,10 @@ if args.paper_proposals:
     net.enable_proposal_supervision("paper")
 if args.vote_fps:
     net.enable_proposal_sampling("vote_fps")
+if args.unit_votes:
+    net.enable_vote_features("unit")
+print("run: vote supervision %s, proposal supervision %s, proposal sampling %s, vote features %s"
+      % (net.vote_supervision or "reference", net.proposal_supervision or "reference", net.proposal_sampling or "seed_fps", net.vote_features or "sum"))
 xs = [torch.from_numpy(synth.room_batch(B, n, 5000 + B * i)).to(dev) for i in range(nb)]
 gts = [VL.gt_to_device(synth.room_gt(B, n, 5000 + B * i), dev) for i in range(nb)]
 val_x = [torch.from_numpy(synth.room_batch(B, n, 90000 + B * i)).to(dev) for i in range(4)]

@@ -29,6 +29,7 @@ SIDE_LIBS = {
     "votesamp": "votenet_vote_sampling.h",   # the proposal module's clusters sampled on the votes, one launch
     "instbox": "votenet_instance_boxes.h",   # ground-truth boxes from instance-labelled points
     "instvote": "votenet_instance_votes.h",  # vote supervision from instance labels, one launch behind the loss
+    "unitvote": "votenet_unit_votes.h",      # unit-length vote features as in the authors' VoteNet, in place of the voting glue launches
 }
 _side = {}  # name -> (the loaded library, its *_last_error function)
 

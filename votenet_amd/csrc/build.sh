@@ -77,6 +77,10 @@ SIDE_LIBS=(
   # vote supervision from instance labels, one launch behind the loss.  No contraction: tests/instance_votes_ref.py restates the rule
   # operation for operation; -fno-slp-vectorize as votesup, whose loss and cotangent these are: the three axes' differences would pack
   "instvote instance_votes.hip instvote -fno-slp-vectorize"
+  # the vote features divided by their L2 norm, as the authors' VoteNet does: one launch each way in the place of a glue launch.  No
+  # contraction: tests/unit_votes_ref.py restates the rule operation for operation and every output is compared by bit pattern;
+  # -fno-slp-vectorize as loss.hip: a lane's neighbouring channels' sums, squares and quotients would pack into the forms the gate refuses
+  "unitvote unit_votes.hip unitvote -fno-slp-vectorize"
 )
 side_lib() { # directory, source, library name, extra flags ...
   local dir="$HERE/$1" src="$HERE/$1/$2" lib="libvotenet_$3.so" obj="$HERE/$1/obj/$(basename "${2%.hip}").o" tmp

@@ -558,6 +558,12 @@ class VoteNetHotPath:
         x = xp[:, :259]
         recs = []
         off, _ = P.mlp_chain_forward(self.voting, rows, P.DenseInput(x, xp if pad > 259 else None), recs)
+        if self.vote_features == "unit":
+            from . import unit_votes as UV  # (the only place of a forward pass that loads libvotenet_unitvote.so)
+            v_xyz, v_p, norm = UV.unit_votes(x, off[:, :259])  # the same sum, each vote's features divided by their L2 norm: ONE launch too
+            if tape is not None:  # (the record owns y and norm: the captured stretch's backward reads them at these addresses)
+                tape.append(dict(op="vote", recs=recs, b=b, n=n, unit=dict(y=v_p, norm=norm)))
+            return v_xyz.view(b, n, 3), v_p.view(b, n, 256)
         v_xyz = torch.empty((b, n, 3), dtype=torch.float32, device=x.device)
         v_p = torch.empty((b, n, 256), dtype=torch.float32, device=x.device)
         M.row_segments(rows, [(v_xyz.view(rows, 3), x[:, :3], off[:, :3]), (v_p.view(rows, 256), x[:, 3:], off[:, 3:])])
@@ -837,7 +843,13 @@ class VoteNetHotPath:
                 (d_votes_p[:, 3:259], d_vp.reshape(rows, 256), None)]
         if padw > 259:
             segs.append((d_votes_p[:, 259:], None, None))
-        M.row_segments(rows, segs)
+        if vote.get("unit") is not None:
+            # unit-length vote features: d_vp is the gradient of y = u / |u|; the same buffer receives the gradient of the sum u,
+            # [d_vx + cot | (d_vp - y (y . d_vp)) / |u| | 0], in ONE launch too -- everything below consumes it as it always did
+            from . import unit_votes as UV
+            UV.unit_votes_backward(d_vx, cv, d_vp, vote["unit"]["y"], vote["unit"]["norm"], d_votes_p)
+        else:
+            M.row_segments(rows, segs)
         d_votes = d_votes_p[:, :259]
         d_in = P.mlp_chain_backward(vote["recs"], d_votes, "plain", need_input_grad=True, g_padded=d_votes_p if padw > 259 else None)
         P.wgrad_flush()
@@ -939,7 +951,7 @@ class VoteNetHotPath:
         key = tuple((k, tuple(v.shape), v.dtype) for k, v in ins.items()) + (P.HALF_GROUPS, P.ASSEMBLE_FIRST, P.ASSEMBLE_INLINE, P.POOL_GRAM_BACKWARD, P.ASSEMBLED_DECOMPOSED,
                                                                              self.overlap_wgrad, STRETCH_SEGMENTS, M.SPLIT_K, M.COEF_TAIL, P.WGRAD_BATCH, P.POOL_IN_EPILOGUE,
                                                                              self.store.split, bool(getattr(self, "inline_wgrad_tail", INLINE_WGRAD_TAIL)), M.FORWARD_H2, M.ADHOC_H2,
-                                                                             self.proposal_sampling or "seed_fps", M.CONFIG_EPOCH)  # (the mode before the epoch: dkey below carries it too)
+                                                                             self.proposal_sampling or "seed_fps", self.vote_features or "sum", M.CONFIG_EPOCH)  # (the modes before the epoch: dkey below carries them too)
         graphs = self.__dict__.setdefault("_stretch_graphs", {})
         sg = graphs.get(key)
         self._gsync.begin()
@@ -1203,6 +1215,31 @@ class VoteNetHotPath:
     def disable_proposal_sampling(self):
         """Back to the launches of a pass with the reference's proposal sampling (the default)."""
         self.proposal_sampling = None
+
+    # ---- unit-length vote features as in the authors' VoteNet (unit_votes.py): off unless asked for --------------------------------------
+    vote_features = None  # the mode while enable_vote_features is in force (unit_votes.MODES); a setting of the run, not checkpoint state
+
+    def enable_vote_features(self, mode="unit"):
+        """From now on every pass -- forward, predict, evaluate, train_step (launch path and replayed graphs) and their backward --
+        forms the vote features by `mode`.  "unit": each vote's 256 features (seed features + the voting MLP's residual) divided by
+        their L2 norm, as the authors' VoteNet does before its proposal module; the reference, and the default here, hand the sum on
+        as it is.  vote() runs unit_votes.unit_votes in the place of its last glue launch and the backward of the head runs
+        unit_votes.unit_votes_backward in the place of the glue launch that builds the voting chain's output gradient: two launches
+        for two launches, the tape's "vote" record carries the unit features and the norms between them.  votes_xyz, the voting
+        chain and everything behind its backward are what they were.  No epsilon, as in the authors' code: a vote whose features
+        are all zero becomes NaN.
+        The stretch graphs key on the mode: the first step in a new mode runs launch by launch, each mode keeps its own capture,
+        switching back replays the old one.  The mode is independent of every other one (vote supervision, instance votes, proposal
+        supervision, proposal sampling, point features, monitors, the step guard).  It is a setting of the run, not checkpoint
+        state, and it applies to inference as much as to training: evaluate a network under the mode it was trained in."""
+        from . import unit_votes as UV
+        if mode not in UV.MODES:
+            raise M.L.InvalidArgumentError("enable_vote_features: mode must be one of %s, got %r" % (", ".join(UV.MODES), mode))
+        self.vote_features = mode
+
+    def disable_vote_features(self):
+        """Back to the launches of a pass with the reference's un-normalised vote features (the default)."""
+        self.vote_features = None
 
     # ---- the step guard (step_guard.py): off unless asked for ------------------------------------------------------------------
     step_guard = None        # a step_guard.StepGuard while enable_step_guard is in force
