@@ -4,7 +4,7 @@ of the per-batch mAPs (the figure of every earlier log), "set mAP" the reference
 validation set (evaluator.evaluate).
     python tools/train_eval.py [steps] [train_batches] [--save PATH] [--resume PATH] [--monitor K] [--guard] [--height] [--per-class] [--min-points K]
                                                       [--nms-overlap {rotated,aabb3d,bev}] [--nms-old-type] [--paper-votes] [--paper-proposals] [--vote-fps]
-                                                      [--unit-votes]
+                                                      [--unit-votes] [--heading-bins N] [--classes K]
 --save PATH: a checkpoint (VoteNetHotPath.save) at every evaluation and at the end.  --resume PATH: continue the run a checkpoint
 holds -- parameters, moving averages, Adam state and step count -- up to `steps` steps in all, on the batches it would have seen.  --monitor K: the reference's training summaries from the device
 (VoteNetHotPath.enable_monitors): every K steps the moving averages of obj_accuracy / sem_accuracy / total_cost over the last 100 steps
@@ -38,7 +38,12 @@ checkpoint: evaluate a network under the mode it was trained in.
 (VoteNetHotPath.enable_vote_features("unit"), unit_votes.py), in training and in every evaluation of the run; the default hands the sum
 on as it is, as the reference does.  Independent of the other flags; likewise a setting of the run, not of the checkpoint.
 --paper-votes --paper-proposals --vote-fps --unit-votes is the paper's training rule as far as this project follows it.  The run's
-modes are printed in its first line."""
+modes are printed in its first line.
+--heading-bins N --classes K: train and evaluate a network of another detection head (VoteNetHotPath(head=synth.room_head(N, K)),
+head.py): N heading bins, K classes with one size template each; the rooms' boxes then take their classes from range(K) and, with
+N = 1, stand axis-aligned, and every loss, decode and evaluation of the run reads the net's head.  --heading-bins 1 --classes 18 is the
+shape of the VoteNet paper's second benchmark.  The defaults, 12 and 10, are the reference's head.  The head is part of the
+checkpoint: --resume refuses a file of another one.  Composes with every flag above."""
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import importlib.util
@@ -49,6 +54,7 @@ import numpy as np, torch
 from votenet_amd import evaluator as E, input_pipeline as IP, loss as VL, synth
 from votenet_amd.model import VoteNetHotPath
 
+synth_default = (synth.NH, synth.NC)
 ap = argparse.ArgumentParser()
 ap.add_argument("steps", nargs="?", type=int, default=600)
 ap.add_argument("train_batches", nargs="?", type=int, default=16)
@@ -65,6 +71,8 @@ ap.add_argument("--paper-votes", action="store_true", help="supervise the votes 
 ap.add_argument("--paper-proposals", action="store_true", help="supervise objectness and centre as the VoteNet paper does (one launch more behind the loss)")
 ap.add_argument("--vote-fps", action="store_true", help="sample the proposal module's centres by FPS on the votes, as the VoteNet paper does (one launch in the stretch)")
 ap.add_argument("--unit-votes", action="store_true", help="divide each vote's features by their L2 norm, as the authors' VoteNet does (in place of two glue launches)")
+ap.add_argument("--heading-bins", metavar="N", type=int, default=synth_default[0], help="heading bins of the detection head (the reference: 12; axis-aligned boxes: 1)")
+ap.add_argument("--classes", metavar="K", type=int, default=synth_default[1], help="classes (= size templates) of the detection head (the reference: 10)")
 args = ap.parse_args()
 if (args.nms_overlap != "rotated" or args.nms_old_type) and not args.per_class:
     ap.error("--nms-overlap / --nms-old-type need --per-class: the reference's protocol suppresses by the rotated-box IoU")
@@ -73,7 +81,8 @@ if args.nms_old_type and args.nms_overlap == "rotated":
 steps, nb = args.steps, args.train_batches
 dev = torch.device("cuda:0")
 B, n = 8, 20480
-net = VoteNetHotPath(dev, seed=0, point_features=1 if args.height else 0)
+head = synth.room_head(args.heading_bins, args.classes)  # (12, 10: the default head itself)
+net = VoteNetHotPath(dev, seed=0, point_features=1 if args.height else 0, head=head)
 net.init_optimizer(1e-3)
 if args.resume:
     net.load(args.resume)
@@ -90,12 +99,13 @@ if args.vote_fps:
     net.enable_proposal_sampling("vote_fps")
 if args.unit_votes:
     net.enable_vote_features("unit")
-print("run: vote supervision %s, proposal supervision %s, proposal sampling %s, vote features %s"
-      % (net.vote_supervision or "reference", net.proposal_supervision or "reference", net.proposal_sampling or "seed_fps", net.vote_features or "sum"))
-xs = [torch.from_numpy(synth.room_batch(B, n, 5000 + B * i)).to(dev) for i in range(nb)]
-gts = [VL.gt_to_device(synth.room_gt(B, n, 5000 + B * i), dev) for i in range(nb)]
-val_x = [torch.from_numpy(synth.room_batch(B, n, 90000 + B * i)).to(dev) for i in range(4)]
-val_gt = [E.gt_for_eval(synth.room_gt(B, n, 90000 + B * i)) for i in range(4)]
+print("run: vote supervision %s, proposal supervision %s, proposal sampling %s, vote features %s, head %d heading bins / %d classes (%d columns)"
+      % (net.vote_supervision or "reference", net.proposal_supervision or "reference", net.proposal_sampling or "seed_fps", net.vote_features or "sum",
+         head.nh, head.nc, head.width))
+xs = [torch.from_numpy(synth.room_batch(B, n, 5000 + B * i, head=head)).to(dev) for i in range(nb)]
+gts = [VL.gt_to_device(synth.room_gt(B, n, 5000 + B * i, head=head), dev) for i in range(nb)]
+val_x = [torch.from_numpy(synth.room_batch(B, n, 90000 + B * i, head=head)).to(dev) for i in range(4)]
+val_gt = [E.gt_for_eval(synth.room_gt(B, n, 90000 + B * i, head=head), head=head) for i in range(4)]
 
 
 def heights(x):
@@ -117,7 +127,7 @@ def evaluate():
         aps = []
         for x, f, g in zip(val_x, val_f, val_gt):
             pred = net.predict(x, 0.25, feats=f)
-            aps.append(E.eval_det(pred, g, thr)[1])
+            aps.append(E.eval_det(pred, g, thr, head=head)[1])
         res[thr] = float(np.nanmean(aps))
     return res
 

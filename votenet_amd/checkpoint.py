@@ -15,8 +15,9 @@ model built with point_features = c has 3 + c there, under the same name, and a 
 for the modules VoteNetHotPath builds -- [xyz | features] at an SA layer's first conv, [interpolated | points1] at FP, [seeds_xyz |
 seeds_points] at voting -- so a kernel is the store's (cin, cout) matrix reshaped, never permuted.
 
-A file is an .npz of numeric arrays plus one JSON header stored as a uint8 array under HEADER_KEY (format version, npoints, NH / NS / NC,
-BatchNorm momentum and epsilon, whether optimizer state is present).  It is read with allow_pickle=False: nothing is unpickled.
+A file is an .npz of numeric arrays plus one JSON header stored as a uint8 array under HEADER_KEY (format version, npoints, NH / NS / NC
+of the net's head and, for another head than the default, its size templates mean_sizes; BatchNorm momentum and epsilon, whether
+optimizer state is present).  It is read with allow_pickle=False: nothing is unpickled.
 
 A restore copies IN PLACE into the existing store.flat, _ema_flat, _m and _v: a captured StretchGraph has their addresses baked in (its
 replay runs votenet_ema_update on them).  Every name, shape, dtype and header field is checked before the first byte is written; then
@@ -70,9 +71,37 @@ def _entries(net, optimizer=True):
 
 def _header(net, optimizer):
     from . import mlp as M
-    from . import model as VM
-    return dict(format="votenet_amd checkpoint", version=FORMAT_VERSION, npoints=[m.npoint for m in (net.sa1, net.sa2, net.sa3, net.sa4)],
-                NH=VM.NH, NS=VM.NS, NC=VM.NC, bn_momentum=net.BN_MOMENTUM, bn_epsilon=M.BN_EPS, optimizer=bool(optimizer))
+    head = _head_of(net)
+    hdr = dict(format="votenet_amd checkpoint", version=FORMAT_VERSION, npoints=[m.npoint for m in (net.sa1, net.sa2, net.sa3, net.sa4)],
+               NH=head.nh, NS=head.ns, NC=head.nc, bn_momentum=net.BN_MOMENTUM, bn_epsilon=M.BN_EPS, optimizer=bool(optimizer))
+    if not head.is_default:
+        # the size templates the network was trained to refine: float64, which JSON's shortest round-trip repr carries exactly
+        hdr["mean_sizes"] = head.mean_sizes_f64.tolist()
+    return hdr
+
+
+def _head_of(net):
+    """net.head (a net from before heads existed, or a stand-in without one, has the default head)."""
+    from .head import HeadConfig
+    head = getattr(net, "head", None)
+    return head if head is not None else HeadConfig.sunrgbd()
+
+
+def _header_mean_sizes(hdr, problems):
+    """The file's size templates as an (NC, 3) float64 array -- a file without the field has the default head's --, or None with the
+    reason appended to problems."""
+    from .head import HeadConfig
+    ms = hdr.get("mean_sizes")
+    if ms is None:
+        return HeadConfig.sunrgbd().mean_sizes_f64
+    try:
+        a = np.array(ms, dtype=np.float64)
+    except (TypeError, ValueError):
+        a = None
+    if a is None or a.ndim != 2 or a.shape[1] != 3:
+        problems.append("header mean_sizes: not an (NC, 3) list of numbers")
+        return None
+    return a
 
 
 def _host(buf):
@@ -244,7 +273,8 @@ def _read(path):
 
 def load(net, path, strict=True):
     """Restore a file written by save() (or converted into its layout).  The header must match the model (format version, npoints,
-    NH / NS / NC, BatchNorm momentum and epsilon); it says whether the optimizer state is in the file."""
+    NH / NS / NC, the size templates mean_sizes by value -- a file without them has the default head's --, BatchNorm momentum and
+    epsilon); it says whether the optimizer state is in the file."""
     hdr, arrays, bad = _read(path)
     problems = ["%s: %s" % (k, why) for k, why in sorted(bad.items())]
     if not isinstance(hdr, dict) or not isinstance(hdr.get("version"), int):
@@ -255,7 +285,37 @@ def load(net, path, strict=True):
     for field in ("npoints", "NH", "NS", "NC", "bn_momentum", "bn_epsilon"):
         if hdr.get(field) != mine[field]:
             problems.append("header %s: file %r, model %r" % (field, hdr.get(field), mine[field]))
+    theirs, ours = _header_mean_sizes(hdr, problems), _head_of(net).mean_sizes_f64
+    if theirs is not None and (theirs.shape != ours.shape or theirs.tobytes() != ours.tobytes()):
+        diff = [i for i in range(min(len(theirs), len(ours))) if theirs[i].tobytes() != ours[i].tobytes()]
+        problems.append("header mean_sizes: the file's size templates differ from the model's head%s"
+                        % (" (first at template %d: file %r, model %r)" % (diff[0], theirs[diff[0]].tolist(), ours[diff[0]].tolist()) if diff
+                           else " (%d templates in the file, %d in the model)" % (len(theirs), len(ours))))
     if not isinstance(hdr.get("optimizer"), bool):
         problems.append("header optimizer: %r, expected true / false" % (hdr.get("optimizer"),))
         hdr["optimizer"] = None
     _restore(net, *_validate(net, arrays, strict, hdr["optimizer"], problems, unreadable=bad))
+
+
+def load_new(cls, path, device, strict=True, **kw):
+    """VoteNetHotPath.load(path, device): build a net for the file -- the head from the header's NH and mean_sizes, npoints, and
+    point_features from the rows of sa1's first kernel -- and restore the file into it.  kw: further constructor arguments (seed)."""
+    from .head import HeadConfig
+    hdr, arrays, _ = _read(path)
+    if not isinstance(hdr, dict) or not isinstance(hdr.get("version"), int):
+        raise ValueError("%s: no votenet_amd checkpoint header (%s)" % (path, HEADER_KEY))
+    problems = []
+    ms = _header_mean_sizes(hdr, problems)
+    if problems:
+        raise ValueError("%s: %s" % (path, "; ".join(problems)))
+    head = HeadConfig(hdr.get("NH"), ms)
+    if hdr.get("NC") != head.nc or hdr.get("NS") != head.ns:
+        raise ValueError("%s: header NS / NC %r / %r, but %d size templates" % (path, hdr.get("NS"), hdr.get("NC"), head.nc))
+    if "npoints" in hdr:
+        kw.setdefault("npoints", tuple(hdr["npoints"]))
+    first = arrays.get(SA1_FIRST)
+    if first is not None and first.ndim == 4 and first.shape[2] != 6:
+        kw.setdefault("point_features", int(first.shape[2]) - 3)
+    net = cls(device, head=HeadConfig.sunrgbd() if head.is_default else head, **kw)
+    load(net, path, strict)
+    return net

@@ -69,12 +69,27 @@ def eval_det_cls(det_img, det_score, det_iou, gt_count, ovthresh=0.25, use_07_me
     return rec, prec, voc_ap(rec, prec, use_07_metric)
 
 
-def eval_det(pred, gt, ovthresh=0.25, use_07_metric=False):
+def _num_class(head, num_class, who):
+    """The class count of a public function that takes head= and num_class=: the head's, else the keyword's, else the default head's."""
+    if head is not None:
+        from .head import resolve
+        return resolve(head, 0, 0, 0)[2]
+    if num_class is None:
+        return NC
+    if isinstance(num_class, bool) or not isinstance(num_class, (int, np.integer)) or not 1 <= int(num_class) <= 64:
+        raise L.InvalidArgumentError("%s: num_class must be an integer in [1, 64], got %r" % (who, num_class))
+    return int(num_class)
+
+
+def eval_det(pred, gt, ovthresh=0.25, use_07_metric=False, head=None, num_class=None):
     """evaluator.py:164-200 on batched device tensors.
     pred: dict(bboxes (B,N,8,3) device, nms_idx (K,2) [scene, box] device, class_scores (B,N,NC) device) -- the predict
           tower's outputs; a kept box is ONE detection of its arg-max class with the max class score (evaluator.py:225-233).
     gt:   dict(boxes (B,G,8,3) numpy corners, labels (B,G) int, count (B,) valid boxes per scene).
+    head / num_class: the classes scored are range(head.nc) / range(num_class) (neither: the default head's ten); a ground-truth
+    label outside is counted nowhere.
     -> {class: ap}, mAP over the classes that occur in gt."""
+    nc = _num_class(head, num_class, "eval_det")
     dev = pred["bboxes"].device
     gt_boxes = torch.from_numpy(np.ascontiguousarray(gt["boxes"], dtype=np.float32)).to(dev)
     iou = tf_nms3d.iou3d_cross(pred["bboxes"], gt_boxes).cpu().numpy()  # (B,N,G): every overlap the evaluation can ask for
@@ -82,7 +97,7 @@ def eval_det(pred, gt, ovthresh=0.25, use_07_metric=False):
     cls_scores = pred["class_scores"].detach().cpu().numpy()
     labels, count = np.asarray(gt["labels"]), np.asarray(gt["count"])
     ap = {}
-    for c in range(NC):
+    for c in range(nc):
         gt_count, gt_cols = {}, {}
         for b in range(labels.shape[0]):
             cols = np.nonzero(labels[b, :count[b]] == c)[0]
@@ -103,8 +118,11 @@ def eval_det(pred, gt, ovthresh=0.25, use_07_metric=False):
     return ap, (float(np.mean(list(ap.values()))) if ap else float("nan"))
 
 
-def gt_for_eval(gt_np, counts=None):
-    """synth.room_gt dict -> corners / labels / per-scene count (padding rows repeat the last box: counted once)."""
+def gt_for_eval(gt_np, counts=None, head=None):
+    """synth.room_gt dict -> corners / labels / per-scene count (padding rows repeat the last box: counted once).  head: the
+    HeadConfig the labels were made for; the labels pass through as they are (one outside [0, head.nc) is counted nowhere by
+    eval_det and DetectionAccumulator)."""
+    _num_class(head, None, "gt_for_eval")
     b, g = gt_np["bboxes_roty"].shape
     if counts is None:
         counts = []
@@ -127,11 +145,14 @@ def gt_to_device(gt, device):
     return dict(boxes=conv(gt["boxes"], torch.float32), labels=conv(gt["labels"], torch.int32), count=conv(gt["count"], torch.int32))
 
 
-def finalize_records(records, npos, thresholds, use_07_metric=False):
+def finalize_records(records, npos, thresholds, use_07_metric=False, head=None):
     """The host half of the streaming evaluation: records (K,4) int32 as votenet_eval_match writes them {score bits, class |
     tp_mask << 8, scene, arrival}, npos (NC,) ground-truth boxes per class over the whole set -> {threshold: dict(ap, mAP, rec,
     prec, npos)}.  Per class: sort by (-score, arrival) -- eval_det_cls's stable argsort of detections listed in arrival order --
-    cumulative sums, voc_ap.  Classes without ground truth are left out, as eval_det leaves them out for a batch."""
+    cumulative sums, voc_ap.  Classes without ground truth are left out, as eval_det leaves them out for a batch.  The class count is
+    len(npos); with head it must be head.nc."""
+    if head is not None and len(npos) != _num_class(head, None, "finalize_records"):
+        raise L.InvalidArgumentError("finalize_records: npos holds %d classes, the head has %d" % (len(npos), head.nc))
     records = np.ascontiguousarray(records, dtype=np.int32).reshape(-1, 4)
     score = records[:, 0].copy().view(np.float32).astype(np.float64)
     cls, mask = records[:, 1] & 0xff, (records[:, 1] >> 8) & 0xff
@@ -163,11 +184,14 @@ class DetectionAccumulator:
         res = acc.result()     # the one synchronisation: res[0.25] -> dict(ap, mAP, rec, prec, npos)
     capacity: the most detections (kept boxes) the whole set can offer; result() raises if more arrived.  records: an int32
     (rows >= capacity, 4) device tensor to use as the record buffer instead of allocating one.  Thresholds are compared in
-    float32, as numpy compares a float32 overlap with a Python float.  Equal scores rank in arrival order (add call, then row)."""
+    float32, as numpy compares a float32 overlap with a Python float.  Equal scores rank in arrival order (add call, then row).
+    num_class (or head: its nc): the classes of the network whose predictions arrive, the default head's ten when neither is given;
+    class_scores must have that many columns, and a ground-truth label outside [0, num_class) is counted nowhere."""
     FLAG_OVERFLOW, FLAG_BAD_ROW, FLAG_SCENE = 1, 2, 4
 
-    def __init__(self, device, thresholds=(0.25, 0.5), capacity=1 << 21, records=None):
+    def __init__(self, device, thresholds=(0.25, 0.5), capacity=1 << 21, records=None, num_class=None, head=None):
         self.device = torch.device(device)
+        self.num_class = _num_class(head, num_class, "DetectionAccumulator")
         self.thresholds = tuple(float(t) for t in thresholds)
         if not 1 <= len(self.thresholds) <= 8:
             raise L.InvalidArgumentError("DetectionAccumulator: 1 to 8 IoU thresholds, got %d" % len(self.thresholds))
@@ -181,7 +205,7 @@ class DetectionAccumulator:
             raise L.InvalidArgumentError("DetectionAccumulator: records must be (>= capacity, 4) int32, got %s" % (tuple(records.shape),))
         self._records = records
         self._thr = (ctypes.c_float * len(self.thresholds))(*self.thresholds)
-        self._state = torch.zeros(2 + NC, dtype=torch.int32, device=self.device)  # [records offered, flags, npos[NC]]
+        self._state = torch.zeros(2 + self.num_class, dtype=torch.int32, device=self.device)  # [records offered, flags, npos[num_class]]
         self._scene = self._arrival = 0
 
     def reset(self):
@@ -199,7 +223,7 @@ class DetectionAccumulator:
             raise L.InvalidArgumentError("DetectionAccumulator.add expects (B, N, 8, 3) boxes")
         if "det_rows" in pred:
             return self._add_rows(boxes, pred, gt)
-        cls = L.dev_f32(pred["class_scores"].detach(), "DetectionAccumulator.add: class_scores (B,N,NC)", 3, NC)
+        cls = L.dev_f32(pred["class_scores"].detach(), "DetectionAccumulator.add: class_scores (B,N,NC)", 3, self.num_class)
         if tuple(cls.shape[:2]) != (b, n):
             raise L.InvalidArgumentError("DetectionAccumulator.add: class_scores %s do not match boxes %s" % (tuple(cls.shape), tuple(boxes.shape)))
         rows = L.dev_i32(pred["nms_idx"], "DetectionAccumulator.add: nms_idx (K,2)", 2)
@@ -214,7 +238,7 @@ class DetectionAccumulator:
             raise L.VotenetError("DetectionAccumulator: more than 2^32 kept rows offered")
         st = self._state
         with L.device_guard(self.device):
-            L.check(L.lib().votenet_eval_match(b, n, ng, NC, L.ptr(boxes), L.ptr(rows) if k else None, k, L.ptr(count), L.ptr(cls),
+            L.check(L.lib().votenet_eval_match(b, n, ng, self.num_class, L.ptr(boxes), L.ptr(rows) if k else None, k, L.ptr(count), L.ptr(cls),
                                                L.ptr(g["boxes"]), L.ptr(g["labels"]), L.ptr(g["count"]), len(self.thresholds), self._thr,
                                                self._scene, self._arrival, L.ptr(self._records), self.capacity, st.data_ptr(),
                                                st.data_ptr() + 8, st.data_ptr() + 4, L.stream_ptr()))
@@ -246,7 +270,7 @@ class DetectionAccumulator:
         st = self._state
         with L.device_guard(self.device):
             L.check(L.side_lib("detect").votenet_eval_match_rows(
-                b, n, ng, NC, L.ptr(boxes), L.ptr(rows) if k else None, k, L.ptr(offset), L.ptr(g["boxes"]), L.ptr(g["labels"]),
+                b, n, ng, self.num_class, L.ptr(boxes), L.ptr(rows) if k else None, k, L.ptr(offset), L.ptr(g["boxes"]), L.ptr(g["labels"]),
                 L.ptr(g["count"]), len(self.thresholds), self._thr, self._scene, self._arrival, L.ptr(self._records), self.capacity,
                 st.data_ptr(), st.data_ptr() + 8, st.data_ptr() + 4, L.stream_ptr()), side="detect")
         self._scene += b
@@ -273,8 +297,11 @@ def evaluate(net, batches, gts, thresholds=(0.25, 0.5), iou_threshold=0.25, prot
     box_points.PAPER_MIN_POINTS, with "per_class": boxes that hold fewer points of the cloud are dropped).  nms_overlap, nms_measure:
     predict's ("aabb3d", aabb_nms.PAPER_OVERLAP, with "per_class" and min_points=5 is the paper's protocol: the NMS suppresses by the
     overlap of the boxes' axis-aligned hulls; the matching below stays on the rotated-box IoU, as the paper's does).
+    The classes are net.head's.
     -> {threshold: dict(ap, mAP, rec, prec, npos)}."""
     from . import aabb_nms
+    head = getattr(net, "head", None)
+    nc = _num_class(head, None, "evaluate")
     aabb_nms.check_overlap(protocol, nms_overlap, nms_measure, "evaluate")
     acc = None
     kw = {} if protocol == "reference" else dict(protocol=protocol)  # (the call of the reference's protocol, as it was)
@@ -290,8 +317,9 @@ def evaluate(net, batches, gts, thresholds=(0.25, 0.5), iou_threshold=0.25, prot
         else:
             pred = net.predict(x, iou_threshold, next_x=nx, sync=False, feats=f, next_feats=nf, **kw)
         if acc is None:  # every proposal of every scene kept (per class: offering every class): the most the set can offer
-            per_box = NC if "det_rows" in pred else 1
-            acc = DetectionAccumulator(x.device, thresholds, capacity=sum(int(v.shape[0]) for v, _ in pairs) * int(pred["bboxes"].shape[1]) * per_box)
+            per_box = nc if "det_rows" in pred else 1
+            acc = DetectionAccumulator(x.device, thresholds, capacity=sum(int(v.shape[0]) for v, _ in pairs) * int(pred["bboxes"].shape[1]) * per_box,
+                                       **(dict(num_class=nc) if head is not None and not head.is_default else {}))
         acc.add(pred, g)
     if acc is None:
         raise L.InvalidArgumentError("evaluate: no batches")

@@ -264,14 +264,16 @@ def select_boxes(raw, raw_offset, calib, objects, n_out=POINT_NUM, choice=None, 
     return res
 
 
-def build_batch(raw, raw_offset, calib, objects, aug=None, choice=None, seed=0, scene0=0, n_out=POINT_NUM, height=False, extra_cols=0):
+def build_batch(raw, raw_offset, calib, objects, aug=None, choice=None, seed=0, scene0=0, n_out=POINT_NUM, height=False, extra_cols=0,
+                head=None):
     """Parsed scenes -> model inputs: select_boxes, then subsample_augment and augment_boxes with the same choice / seed for
     the scenes that kept at least one box (the reference skips the others, dataset.py:300).  aug holds one draw per INPUT
     scene: the reference draws before it looks at the objects (dataset.py:219-231), so a dropped scene consumes its draw.
     -> (points (k, n_out, 3) float32, gt dict of augment_boxes, scene_index host int64 (k)); (None, None, empty) when every
     scene is dropped.  height / extra_cols (subsample_augment_features): the dict also holds "features" (k, n_out, c), the input
     features of a network built with point_features = c, and the points come from that entry (the same bits); the boxes are
-    selected on the same un-augmented rows either way."""
+    selected on the same un-augmented rows either way.  head: the HeadConfig whose heading bins and size templates encode the labels
+    (None: the default head's, as augment_boxes' own defaults)."""
     b = len(raw_offset) - 1
     if aug is not None and aug.b != b:
         raise L.InvalidArgumentError("build_batch: %d scenes but %d augmentation draws" % (b, aug.b))
@@ -293,10 +295,18 @@ def build_batch(raw, raw_offset, calib, objects, aug=None, choice=None, seed=0, 
         if aug is not None:
             aug = Augmentation(aug.flip_x[scene_index], aug.flip_z[scene_index], aug.angle[scene_index], aug.scale[scene_index])
     box_offset = np.concatenate([[0], np.cumsum(cnt[scene_index])]).astype(np.int64)
-    gt = augment_boxes(sel["center"], sel["size"], sel["heading"], sel["cls"], box_offset, aug)
+    gt = augment_boxes(sel["center"], sel["size"], sel["heading"], sel["cls"], box_offset, aug, **_head_kw(head))
     if feats is not None:
         gt["features"] = feats
     return points, gt, scene_index
+
+
+def _head_kw(head):
+    """augment_boxes' mean_size / nh of a HeadConfig; nothing for None (the call as it always was)."""
+    if head is None:
+        return {}
+    from .head import resolve
+    return dict(mean_size=head.mean_sizes_f64, nh=resolve(head, 0, 0, 0)[0])
 
 
 def _ragged_labels(t, total, dev, name):
@@ -309,7 +319,7 @@ def _ragged_labels(t, total, dev, name):
 
 
 def build_batch_from_labels(raw, raw_offset, instance, semantic, class_map, choice, aug=None, n_out=POINT_NUM, k=256, min_points=1,
-                            height=False, extra_cols=0, point_box=False):
+                            height=False, extra_cols=0, point_box=False, head=None):
     """Scenes without annotated boxes -> model inputs: raw, raw_offset, aug, n_out, height, extra_cols as for build_batch; instance,
     semantic (sum n_s) int32, host or device: an instance id (negative: none) and a semantic label per row of raw; class_map (n_sem)
     int32: label -> class of the network, or -1; choice (b, n_out), host or device (draw_choice makes one): the rows
@@ -319,7 +329,9 @@ def build_batch_from_labels(raw, raw_offset, instance, semantic, class_map, choi
     -> (points, gt, scene_index) with build_batch's contract; a scene that keeps no box is dropped.
     point_box: the dict also holds "point_box" (k, n_out) int32, the row of every point's box within its scene's ground truth, -1 where
     the point has none (one more launch, instance_boxes.boxes_from_labels(want_point_box=True)): what
-    VoteNetHotPath.enable_instance_votes() supervises the votes by.  False: the launches and the keys of a call without it."""
+    VoteNetHotPath.enable_instance_votes() supervises the votes by.  False: the launches and the keys of a call without it.
+    head: the HeadConfig of the network the batch is for: class_map maps into its nc classes, its templates and heading bins encode
+    the labels (None: the default head)."""
     from . import instance_boxes as IB  # (the only place of this module that loads libvotenet_instbox.so)
     if choice is None:
         raise L.InvalidArgumentError("build_batch_from_labels: choice is required (draw_choice makes one): the labels follow its rows")
@@ -341,7 +353,7 @@ def build_batch_from_labels(raw, raw_offset, instance, semantic, class_map, choi
     last = torch.from_numpy(np.diff(off) - 1).to(dev)[:, None]
     rows = start + torch.minimum(ch.to(torch.int64).clamp(min=0), last)
     boxes = IB.boxes_from_labels(points, instance[rows], semantic[rows], class_map, k=k, min_points=min_points,
-                                 **(dict(want_point_box=True) if point_box else {}))
+                                 **(dict(want_point_box=True) if point_box else {}), **(dict(head=head) if head is not None else {}))
     rows_of = boxes["point_box"] if point_box else None  # (of the un-dropped batch: a dropped scene's rows are all -1)
     cnt = np.diff(boxes["box_offset"])
     scene_index = np.nonzero(cnt > 0)[0].astype(np.int64)
@@ -353,7 +365,7 @@ def build_batch_from_labels(raw, raw_offset, instance, semantic, class_map, choi
         feats = feats[keep] if feats is not None else None
         rows_of = rows_of[keep] if rows_of is not None else None
     box_offset = np.concatenate([[0], np.cumsum(cnt[scene_index])]).astype(np.int64)  # (the rows are compact: a dropped scene has none)
-    gt = augment_boxes(boxes["center"], boxes["size"], boxes["heading"], boxes["cls"], box_offset, None)
+    gt = augment_boxes(boxes["center"], boxes["size"], boxes["heading"], boxes["cls"], box_offset, None, **_head_kw(head))
     if feats is not None:
         gt["features"] = feats
     if rows_of is not None:  # (augment_boxes keeps the row order and pads at the end: the rows index the padded ground truth)

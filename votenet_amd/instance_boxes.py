@@ -50,14 +50,18 @@ def _labels(t, name, shape, dev):
     return t
 
 
-def boxes_from_labels(points, instance, semantic, class_map, k=256, n_class=NC, min_points=1, want_point_box=False):
+def boxes_from_labels(points, instance, semantic, class_map, k=256, n_class=NC, min_points=1, want_point_box=False, head=None):
     """points (b, n, 3) float32 -- the cloud the network sees, i.e. subsample_augment's output --, instance (b, n) and semantic (b, n)
     int32, all contiguous on one device; class_map (n_sem) int32, a device tensor or a host array: semantic label -> class of the
     network, or -1.  Ids outside [0, k), non-finite points and negative ("unlabelled") ids are ignored.
     -> dict: center (nkept, 3), size (nkept, 3), heading (nkept) float64 and cls (nkept) int32 device tensors, scene order then
     ascending id -- what augment_boxes takes; box_offset host int64 (b+1), the one read-back; instance_id, n_points (nkept) int32;
     status (STATUS), inst_count, slot (b, k) int32; ignored (b, 3) int32: unlabelled, id out of the table, non-finite;
-    point_box (b, n) int32 if asked: the row of each point's instance within its scene, -1 where it has none."""
+    point_box (b, n) int32 if asked: the row of each point's instance within its scene, -1 where it has none.
+    head: a HeadConfig whose class count stands in n_class's place."""
+    if head is not None:
+        from .head import resolve
+        n_class = resolve(head, 0, 0, n_class)[2]
     if not torch.is_tensor(points) or not points.is_cuda:
         raise L.InvalidArgumentError("boxes_from_labels: points must be a device tensor")
     if points.dtype != torch.float32:

@@ -3,6 +3,7 @@ and its cotangents with respect to the three tensors through which it reaches th
 import torch
 
 from . import _lib as L
+from .head import resolve as _head_bins
 from .synth import NC, NH, NS
 
 POSITIVE_THRES, NEGATIVE_THRES = 0.3, 0.6  # config.py
@@ -45,10 +46,12 @@ def check_losses(losses, dev, who):
         raise L.InvalidArgumentError("%s: losses must be the 12 floats of votenet_loss on the device" % who)
 
 
-def votenet_loss(out, gt, nh=NH, ns=NS, nc=NC, buffers=None):
-    """out: the dict VoteNetHotPath.forward returns; gt: device tensors (gt_to_device).
+def votenet_loss(out, gt, nh=NH, ns=NS, nc=NC, buffers=None, head=None):
+    """out: the dict VoteNetHotPath.forward returns; gt: device tensors (gt_to_device).  head: the net's HeadConfig (its nh / ns / nc in
+    place of the keywords'; None: the keywords, whose defaults are the default head's).
     -> losses (12,) f32 on the device (NAMES), cotangents dict(votes_xyz, proposals_xyz, proposals_output).
     buffers: (losses, flat) from loss_buffers(out), flat zeroed by the caller -- the results land there instead of in fresh tensors."""
+    nh, ns, nc = _head_bins(head, nh, ns, nc)
     seeds = L.dev_f32(out["seeds_xyz"], "loss seeds_xyz", 3, 3)
     votes = L.dev_f32(out["votes_xyz"], "loss votes_xyz", 3, 3)
     pxyz = L.dev_f32(out["proposals_xyz"], "loss proposals_xyz", 3, 3)
@@ -84,13 +87,14 @@ ACCURACY_COUNTS = ("n_obj_correct", "n_sem_correct", "n_pos", "n_neg")
 RING_COLS = 5  # VOTENET_MONITOR_RING_COLS (include/votenet_monitors.h): obj_accuracy, sem_accuracy, total_cost, n_pos, n_neg
 
 
-def votenet_accuracies(out, gt, nh=NH, ns=NS, nc=NC, losses=None, ring=None, ring_row=0, buffers=None):
+def votenet_accuracies(out, gt, nh=NH, ns=NS, nc=NC, losses=None, ring=None, ring_row=0, buffers=None, head=None):
     """obj_accuracy and sem_accuracy of one step (model.py:164-166, 215-216) on the device, one launch (votenet_accuracies of
     libvotenet_monitors.so, csrc/monitors/monitors.hip).
     out, gt: as votenet_loss takes them.  -> accuracies (2,) f32, counts (4,) int32 (ACCURACY_COUNTS), both on the device; nothing is
     read back.  losses: the vector votenet_loss returned; with ring (window, RING_COLS) f32 the launch also writes row ring_row of it:
     (obj_accuracy, sem_accuracy, losses[0], n_pos, n_neg).  buffers: (accuracies, counts, workspace) of a caller that keeps them
-    (monitors.Monitors; the workspace is 8 int32 zeros, left zero by every launch)."""
+    (monitors.Monitors; the workspace is 8 int32 zeros, left zero by every launch).  head: as votenet_loss takes it."""
+    nh, ns, nc = _head_bins(head, nh, ns, nc)
     pxyz = L.dev_f32(out["proposals_xyz"], "accuracies proposals_xyz", 3, 3)
     pout = L.dev_f32_rows(out["proposals_output"], "accuracies proposals_output")
     b, p = pxyz.shape[:2]
@@ -124,15 +128,25 @@ def votenet_accuracies(out, gt, nh=NH, ns=NS, nc=NC, losses=None, ring=None, rin
     return acc, counts
 
 
-def decode_boxes(proposals_xyz, proposals_output, nh=NH, ns=NS, nc=NC):
-    """model.py:100-129 on the device: -> bboxes (B,P,8,3), scores (B,P) = max class logit (the inputs of NMS3D)."""
-    from .synth import MEAN_SIZES
+def decode_boxes(proposals_xyz, proposals_output, nh=NH, ns=NS, nc=NC, head=None, mean_sizes=None):
+    """model.py:100-129 on the device: -> bboxes (B,P,8,3), scores (B,P) = max class logit (the inputs of NMS3D).
+    head: the HeadConfig whose bins and size templates decode (None: the keywords' bins and the default head's templates).
+    mean_sizes: the templates as an (ns, 3) float32 tensor already on the device (a net keeps one: VoteNetHotPath.decode_boxes)."""
+    nh, ns, nc = _head_bins(head, nh, ns, nc)
     pxyz = L.dev_f32(proposals_xyz, "decode_boxes proposals_xyz", 3, 3)
     pout = L.dev_f32(proposals_output, "decode_boxes proposals_output", 3)
     b, p = pxyz.shape[:2]
     if pout.shape[2] != 5 + 2 * nh + 4 * ns + nc:
         raise L.InvalidArgumentError("decode_boxes: proposals_output has %d channels" % pout.shape[2])
-    mean = torch.tensor(MEAN_SIZES, dtype=torch.float32, device=pxyz.device).contiguous()
+    if mean_sizes is not None:
+        mean = L.dev_f32(mean_sizes, "decode_boxes mean_sizes", 2, 3)
+        if mean.device != pxyz.device:
+            raise L.InvalidArgumentError("decode_boxes: mean_sizes live on another device than the proposals")
+    else:
+        from .synth import MEAN_SIZES
+        mean = torch.tensor(head.mean_sizes_f32 if head is not None else MEAN_SIZES, dtype=torch.float32, device=pxyz.device).contiguous()
+    if mean.shape[0] < ns:
+        raise L.InvalidArgumentError("decode_boxes: %d size templates for ns = %d" % (mean.shape[0], ns))
     boxes = torch.empty((b, p, 8, 3), dtype=torch.float32, device=pxyz.device)
     scores = torch.empty((b, p), dtype=torch.float32, device=pxyz.device)
     with L.device_guard(pxyz.device):

@@ -19,6 +19,7 @@ import torch
 
 from . import checkpoint
 from . import dp
+from . import head as H
 from . import mlp as M
 from . import pointnet2 as P
 
@@ -280,6 +281,7 @@ class StretchGraph:
         self.nd = nd
         self.arena = torch.empty(nd + (n32 + 1) // 2, dtype=torch.float64, device=dev)
         self.segments = []  # (graph, [(thunk, tensors) ...]) in replay order
+        self.head = net.head  # (the loss launch of every replay reads its nh / ns / nc)
         self._losses = torch.empty(12, dtype=torch.float32, device=dev)
         self._loss_ring = [torch.empty(12, dtype=torch.float32, device=dev) for _ in range(8)]
         self.replays = 0
@@ -352,7 +354,7 @@ class StretchGraph:
                     # the loss launch is not captured and no captured kernel reads the 12 losses: each replay writes them into the next
                     # vector of a small ring, so a handle to last_losses kept across a few steps still shows ITS step (no copy launch)
                     losses = self._loss_ring[self.replays % len(self._loss_ring)]
-                    VL.votenet_loss(self.out, gt, buffers=(losses, self.loss_bufs[1]))
+                    VL.votenet_loss(self.out, gt, buffers=(losses, self.loss_bufs[1]), head=self.head)
                     if after_loss is not None:
                         after_loss(self.out, gt, losses, self.cot)
                 graph.replay()
@@ -365,16 +367,34 @@ class StretchGraph:
         return _StretchOutputs(self.out, self), losses, self.grads
 
 
+class _Load:
+    """VoteNetHotPath.load, both ways.  net.load(path, strict=True): restore a file written by save() in place, between two train_step
+    calls or before predict.  VoteNetHotPath.load(path, device, **kw): a new net built for the file -- its head (NH and the size
+    templates of the header; a file without templates has the default ones), its npoints and, from sa1's first kernel, its
+    point_features -- with the file restored into it."""
+
+    def __get__(self, net, cls):
+        if net is not None:
+            return lambda path, strict=True: checkpoint.load(net, path, strict)
+        return lambda path, device, strict=True, **kw: checkpoint.load_new(cls, path, device, strict, **kw)
+
+
 SPLIT_BF16 = True  # fused GEMMs on bf16 x 3 split operands (fp32-accurate products, six bf16 MFMAs per k-step; mlp.SplitImages)
 
 
 class VoteNetHotPath:
-    def __init__(self, device, seed=0, npoints=(2048, 1024, 512, 256), point_features=0):
-        """point_features: 0 -- the reference's network: sa1's input features are the coordinates themselves (model.py:36,39) --, or c in
+    def __init__(self, device, seed=0, npoints=(2048, 1024, 512, 256), point_features=0, head=None):
+        """head: the dataset's detection head (head.HeadConfig: heading bins, classes, size templates); None: the reference's,
+        HeadConfig.sunrgbd().  The proposal module's last layer has head.width columns, and the loss, the decode, predict, the monitors
+        and the checkpoint header read net.head.  A net has one head for life.
+        point_features: 0 -- the reference's network: sa1's input features are the coordinates themselves (model.py:36,39) --, or c in
         1..5: sa1 takes c features per point beside the coordinates (height above the floor, colour, intensity:
         input_pipeline.subsample_augment_features), handed to forward / predict / train_step as feats (B, n, c).  3 + c <= 8, so sa1
         keeps its narrow first layer (csrc/narrow.hip); sa1/conv0/W then has 3 + c input rows."""
         self.device = device
+        if head is not None and not isinstance(head, H.HeadConfig):
+            raise M.L.InvalidArgumentError("VoteNetHotPath: head must be a head.HeadConfig, got %r" % type(head).__name__)
+        self.head = head if head is not None else H.HeadConfig.sunrgbd()
         c = int(point_features)
         if not 0 <= c <= 5:
             raise M.L.InvalidArgumentError("VoteNetHotPath: point_features must be in [0, 5] (sa1's narrow first layer serves 3 + c <= 8 "
@@ -393,7 +413,7 @@ class VoteNetHotPath:
         self.fp2 = P.FPModule(s, "fp2", 256, 256, [256, 256])               # model.py:49
         self.voting = P.make_mlp(s, "voting", 259, [256, 256, 259], "fc", last_plain=True)  # model.py:53-57
         self.proposal = P.SAModule(s, "proposal", PROPOSAL_NUM, 0.3, 64, 256, [128, 128, 128],
-                                   mlp2=[128, 128, PROPOSAL_OUT])           # model.py:89-93
+                                   mlp2=[128, 128, self.head.width])       # model.py:89-93 (79 for the default head)
         s.materialize(seed)
         s.enable_split(SPLIT_BF16)  # forward() refreshes the images at its start, refresh_transposes() those of the copies
         self._geometry = GeometryPrefetch(self._geometry_chain, lambda: self._side_stream(), device, self.proposal.npoint)
@@ -626,7 +646,14 @@ class VoteNetHotPath:
     def decode_boxes(self, proposals_xyz, proposals_output):
         """model.py:100-129 (votenet_decode_boxes): -> bboxes (B,N,8,3) in get_3d_bbox's corner order, class score (B,N)."""
         from . import loss as VL
-        return VL.decode_boxes(proposals_xyz, proposals_output)
+        return VL.decode_boxes(proposals_xyz, proposals_output, head=self.head, mean_sizes=self._mean_sizes_device(proposals_xyz.device))
+
+    def _mean_sizes_device(self, device):
+        """The head's size templates (nc, 3) float32 on `device`: uploaded once per net, not per decode."""
+        t = self.__dict__.get("_mean_sizes_dev")
+        if t is None or t.device != device:
+            t = self._mean_sizes_dev = torch.from_numpy(self.head.mean_sizes_f32.copy()).to(device).contiguous()
+        return t
 
     # ---- BatchNorm moving averages (training) and the inference-mode BatchNorm built from them ----------------------
     BN_MOMENTUM = 0.9  # Tensorpack BatchNorm default (`momentum=0.9`, epsilon 1e-5); Tensorpack is not in the reference tree
@@ -774,7 +801,7 @@ class VoteNetHotPath:
             gated = box_points.gate_objectness(objectness(), gate["point_counts"], min_points)
             objectness = lambda: gated
         if params is not None:
-            cls = out["proposals_output"][..., -NC:].contiguous()
+            cls = out["proposals_output"][..., self.head.sem].contiguous()
             if nms_overlap == "rotated":
                 det = detections.class_nms3d(boxes, objectness(), cls, **params)
             else:  # (the only place that loads libvotenet_aabb.so)
@@ -782,7 +809,7 @@ class VoteNetHotPath:
             return dict(bboxes=boxes, scores=score, class_scores=cls, **gate, **det, **out)
         keep = tf_nms3d.NMS3D(boxes, score, objectness(), iou_threshold, padded=not sync)
         extra = dict(gate) if sync else dict(nms_count=keep[1], **gate)
-        return dict(bboxes=boxes, scores=score, nms_idx=keep if sync else keep[0], class_scores=out["proposals_output"][..., -NC:].contiguous(),
+        return dict(bboxes=boxes, scores=score, nms_idx=keep if sync else keep[0], class_scores=out["proposals_output"][..., self.head.sem].contiguous(),
                     **extra, **out)
 
     # ---- backward / training --------------------------------------------------------
@@ -791,7 +818,7 @@ class VoteNetHotPath:
         (B,256,79) and d loss / d votes_xyz (B,1024,3).  Training uses the loss graph instead (train_step(gt=...))."""
         g = torch.Generator(device="cpu").manual_seed(1234 + seed)
         n_seed = self.sa2.npoint
-        return dict(proposals_output=(torch.randn(b, PROPOSAL_NUM, PROPOSAL_OUT, generator=g) / (b * PROPOSAL_NUM)).to(self.device),
+        return dict(proposals_output=(torch.randn(b, PROPOSAL_NUM, self.head.width, generator=g) / (b * PROPOSAL_NUM)).to(self.device),
                     votes_xyz=(torch.randn(b, n_seed, 3, generator=g) / (b * n_seed)).to(self.device))
 
     def backward(self, tape, cot):
@@ -924,7 +951,7 @@ class VoteNetHotPath:
         lv = {k: I[k] for k in ("l2_xyz", "l2_p", "l3_xyz", "l3_p", "l4_xyz", "l4_p")}
         out = self._head_forward(lv, geom("fp1"), geom("fp2"), I["prop_fps"], tail, copy_seeds=copy_seeds)
         self.update_moving_averages(list(tape_levels) + tail)
-        losses, cot = loss_hook(out) if loss_hook is not None else VL.votenet_loss(out, gt)
+        losses, cot = loss_hook(out) if loss_hook is not None else VL.votenet_loss(out, gt, head=self.head)
         if loss_hook is None:  # (captured: the loss and what runs behind it are launches of every replay, StretchGraph.replay)
             self._after_loss(out, gt, losses, cot)
         with P.WGRAD.on(wgrad_stream):
@@ -1172,7 +1199,8 @@ class VoteNetHotPath:
         if self.proposal_supervision == "paper":
             from . import proposal_supervision as PS  # (the only place of a train step that loads libvotenet_propsup.so)
             work, counts = self._loss_tail_buffers(PS, out["proposals_xyz"].shape[0], 3)
-            PS.paper_proposal_loss(out, gt, losses, d_xyz=cot["proposals_xyz"], d_out=cot["proposals_output"], counts=counts, work=work)
+            PS.paper_proposal_loss(out, gt, losses, d_xyz=cot["proposals_xyz"], d_out=cot["proposals_output"], counts=counts, work=work,
+                                   head=self.head)
         if self.monitors is not None:
             self.last_accuracies = self.monitors.after_loss(out, gt, losses)
 
@@ -1296,9 +1324,7 @@ class VoteNetHotPath:
         """Write the state to an .npz file at `path` (numeric arrays + a JSON header)."""
         checkpoint.save(self, path, optimizer)
 
-    def load(self, path, strict=True):
-        """Restore a file written by save(): in place, between two train_step calls or before predict."""
-        checkpoint.load(self, path, strict)
+    load = _Load()
 
     def train_step(self, x, cot=None, world=1, gt=None, next_x=None, feats=None, next_feats=None):
         """forward + loss + backward + (world>1: the RCCL all-reduce of the flat gradient bucket, its tail overlapped with the
@@ -1329,7 +1355,7 @@ class VoteNetHotPath:
                 if gt is not None:
                     from . import loss as VL
                     self._keep_seed_levels(tape)
-                    self.last_losses, cot = VL.votenet_loss(out, gt)
+                    self.last_losses, cot = VL.votenet_loss(out, gt, head=self.head)
                     self._after_loss(out, gt, self.last_losses, cot)
                 self._gsync.begin()
                 if PREFETCH_AFTER >= 5:  # the next batch's geometry chain under the BACKWARD pass

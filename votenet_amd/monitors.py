@@ -117,6 +117,7 @@ class Monitors:
             raise ValueError("monitors: window >= 1 and tensors_every >= 0 expected, got %d, %d" % (window, tensors_every))
         dev = net.device
         self.window, self.tensors_every = window, tensors_every
+        self.head = getattr(net, "head", None)  # the accuracy launch reads its nh / ns / nc (None: the default head's)
         self.steps = 0          # accuracy launches so far: the next one writes ring row steps % window
         self.ring = torch.zeros((window, VL.RING_COLS), dtype=torch.float32, device=dev)
         self.accuracies = torch.zeros(2, dtype=torch.float32, device=dev)
@@ -128,7 +129,7 @@ class Monitors:
     def after_loss(self, out, gt, losses):
         """The accuracy launch of one step, behind its loss launch on the same stream."""
         VL.votenet_accuracies(out, gt, losses=losses, ring=self.ring, ring_row=self.steps % self.window,
-                              buffers=(self.accuracies, self.counts, self._work))
+                              buffers=(self.accuracies, self.counts, self._work), head=self.head)
         self.steps += 1
         return self.accuracies
 

@@ -20,6 +20,7 @@ votes instead of on the seeds are a mode of their own: vote_sampling.py, VoteNet
 import torch
 
 from . import _lib as L
+from .head import resolve as _head_bins
 from .loss import NEGATIVE_THRES, POSITIVE_THRES, check_losses
 from .synth import NC, NH, NS
 
@@ -43,12 +44,14 @@ def _scene(out, gt, who, width=None):
     return pxyz, pout, gxyz, (b, p, gxyz.shape[1])
 
 
-def proposal_targets(out, gt, pos_thr=POSITIVE_THRES, neg_thr=NEGATIVE_THRES):
+def proposal_targets(out, gt, pos_thr=POSITIVE_THRES, neg_thr=NEGATIVE_THRES, head=None):
     """out: proposals_xyz (B,P,3), proposals_output (B,P,W) (columns 2..4 are read); gt: device tensors (loss.gt_to_device) -> int32
     tensors label (B,P): 1 positive, 0 negative, -1 grey; near_box (B,P): the nearest real box of a positive's PREDICTED centre, else
     -1; dual_prop (B,BB): the proposal whose predicted centre is nearest to real box j, -1 for a padding row; real_boxes (B,): the
-    scene's boxes without the repetitions of the last.  One launch, nothing synchronises; for inspection."""
-    pxyz, pout, gxyz, (b, p, bb) = _scene(out, gt, "proposal_targets")
+    scene's boxes without the repetitions of the last.  One launch, nothing synchronises; for inspection.  head: a HeadConfig whose
+    width proposals_output must have (None: any width >= 5)."""
+    nh, ns, nc = _head_bins(head, 0, 0, 0)
+    pxyz, pout, gxyz, (b, p, bb) = _scene(out, gt, "proposal_targets", 5 + 2 * nh + 4 * ns + nc if head is not None else None)
     dev = pxyz.device
     label = torch.empty((b, p), dtype=torch.int32, device=dev)
     near = torch.empty((b, p), dtype=torch.int32, device=dev)
@@ -67,13 +70,15 @@ def workspace(b, device):
 
 
 def paper_proposal_loss(out, gt, losses, d_xyz=None, d_out=None, counts=None, work=None, nh=NH, ns=NS, nc=NC,
-                        pos_thr=POSITIVE_THRES, neg_thr=NEGATIVE_THRES):
+                        pos_thr=POSITIVE_THRES, neg_thr=NEGATIVE_THRES, head=None):
     """out: the dict VoteNetHotPath.forward returns (proposals_xyz, proposals_output are read); gt: device tensors; losses: the 12 floats
     votenet_loss returned, changed IN PLACE: losses[2] becomes the paper's obj_cls_loss, losses[3] its center_loss, losses[9] and
     losses[0] are re-formed with them.  d_xyz (B,P,3), d_out (B,P,W) contiguous: votenet_loss's proposals_xyz / proposals_output
     cotangents; d_xyz is written in full, of d_out columns 0..4 of every row (the rest keeps its bits); None: fresh tensors (d_out zero
     beyond column 4).  counts: a three-element int32 device tensor for Np, Nn and the number of real boxes, or None: a fresh one.  work:
-    workspace(B, device) of a caller that keeps it.  -> d_xyz, d_out, counts.  One launch, nothing is read back."""
+    workspace(B, device) of a caller that keeps it.  head: the net's HeadConfig (its nh / ns / nc in place of the keywords').
+    -> d_xyz, d_out, counts.  One launch, nothing is read back."""
+    nh, ns, nc = _head_bins(head, nh, ns, nc)
     width = 5 + 2 * nh + 4 * ns + nc
     pxyz, pout, gxyz, (b, p, bb) = _scene(out, gt, "paper_proposal_loss", width)
     dev = pxyz.device

@@ -14,7 +14,28 @@ MEAN_SIZES = np.array([[2.114256, 1.620300, 0.927272], [0.791118, 1.279516, 0.71
                        [0.76584, 1.398258, 0.472728]], dtype=np.float64)
 
 
-def room_scene(n, seed, size=(5.0, 3.0, 5.0), nbox=(6, 10)):
+def room_head(nh, nc):
+    """A deterministic head for the synthetic rooms: nh heading bins and nc classes whose size templates are the SUN RGB-D ones taken
+    round and round, each round 15 % larger: MEAN_SIZES[c % 10] * (1 + 0.15 * (c // 10)).  room_head(12, 10) is the default head."""
+    from .head import HeadConfig
+    if isinstance(nc, bool) or not isinstance(nc, (int, np.integer)) or nc < 1:
+        from ._lib import InvalidArgumentError
+        raise InvalidArgumentError("room_head: nc must be an integer >= 1, got %r" % (nc,))
+    return HeadConfig(nh, [MEAN_SIZES[c % 10] * (1 + 0.15 * (c // 10)) for c in range(int(nc))])
+
+
+def _head_sizes(head):
+    """(class count, templates, one heading bin only?) of head; the default head's for None."""
+    if head is None:
+        return 10, MEAN_SIZES, False
+    return head.nc, head.mean_sizes_f64, head.nh == 1
+
+
+def room_scene(n, seed, size=(5.0, 3.0, 5.0), nbox=(6, 10), head=None):
+    """head (head.HeadConfig; synth.room_head makes one): the boxes' classes are drawn from range(head.nc), their sizes around the
+    head's templates, and with one heading bin every heading is 0 (axis-aligned boxes).  None, or the default head: the output of
+    every seed is what it always was."""
+    ncls, templates, upright = _head_sizes(head)
     rng = np.random.default_rng(seed)
     sx, sy, sz = size
     n_struct = int(n * 0.6)
@@ -33,9 +54,11 @@ def room_scene(n, seed, size=(5.0, 3.0, 5.0), nbox=(6, 10)):
     o = n_struct
     boxes = []
     for i in range(k):
-        cls = int(rng.integers(0, 10))  # SUN RGB-D class of the box (dataset.py:31-32); same draw as before: clouds unchanged
-        l, w, h = MEAN_SIZES[cls] * rng.uniform(0.8, 1.2, 3)
+        cls = int(rng.integers(0, ncls))  # SUN RGB-D class of the box (dataset.py:31-32); same draw as before: clouds unchanged
+        l, w, h = templates[cls] * rng.uniform(0.8, 1.2, 3)
         ang = rng.uniform(0, 2 * np.pi)
+        if upright:  # (drawn all the same: the generator's state does not depend on nh)
+            ang = 0.0
         cx, cz = rng.uniform(-sx / 2 + 0.8, sx / 2 - 0.8), rng.uniform(0.8, sz - 0.8)
         cy = -1.2 + h / 2
         q = rng.uniform(-0.5, 0.5, (per[i], 3)) * np.array([l, h, w])
@@ -56,11 +79,12 @@ def room_scene(n, seed, size=(5.0, 3.0, 5.0), nbox=(6, 10)):
     return pts.astype(np.float32), np.array(boxes, np.float32)
 
 
-def room_scene_labels(n, seed, size=(5.0, 3.0, 5.0), nbox=(6, 10)):
+def room_scene_labels(n, seed, size=(5.0, 3.0, 5.0), nbox=(6, 10), head=None):
     """The labels of room_scene(n, seed, size, nbox)'s points -> (instance (n,) int32: the index of the box a point was drawn on, -1
     for the floor and the walls; semantic (n,) int32: that box's SUN RGB-D class, -1 likewise).  room_scene's draws are replayed in
     its order, so the generator is in room_scene's state when the rows are shuffled, and the labels -- shuffled as rows of a 2-D array,
-    as the points are -- take the points' permutation."""
+    as the points are -- take the points' permutation.  head: room_scene's."""
+    ncls = _head_sizes(head)[0]
     rng = np.random.default_rng(seed)
     n_struct = int(n * 0.6)
     n_obj = n - n_struct
@@ -72,7 +96,7 @@ def room_scene_labels(n, seed, size=(5.0, 3.0, 5.0), nbox=(6, 10)):
     labels = np.full((n, 2), -1, np.int32)
     o = n_struct
     for i in range(k):
-        cls = int(rng.integers(0, 10))
+        cls = int(rng.integers(0, ncls))
         rng.uniform(0.8, 1.2, 3)                               # l, w, h
         rng.uniform(0, 2 * np.pi)                              # ang
         rng.uniform(0.0, 1.0), rng.uniform(0.0, 1.0)           # cx, cz (one double each, whatever the bounds)
@@ -86,7 +110,7 @@ def room_scene_labels(n, seed, size=(5.0, 3.0, 5.0), nbox=(6, 10)):
     return labels[:, 0].copy(), labels[:, 1].copy()
 
 
-def room_batch(b, n, seed0=1000, **kw):
+def room_batch(b, n, seed0=1000, **kw):  # (kw: room_scene's, head= among them)
     return np.stack([room_scene(n, seed0 + i, **kw)[0] for i in range(b)])
 
 
@@ -109,20 +133,25 @@ def angle2class(angle, num_class=NH):
     return (0 if cid >= num_class else cid), res
 
 
-def room_gt(b, n, seed0=1000, **kw):
+def room_gt(b, n, seed0=1000, head=None, **kw):
     """Ground truth of room_batch(b, n, seed0) in the reference's input layout (model.py:22-32, dataset.py:279-299): the
     generating boxes, ragged lists padded to the longest by repeating the last box (run.py:14-24, np.pad mode='edge').
     -> dict of float32 / int32 arrays: bboxes_xyz (b,BB,3), bboxes_lwh (b,BB,3), bboxes_roty (b,BB), semantic_labels,
-    heading_labels (b,BB), heading_residuals (b,BB), size_labels (b,BB), size_residuals (b,BB,3)."""
+    heading_labels (b,BB), heading_residuals (b,BB), size_labels (b,BB), size_residuals (b,BB,3).
+    head: room_scene's; its heading bins and templates encode the labels."""
+    _, templates, _ = _head_sizes(head)
+    nh = head.nh if head is not None else NH
+    if head is not None:
+        kw["head"] = head
     per_scene = []
     for i in range(b):
         boxes = room_scene(n, seed0 + i, **kw)[1].astype(np.float64)
         rows = []
         for cx, cy, cz, l, w, h, ang, cls in boxes:
             cls = int(cls)
-            hc, hr = angle2class(ang)
+            hc, hr = angle2class(ang, nh)
             size = np.array([l, w, h])
-            rows.append((np.array([cx, cy, cz]), size, ang, cls, hc, hr / (np.pi / NH), cls, (size - MEAN_SIZES[cls]) / MEAN_SIZES[cls]))
+            rows.append((np.array([cx, cy, cz]), size, ang, cls, hc, hr / (np.pi / nh), cls, (size - templates[cls]) / templates[cls]))
         per_scene.append(rows)
     bb = max(len(r) for r in per_scene)
     for r in per_scene:
