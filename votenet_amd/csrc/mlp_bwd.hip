@@ -937,89 +937,82 @@ extern "C" int votenet_mlp_wgrad_bn(const votenet_mlp_input *in, long rows, int 
     return wgrad_entry(in, rows, cin, cout, nullptr, bs, da ? 1 : 2, dw, scratch, stream);
 }
 
-// Weight gradient of the SECOND layer of a chain whose first layer is NARROW (narrow.hip): dw (c0 x cout) += act(z0)^T dz1 with
-// z0 rebuilt from u8 in the loader (act = relu(z0*in_scale+in_shift)) and dz1 from (da, z, coef) as votenet_mlp_wgrad_bn.
+// ---- weight gradient of the SECOND layer of a chain whose first layer is rebuilt in the loader: dw (c0 x cout) += act(z0)^T dz1 with
+// act = relu(z0*in_scale+in_shift) and dz1 from (da, z, coef) as votenet_mlp_wgrad_bn.  Four entries, one impl: the one place that builds
+// their MlpIn and BnSrc.  `first` arrives with the first layer's rows: narrow_first (mode 2) or assembled_first (mode 3).
+static MlpIn narrow_first(const float *u8, const float *w0, const float *b0, int k0)
+{
+    MlpIn d = {};
+    d.u8 = u8;
+    d.w0 = w0;
+    d.b0 = b0;
+    d.k0 = k0;
+    return d;
+}
+static MlpIn assembled_first(const float *geo, const float *P, const float *wx)
+{
+    MlpIn d = {};
+    d.geo = geo;
+    d.ptab = P;
+    d.wx = wx;
+    return d;
+}
+static int rebuilt_wgrad_bn_impl(const char *name, const char *not_served, int mode, MlpIn d, long rows, int c0, int cout, const float *in_scale,
+                                 const float *in_shift, int in_relu, const float *da, const float *z, const float *coef, int relu, int bsrc,
+                                 const float *wh, const int *nh_dev, float *dw, float *scratch, void *stream)
+{
+    const bool narrow = mode == 2;
+    VN_REQUIRE(rows > 0 && rows < (1L << 31) && (!narrow || (d.k0 >= 3 && d.k0 <= 8)) && c0 > 0 && cout > 0, "%s: bad shape", name);
+    VN_REQUIRE((narrow ? d.u8 && d.w0 : d.geo && d.ptab && d.wx) && in_scale && in_shift && da && z && coef && dw, "%s: null buffer", name);
+    d.in_scale = in_scale;
+    d.in_shift = in_shift;
+    d.in_relu = in_relu;
+    BnSrc bs = {da, nullptr, nullptr, 0, -1, z, coef, relu, nullptr, 0, wh, nh_dev};
+    if (!wgrad_fast_launch(mode, d, rows, c0, cout, nullptr, bs, bsrc, dw, as_stream(stream), scratch))
+        return set_error(VOTENET_E_INVALID_ARGUMENT, "%s: %s", name, not_served);
+    return check_launch(name);
+}
+
+// The first layer is NARROW (narrow.hip): z0 rebuilt from u8.
 extern "C" int votenet_narrow_wgrad_bn(long rows, int k0, int c0, int cout, const float *u8, const float *w0, const float *b0,
                                        const float *in_scale, const float *in_shift, int in_relu, const float *da, const float *z,
                                        const float *coef, int relu, float *dw, float *scratch, void *stream)
 {
-    VN_REQUIRE(rows > 0 && rows < (1L << 31) && k0 >= 3 && k0 <= 8 && c0 > 0 && cout > 0, "narrow_wgrad_bn: bad shape");
-    VN_REQUIRE(u8 && w0 && in_scale && in_shift && da && z && coef && dw, "narrow_wgrad_bn: null buffer");
-    MlpIn d = {};
-    d.in_scale = in_scale;
-    d.in_shift = in_shift;
-    d.in_relu = in_relu;
-    d.u8 = u8;
-    d.w0 = w0;
-    d.b0 = b0;
-    d.k0 = k0;
-    BnSrc bs = {da, nullptr, nullptr, 0, -1, z, coef, relu, nullptr, 0};
-    if (!wgrad_fast_launch(2, d, rows, c0, cout, nullptr, bs, 1, dw, as_stream(stream), scratch))
-        return set_error(VOTENET_E_INVALID_ARGUMENT, "narrow_wgrad_bn: shape not served (c0 %% 64 == 0, cout %% 64 == 0, 16-byte aligned buffers)");
-    return check_launch("narrow_wgrad_bn");
+    return rebuilt_wgrad_bn_impl("narrow_wgrad_bn", "shape not served (c0 % 64 == 0, cout % 64 == 0, 16-byte aligned buffers)", 2,
+                                 narrow_first(u8, w0, b0, k0), rows, c0, cout, in_scale, in_shift, in_relu, da, z, coef, relu, /* bsrc */ 1,
+                                 nullptr, nullptr, dw, scratch, stream);
 }
-
-// votenet_narrow_wgrad_bn on the piece layout (half.hip): da holds totals per compact row, the affine part of dz1 is weighted.
+// votenet_narrow_wgrad_bn on the piece layout (half.hip): da holds totals per compact row, the affine part of dz1 is weighted (BSRC 4);
+// whole pairs of pieces, no scratch.
 extern "C" int votenet_narrow_wgrad_bn_half(long rows, int k0, int c0, int cout, const float *u8, const float *w0, const float *b0,
                                             const float *in_scale, const float *in_shift, int in_relu, const float *da, const float *z,
                                             const float *coef, int relu, const float *wh, float *dw, void *stream)
 {
-    VN_REQUIRE(rows > 0 && rows % 32 == 0 && rows < (1L << 31) && k0 >= 3 && k0 <= 8 && c0 > 0 && cout > 0, "narrow_wgrad_bn_half: bad shape");
-    VN_REQUIRE(u8 && w0 && in_scale && in_shift && da && z && coef && wh && dw, "narrow_wgrad_bn_half: null buffer");
-    MlpIn d = {};
-    d.in_scale = in_scale;
-    d.in_shift = in_shift;
-    d.in_relu = in_relu;
-    d.u8 = u8;
-    d.w0 = w0;
-    d.b0 = b0;
-    d.k0 = k0;
-    BnSrc bs = {da, nullptr, nullptr, 0, -1, z, coef, relu, nullptr, 0, wh};
-    if (!wgrad_fast_launch(2, d, rows, c0, cout, nullptr, bs, 4, dw, as_stream(stream), nullptr))
-        return set_error(VOTENET_E_INVALID_ARGUMENT, "narrow_wgrad_bn_half: shape not served (as votenet_narrow_wgrad_bn)");
-    return check_launch("narrow_wgrad_bn_half");
+    VN_REQUIRE(rows % 32 == 0, "narrow_wgrad_bn_half: bad shape");
+    VN_REQUIRE(wh != nullptr, "narrow_wgrad_bn_half: null buffer");
+    return rebuilt_wgrad_bn_impl("narrow_wgrad_bn_half", "shape not served (as votenet_narrow_wgrad_bn)", 2, narrow_first(u8, w0, b0, k0), rows,
+                                 c0, cout, in_scale, in_shift, in_relu, da, z, coef, relu, /* bsrc */ 4, wh, nullptr, dw, nullptr, stream);
 }
 
-// Weight gradient of the SECOND layer of a chain whose first layer is ASSEMBLED (assemble.hip): dw (c0 x cout) += act(z0)^T dz1 with
-// z0[r,:] = P[prow(r),:] + dxyz(r) . wx rebuilt in the loader (act = relu(z0*in_scale+in_shift)), dz1 from (da, z, coef).
+// The first layer is ASSEMBLED (assemble.hip): z0[r,:] = P[prow(r),:] + dxyz(r) . wx.
 extern "C" int votenet_assembled_wgrad_bn(long rows, int c0, int cout, const float *geo, const float *P, const float *wx,
                                           const float *in_scale, const float *in_shift, int in_relu, const float *da, const float *z,
                                           const float *coef, int relu, float *dw, float *scratch, void *stream)
 {
-    VN_REQUIRE(rows > 0 && rows < (1L << 31) && c0 > 0 && cout > 0, "assembled_wgrad_bn: bad shape");
-    VN_REQUIRE(geo && P && wx && in_scale && in_shift && da && z && coef && dw, "assembled_wgrad_bn: null buffer");
-    MlpIn d = {};
-    d.in_scale = in_scale;
-    d.in_shift = in_shift;
-    d.in_relu = in_relu;
-    d.geo = geo;
-    d.ptab = P;
-    d.wx = wx;
-    BnSrc bs = {da, nullptr, nullptr, 0, -1, z, coef, relu, nullptr, 0};
-    if (!wgrad_fast_launch(3, d, rows, c0, cout, nullptr, bs, 1, dw, as_stream(stream), scratch))
-        return set_error(VOTENET_E_INVALID_ARGUMENT, "assembled_wgrad_bn: shape not served (c0 %% 64 == 0, cout %% 64 == 0, 16-byte aligned buffers)");
-    return check_launch("assembled_wgrad_bn");
+    return rebuilt_wgrad_bn_impl("assembled_wgrad_bn", "shape not served (c0 % 64 == 0, cout % 64 == 0, 16-byte aligned buffers)", 3,
+                                 assembled_first(geo, P, wx), rows, c0, cout, in_scale, in_shift, in_relu, da, z, coef, relu, /* bsrc */ 1,
+                                 nullptr, nullptr, dw, scratch, stream);
 }
-
 // The same on the piece layout (half.hip): da holds TOTAL gradients per compact row, the affine part of the rebuilt dz1 counts wh[q]
-// times on row 16 q.
+// times on row 16 q (BSRC 4); whole pairs of pieces, no scratch; the only one of the four that takes the device's piece count.
 extern "C" int votenet_assembled_wgrad_bn_half(long rows, int c0, int cout, const float *geo, const float *P, const float *wx,
                                                const float *in_scale, const float *in_shift, int in_relu, const float *da, const float *z,
                                                const float *coef, int relu, const float *wh, float *dw, const int *nh_dev, void *stream)
 {
-    VN_REQUIRE(rows > 0 && rows % 32 == 0 && rows < (1L << 31) && c0 > 0 && cout > 0, "assembled_wgrad_bn_half: bad shape");
-    VN_REQUIRE(geo && P && wx && in_scale && in_shift && da && z && coef && wh && dw, "assembled_wgrad_bn_half: null buffer");
-    MlpIn d = {};
-    d.in_scale = in_scale;
-    d.in_shift = in_shift;
-    d.in_relu = in_relu;
-    d.geo = geo;
-    d.ptab = P;
-    d.wx = wx;
-    BnSrc bs = {da, nullptr, nullptr, 0, -1, z, coef, relu, nullptr, 0, wh, nh_dev};
-    if (!wgrad_fast_launch(3, d, rows, c0, cout, nullptr, bs, 4, dw, as_stream(stream), nullptr))
-        return set_error(VOTENET_E_INVALID_ARGUMENT, "assembled_wgrad_bn_half: shape not served (as votenet_assembled_wgrad_bn)");
-    return check_launch("assembled_wgrad_bn_half");
+    VN_REQUIRE(rows % 32 == 0, "assembled_wgrad_bn_half: bad shape");
+    VN_REQUIRE(wh != nullptr, "assembled_wgrad_bn_half: null buffer");
+    return rebuilt_wgrad_bn_impl("assembled_wgrad_bn_half", "shape not served (as votenet_assembled_wgrad_bn)", 3, assembled_first(geo, P, wx),
+                                 rows, c0, cout, in_scale, in_shift, in_relu, da, z, coef, relu, /* bsrc */ 4, wh, nh_dev, dw, nullptr, stream);
 }
 
 // coefficient vector [A | B | C | scale | shift] (5*c floats) of the folded BatchNorm backward, from the reductions

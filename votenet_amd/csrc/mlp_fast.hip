@@ -1631,23 +1631,104 @@ static bool fast_dispatch(const FastArgs &a_in, hipStream_t st)
     return false;
 }
 
-// returns true when the fast kernel took the launch
-bool mlp_linear_fast_launch(const float *x, const float *in_scale, const float *in_shift, const BnRaw &in_raw, int in_relu,
-                            long rows, int cin, int cout, const float *w, const float *bias, float *z, double *stats, hipStream_t st)
+// ---- the host launch surface ---------------------------------------------------------------------------------------------------------
+// One builder per group of FastArgs: an entry point names the groups its operand form has and nothing else, so a field added to a group
+// reaches every entry that has the group.  Twin entries (plain / _half / _masked) share one impl; what tells them apart stands in their
+// wrappers, or in one commented line of the impl.
+// the GEMM proper
+static void set_gemm(FastArgs &a, long rows, int cin, int cout, const float *w, const float *bias, float *z)
 {
-    FastArgs a = {};
-    a.x = x;
-    a.in_scale = in_scale;
-    a.in_shift = in_shift;
-    a.in_raw = in_raw;
-    a.in_relu = in_relu;
     a.rows = rows;
     a.cin = cin;
     a.cout = cout;
     a.w = w;
     a.bias = bias;
     a.z = z;
+}
+// the input affine: relu(. * in_scale + in_shift), or the same derived from the producer's raw sums
+static void set_in_affine(FastArgs &a, const float *in_scale, const float *in_shift, const BnRaw &in_raw, int in_relu)
+{
+    a.in_scale = in_scale;
+    a.in_shift = in_shift;
+    a.in_raw = in_raw;
+    a.in_relu = in_relu;
+}
+// SRC 1 / 5: what dz is rebuilt from
+static void set_dz(FastArgs &a, const float *da, const float *zsrc, const float *coef, int src_relu)
+{
+    a.da = da;
+    a.zsrc = zsrc;
+    a.coef = coef;
+    a.src_relu = src_relu;
+}
+// EPI 3 / 4 / 6 / 7: the BatchNorm of the layer below, its backward sums and its coefficient tail
+static void set_below(FastArgs &a, const float *scale, const float *shift, const float *mean, const float *var, float eps, int relu,
+                      double *sums, const votenet_coef_tail *tail)
+{
+    a.e_scale = scale;
+    a.e_shift = shift;
+    a.e_mean = mean;
+    a.e_var = var;
+    a.e_eps = eps;
+    a.e_relu = relu;
+    a.stats = sums;
+    a.tail = to_tail(tail);
+}
+// SRC 4 / EPI 6: assembled rows
+static void set_assembled(FastArgs &a, const float *geo, const float *P, const float *wx)
+{
+    a.geo = geo;
+    a.ptab = P;
+    a.wx = wx;
+}
+// SRC 3 / EPI 4 / EPI 7: narrow rows
+static void set_narrow(FastArgs &a, const float *u8, const float *w0, const float *b0, int k0)
+{
+    a.u8 = u8;
+    a.w0 = w0;
+    a.b0 = b0;
+    a.k0 = k0;
+}
+// the piece layout (half.hip): the weight of every piece's row 0 and, where only the device knows it, the piece count
+static void set_pieces(FastArgs &a, const float *wh, const int *nh_dev)
+{
+    a.wh = wh;
+    a.nh_dev = nh_dev;
+}
+// the checks more than one twin set makes
+static bool tail_complete(const votenet_coef_tail *t) { return !t || (t->ticket && t->gamma && t->coef && t->rows > 0); }
+static bool first_bn_given(const votenet_bn_raw *in_bn, const float *in_scale, const float *in_shift)
+{
+    return in_bn != nullptr || (in_scale != nullptr && in_shift != nullptr);
+}
+static bool below_given(const float *scale, const float *shift, const float *mean, const float *var, const double *sums)
+{
+    return scale && shift && mean && var && sums;
+}
+// the end of every entry: `why` is the entry's own text for a shape fast_dispatch did not serve
+static int launched(bool served, const char *name, const char *why)
+{
+    if (!served) return set_error(VOTENET_E_INVALID_ARGUMENT, "%s: %s", name, why);
+    return check_launch(name);
+}
+
+// what the three dense forward launches share: x through its folded BatchNorm + ReLU, times w
+static FastArgs dense_forward_args(const float *x, const float *in_scale, const float *in_shift, const BnRaw &in_raw, int in_relu, long rows,
+                                   int cin, int cout, const float *w, const float *bias, float *z, double *stats)
+{
+    FastArgs a = {};
+    a.x = x;
+    set_in_affine(a, in_scale, in_shift, in_raw, in_relu);
+    set_gemm(a, rows, cin, cout, w, bias, z);
     a.stats = stats;
+    return a;
+}
+
+// returns true when the fast kernel took the launch
+bool mlp_linear_fast_launch(const float *x, const float *in_scale, const float *in_shift, const BnRaw &in_raw, int in_relu,
+                            long rows, int cin, int cout, const float *w, const float *bias, float *z, double *stats, hipStream_t st)
+{
+    const FastArgs a = dense_forward_args(x, in_scale, in_shift, in_raw, in_relu, rows, cin, cout, w, bias, z, stats);
     return stats ? fast_dispatch<0, 0>(a, st) : fast_dispatch<0, 1>(a, st); // no statistics wanted: skip their arithmetic
 }
 
@@ -1658,21 +1739,10 @@ extern "C" int votenet_mlp_linear_half(const float *x, const float *in_scale, co
 {
     VN_REQUIRE(rows > 0 && cin > 0 && cout > 0 && x && w && z && nh_dev, "mlp_linear_half: bad arguments");
     VN_REQUIRE((in_scale == nullptr) == (in_shift == nullptr), "mlp_linear_half: in_scale and in_shift go together");
-    FastArgs a = {};
-    a.x = x;
-    a.in_scale = in_scale;
-    a.in_shift = in_shift;
-    a.in_relu = in_relu;
-    a.rows = rows;
-    a.cin = cin;
-    a.cout = cout;
-    a.w = w;
-    a.bias = bias;
-    a.z = z;
-    a.nh_dev = nh_dev;
-    if (!fast_dispatch<0, 1>(a, as_stream(stream)))
-        return set_error(VOTENET_E_INVALID_ARGUMENT, "mlp_linear_half: shape not served (rows %% 128 == 0, cin %% 32 == 0, cout %% 64 == 0, 16-byte aligned)");
-    return check_launch("mlp_linear_half");
+    FastArgs a = dense_forward_args(x, in_scale, in_shift, BnRaw{}, in_relu, rows, cin, cout, w, bias, z, nullptr);
+    set_pieces(a, nullptr, nh_dev); // nothing is summed: no weights
+    return launched(fast_dispatch<0, 1>(a, as_stream(stream)), "mlp_linear_half",
+                    "shape not served (rows % 128 == 0, cin % 32 == 0, cout % 64 == 0, 16-byte aligned)");
 }
 
 // forward layer + raw max / min pooling over groups of 64 rows (EPI 2).  Returns false when the shape is not served.
@@ -1680,23 +1750,10 @@ bool mlp_linear_pool_launch(const float *x, const float *in_scale, const float *
                             long rows, int cin, int cout, const float *w, const float *bias, float *z, double *stats, float *zmax,
                             float *zmin, int *amax, int *amin, hipStream_t st, const float *wh, const float *pool_gamma, const int *nh_dev)
 {
-    FastArgs a = {};
-    a.nh_dev = nh_dev;
-    a.wh = wh;                       // piece layout (half.hip): weighted statistics ...
+    FastArgs a = dense_forward_args(x, in_scale, in_shift, in_raw, in_relu, rows, cin, cout, w, bias, z, stats);
+    set_pieces(a, wh, nh_dev);        // piece layout (half.hip): weighted statistics ...
     a.pool32 = wh != nullptr ? 1 : 0; // ... and the pool's candidate (max or min by the sign of gamma) per 16-row piece
     a.pool_gamma = pool_gamma;
-    a.x = x;
-    a.in_scale = in_scale;
-    a.in_shift = in_shift;
-    a.in_raw = in_raw;
-    a.in_relu = in_relu;
-    a.rows = rows;
-    a.cin = cin;
-    a.cout = cout;
-    a.w = w;
-    a.bias = bias;
-    a.z = z;
-    a.stats = stats;
     a.zmax = zmax;
     a.zmin = zmin;
     a.amax = amax;
@@ -1716,33 +1773,34 @@ bool mlp_linear_pool_launch(const float *x, const float *in_scale, const float *
 
 using namespace votenet;
 
+// What every input-gradient entry over a `rows x c` dz shares (the three dense ones below, the assembled pair): the shape check, the
+// buffers all of them need, the rebuilt-dz source and the GEMM.  da is not checked here: votenet_mlp_dgrad_bn may come with gout instead.
+static int dgrad_bn_args(FastArgs &a, const char *name, long rows, int c, int cout, const float *da, const float *zsrc, const float *coef,
+                         int relu, const float *wT, float *da_prev)
+{
+    VN_REQUIRE(rows > 0 && c > 0 && cout > 0, "%s expects rows > 0, c > 0, cout > 0", name);
+    VN_REQUIRE(zsrc && coef && wT && da_prev, "%s: null buffer", name);
+    set_dz(a, da, zsrc, coef, relu);
+    set_gemm(a, rows, c, cout, wT, nullptr, da_prev);
+    return VOTENET_OK;
+}
+
 // da_prev (rows x cout) = dz (rows x c) * wT (c x cout) with dz = BatchNorm-backward(da | pooled gout, zsrc, coef)
 // formed inside the A-operand loader.
 extern "C" int votenet_mlp_dgrad_bn(long rows, int c, int cout, const float *da, const float *gout, const int *argmax,
                                     int pool_k, const float *zsrc, const float *coef, int relu, const float *wT,
                                     float *da_prev, void *stream)
 {
-    VN_REQUIRE(rows > 0 && c > 0 && cout > 0, "mlp_dgrad_bn expects rows > 0, c > 0, cout > 0");
-    VN_REQUIRE((da != nullptr) != (gout != nullptr), "mlp_dgrad_bn: exactly one of da / gout");
-    VN_REQUIRE(zsrc && coef && wT && da_prev, "mlp_dgrad_bn: null buffer");
-    VN_REQUIRE(gout == nullptr || (argmax != nullptr && pool_k > 0 && rows % pool_k == 0), "mlp_dgrad_bn: pooled source needs argmax and k");
     FastArgs a = {};
-    a.da = da;
-    a.gout = gout;
+    if (const int rc = dgrad_bn_args(a, "mlp_dgrad_bn", rows, c, cout, da, zsrc, coef, relu, wT, da_prev)) return rc;
+    VN_REQUIRE((da != nullptr) != (gout != nullptr), "mlp_dgrad_bn: exactly one of da / gout");
+    VN_REQUIRE(gout == nullptr || (argmax != nullptr && pool_k > 0 && rows % pool_k == 0), "mlp_dgrad_bn: pooled source needs argmax and k");
+    a.gout = gout; // SRC 2: the max-pooled upstream gradient
     a.argmax = argmax;
     a.pool_k = pool_k;
-    a.zsrc = zsrc;
-    a.coef = coef;
-    a.src_relu = relu;
-    a.rows = rows;
-    a.cin = c;
-    a.cout = cout;
-    a.w = wT;
-    a.z = da_prev;
     hipStream_t st = as_stream(stream);
-    const bool ok = da ? fast_dispatch<1, 1>(a, st) : fast_dispatch<2, 1>(a, st);
-    if (!ok) return set_error(VOTENET_E_INVALID_ARGUMENT, "mlp_dgrad_bn: shape not supported by the fused kernel (use votenet_bn_backward_apply + votenet_mlp_linear)");
-    return check_launch("mlp_dgrad_bn");
+    return launched(da ? fast_dispatch<1, 1>(a, st) : fast_dispatch<2, 1>(a, st), "mlp_dgrad_bn",
+                    "shape not supported by the fused kernel (use votenet_bn_backward_apply + votenet_mlp_linear)");
 }
 
 // votenet_mlp_dgrad_bn (dense upstream gradient) on the piece layout (half.hip): da / da_prev are TOTAL gradients per compact row, the
@@ -1751,23 +1809,12 @@ extern "C" int votenet_mlp_dgrad_bn(long rows, int c, int cout, const float *da,
 extern "C" int votenet_mlp_dgrad_bn_half(long rows, int c, int cout, const float *da, const float *zsrc, const float *coef, int relu,
                                          const float *wT, float *da_prev, const float *wh, const int *nh_dev, void *stream)
 {
-    VN_REQUIRE(rows > 0 && c > 0 && cout > 0, "mlp_dgrad_bn_half expects rows > 0, c > 0, cout > 0");
-    VN_REQUIRE(da && zsrc && coef && wT && da_prev && wh, "mlp_dgrad_bn_half: null buffer");
     FastArgs a = {};
-    a.da = da;
-    a.zsrc = zsrc;
-    a.coef = coef;
-    a.src_relu = relu;
-    a.rows = rows;
-    a.cin = c;
-    a.cout = cout;
-    a.w = wT;
-    a.z = da_prev;
-    a.wh = wh;
-    a.nh_dev = nh_dev;
-    if (!fast_dispatch<5, 1>(a, as_stream(stream)))
-        return set_error(VOTENET_E_INVALID_ARGUMENT, "mlp_dgrad_bn_half: shape not served (rows %% 128 == 0, c %% 32 == 0, cout %% 64 == 0, 16-byte aligned buffers)");
-    return check_launch("mlp_dgrad_bn_half");
+    if (const int rc = dgrad_bn_args(a, "mlp_dgrad_bn_half", rows, c, cout, da, zsrc, coef, relu, wT, da_prev)) return rc;
+    VN_REQUIRE(da && wh, "mlp_dgrad_bn_half: null buffer");
+    set_pieces(a, wh, nh_dev);
+    return launched(fast_dispatch<5, 1>(a, as_stream(stream)), "mlp_dgrad_bn_half",
+                    "shape not served (rows % 128 == 0, c % 32 == 0, cout % 64 == 0, 16-byte aligned buffers)");
 }
 
 // The same GEMM whose epilogue also reduces the BatchNorm backward of the layer BELOW (the one whose activation da_prev is the
@@ -1779,67 +1826,38 @@ extern "C" int votenet_mlp_dgrad_bn_reduce(long rows, int c, int cout, const flo
                                            const float *shift_prev, const float *mean_prev, const float *var_prev, float eps,
                                            int relu_prev, double *sums, const votenet_coef_tail *tail, void *stream)
 {
-    VN_REQUIRE(!tail || (tail->ticket && tail->gamma && tail->coef && tail->rows > 0), "mlp_dgrad_bn_reduce: incomplete coefficient tail");
-    VN_REQUIRE(rows > 0 && c > 0 && cout > 0, "mlp_dgrad_bn_reduce expects rows > 0, c > 0, cout > 0");
-    VN_REQUIRE(da && zsrc && coef && wT && da_prev, "mlp_dgrad_bn_reduce: null buffer");
-    VN_REQUIRE(z_prev && scale_prev && shift_prev && mean_prev && var_prev && sums, "mlp_dgrad_bn_reduce: null buffer of the layer below");
+    VN_REQUIRE(tail_complete(tail), "mlp_dgrad_bn_reduce: incomplete coefficient tail");
     FastArgs a = {};
-    a.da = da;
-    a.zsrc = zsrc;
-    a.coef = coef;
-    a.src_relu = relu;
-    a.rows = rows;
-    a.cin = c;
-    a.cout = cout;
-    a.w = wT;
-    a.z = da_prev;
-    a.ez = z_prev;
-    a.e_scale = scale_prev;
-    a.e_shift = shift_prev;
-    a.e_mean = mean_prev;
-    a.e_var = var_prev;
-    a.e_eps = eps;
-    a.e_relu = relu_prev;
-    a.stats = sums;
-    a.tail = to_tail(tail);
-    if (!fast_dispatch<1, 3>(a, as_stream(stream)))
-        return set_error(VOTENET_E_INVALID_ARGUMENT, "mlp_dgrad_bn_reduce: shape not supported by the fused kernel (use votenet_mlp_dgrad_bn + votenet_bn_backward_reduce)");
-    return check_launch("mlp_dgrad_bn_reduce");
+    if (const int rc = dgrad_bn_args(a, "mlp_dgrad_bn_reduce", rows, c, cout, da, zsrc, coef, relu, wT, da_prev)) return rc;
+    VN_REQUIRE(da, "mlp_dgrad_bn_reduce: null buffer");
+    VN_REQUIRE(z_prev && below_given(scale_prev, shift_prev, mean_prev, var_prev, sums), "mlp_dgrad_bn_reduce: null buffer of the layer below");
+    a.ez = z_prev; // EPI 3: the layer below's z is read, not rebuilt
+    set_below(a, scale_prev, shift_prev, mean_prev, var_prev, eps, relu_prev, sums, tail);
+    return launched(fast_dispatch<1, 3>(a, as_stream(stream)), "mlp_dgrad_bn_reduce",
+                    "shape not supported by the fused kernel (use votenet_mlp_dgrad_bn + votenet_bn_backward_reduce)");
 }
 
 // Second layer of an SA chain whose first layer is NARROW (narrow.hip): z (rows x cout) = relu(bn0(z0)) w + bias with
 // z0[r,:] = narrow_z(u8[r], W0, b0) rebuilt in the operand loader (z0 is never stored), bn0 from raw statistics (in_bn) or from
-// in_scale / in_shift.  stats as for votenet_mlp_linear.
+// in_scale / in_shift.  stats as for votenet_mlp_linear.  The three entries answer with the plain entry's name.
 static int narrow_linear_impl(long rows, int k0, int c0, int cout, const float *u8, const float *w0, const float *b0, const float *in_scale,
                               const float *in_shift, const votenet_bn_raw *in_bn, int in_relu, const float *w, const float *bias, float *z,
                               double *stats, const float *wh, void *stream, unsigned short *mask_out = nullptr)
 {
     VN_REQUIRE(rows > 0 && k0 >= 3 && k0 <= 8 && c0 > 0 && cout > 0, "narrow_linear expects rows > 0, 3 <= k0 <= 8, c0 > 0, cout > 0");
     VN_REQUIRE(u8 && w0 && w && z, "narrow_linear: null buffer");
-    VN_REQUIRE(in_bn != nullptr || (in_scale != nullptr && in_shift != nullptr), "narrow_linear: the first layer's BatchNorm is missing");
-    FastArgs a = {};
-    a.u8 = u8;
-    a.w0 = w0;
-    a.b0 = b0;
-    a.k0 = k0;
-    a.in_scale = in_scale;
-    a.in_shift = in_shift;
-    a.in_raw = to_raw(in_bn);
-    a.in_relu = in_relu;
-    a.rows = rows;
-    a.cin = c0;
-    a.cout = cout;
-    a.w = w;
-    a.bias = bias;
-    a.z = z;
-    a.stats = stats;
-    a.wh = wh; // piece layout (half.hip): the statistics weigh row 0 of every piece
-    a.mask_out = mask_out;
+    VN_REQUIRE(first_bn_given(in_bn, in_scale, in_shift), "narrow_linear: the first layer's BatchNorm is missing");
     VN_REQUIRE(mask_out == nullptr || (uintptr_t)mask_out % 8 == 0, "narrow_linear: the mask must be 8-byte aligned");
+    FastArgs a = {};
+    set_narrow(a, u8, w0, b0, k0);
+    set_in_affine(a, in_scale, in_shift, to_raw(in_bn), in_relu);
+    set_gemm(a, rows, c0, cout, w, bias, z);
+    a.stats = stats;
+    set_pieces(a, wh, nullptr); // piece layout (half.hip): the statistics weigh row 0 of every piece
+    a.mask_out = mask_out;
     hipStream_t st = as_stream(stream);
-    const bool ok = stats ? fast_dispatch<3, 0>(a, st) : fast_dispatch<3, 1>(a, st);
-    if (!ok) return set_error(VOTENET_E_INVALID_ARGUMENT, "narrow_linear: shape not served (rows %% 128 == 0, c0 %% 32 == 0, c0 <= 128, cout == 64 or cout %% 128 == 0, 16-byte aligned buffers)");
-    return check_launch("narrow_linear");
+    return launched(stats ? fast_dispatch<3, 0>(a, st) : fast_dispatch<3, 1>(a, st), "narrow_linear",
+                    "shape not served (rows % 128 == 0, c0 % 32 == 0, c0 <= 128, cout == 64 or cout % 128 == 0, 16-byte aligned buffers)");
 }
 extern "C" int votenet_narrow_linear(long rows, int k0, int c0, int cout, const float *u8, const float *w0, const float *b0,
                                      const float *in_scale, const float *in_shift, const votenet_bn_raw *in_bn, int in_relu,
@@ -1869,50 +1887,33 @@ extern "C" int votenet_narrow_linear_masked(long rows, int k0, int c0, int cout,
 // Input-gradient GEMM of that second layer: da0 = dz1 wT (dz1 from (da, zsrc, coef) as votenet_mlp_dgrad_bn) is NOT stored; its
 // epilogue reduces the first layer's BatchNorm backward (sums: 2*c0 doubles, as votenet_mlp_dgrad_bn_reduce, z0 rebuilt from u8)
 // and ug[d*c0 + c] += sum_r u8[r,d] da0'[r,c] (8*c0 doubles), the data term of votenet_narrow_wgrad_first.  Both pre-zeroed.
+// The plain and the _half entry answer with the plain entry's name.
 static int narrow_dgrad_bn_reduce_impl(long rows, int c, int c0, int k0, const float *da, const float *zsrc, const float *coef, int relu,
                                        const float *wT, const float *u8, const float *w0, const float *b0, const float *scale0,
                                        const float *shift0, const float *mean0, const float *var0, float eps, int relu0, double *sums,
                                        double *ug, const votenet_coef_tail *tail, const float *wh, void *stream,
                                        const void *mask = nullptr)
 {
-    VN_REQUIRE(!tail || (tail->ticket && tail->gamma && tail->coef && tail->rows > 0), "narrow_dgrad_bn_reduce: incomplete coefficient tail");
+    VN_REQUIRE(tail_complete(tail), "narrow_dgrad_bn_reduce: incomplete coefficient tail");
     VN_REQUIRE(rows > 0 && c > 0 && c0 > 0 && k0 >= 3 && k0 <= 8, "narrow_dgrad_bn_reduce expects rows > 0, c > 0, c0 > 0, 3 <= k0 <= 8");
     VN_REQUIRE(da && zsrc && coef && wT && u8 && w0, "narrow_dgrad_bn_reduce: null buffer");
-    VN_REQUIRE(scale0 && shift0 && mean0 && var0 && sums && ug, "narrow_dgrad_bn_reduce: null buffer of the first layer");
+    VN_REQUIRE(below_given(scale0, shift0, mean0, var0, sums) && ug, "narrow_dgrad_bn_reduce: null buffer of the first layer");
     FastArgs a = {};
-    a.da = da;
-    a.zsrc = zsrc;
-    a.coef = coef;
-    a.src_relu = relu;
-    a.rows = rows;
-    a.cin = c;
-    a.cout = c0;
-    a.w = wT;
-    a.u8 = u8;
-    a.w0 = w0;
-    a.b0 = b0;
-    a.k0 = k0;
-    a.e_scale = scale0;
-    a.e_shift = shift0;
-    a.e_mean = mean0;
-    a.e_var = var0;
-    a.e_eps = eps;
-    a.e_relu = relu0;
-    a.stats = sums;
+    set_dz(a, da, zsrc, coef, relu);
+    set_gemm(a, rows, c, c0, wT, nullptr, nullptr); // nothing is stored
+    set_narrow(a, u8, w0, b0, k0);
+    set_below(a, scale0, shift0, mean0, var0, eps, relu0, sums, tail);
     a.ug = ug;
-    a.tail = to_tail(tail);
-    a.wh = wh; // piece layout: da holds totals, the affine part of the rebuilt dz1 counts wh[q] times on row 16 q (SRC 5)
+    set_pieces(a, wh, nullptr); // piece layout: da holds totals, the affine part of the rebuilt dz1 counts wh[q] times on row 16 q (SRC 5)
+    hipStream_t st = as_stream(stream);
     if (mask != nullptr) { // EPI 7: the mask the forward pass recorded instead of the rebuild of z0; s2 from the tail
         VN_REQUIRE(tail != nullptr && wh != nullptr && c0 % 64 == 0 && (uintptr_t)mask % 8 == 0,
                    "narrow_dgrad_bn_reduce_masked needs the coefficient tail, the piece layout's weights, c0 %% 64 == 0 and an 8-byte aligned mask");
         a.mask_in = static_cast<const unsigned long long *>(mask);
-        if (!fast_dispatch<5, 7>(a, as_stream(stream)))
-            return set_error(VOTENET_E_INVALID_ARGUMENT, "narrow_dgrad_bn_reduce_masked: shape not served (as votenet_narrow_dgrad_bn_reduce)");
-        return check_launch("narrow_dgrad_bn_reduce_masked");
+        return launched(fast_dispatch<5, 7>(a, st), "narrow_dgrad_bn_reduce_masked", "shape not served (as votenet_narrow_dgrad_bn_reduce)");
     }
-    if (!(wh ? fast_dispatch<5, 4>(a, as_stream(stream)) : fast_dispatch<1, 4>(a, as_stream(stream))))
-        return set_error(VOTENET_E_INVALID_ARGUMENT, "narrow_dgrad_bn_reduce: shape not served (rows %% 128 == 0, c %% 32 == 0, c <= 512, c0 == 64 or c0 %% 128 == 0, 16-byte aligned buffers)");
-    return check_launch("narrow_dgrad_bn_reduce");
+    return launched(wh ? fast_dispatch<5, 4>(a, st) : fast_dispatch<1, 4>(a, st), "narrow_dgrad_bn_reduce",
+                    "shape not served (rows % 128 == 0, c % 32 == 0, c <= 512, c0 == 64 or c0 % 128 == 0, 16-byte aligned buffers)");
 }
 extern "C" int votenet_narrow_dgrad_bn_reduce(long rows, int c, int c0, int k0, const float *da, const float *zsrc, const float *coef,
                                               int relu, const float *wT, const float *u8, const float *w0, const float *b0,
@@ -2065,32 +2066,31 @@ extern "C" void votenet_debug_fast_workgroups(int cap22, int cap41) // tuning ho
 // Second layer of an SA chain whose first layer is ASSEMBLED in the operand loader (assemble.hip): z (rows x cout) =
 // relu(bn0(z0)) w + bias with z0[r,:] = P[prow(r),:] + dxyz(r) . wx rebuilt from geo and the per-point table P (points x c0,
 // bias included); bn0 from raw statistics (in_bn: votenet_assemble_stats) or in_scale / in_shift.  stats as votenet_mlp_linear.
+// wh: the piece layout (the _half entry, which requires it).
+static int assembled_linear_impl(const char *name, const char *not_served, long rows, int c0, int cout, const float *geo, const float *P,
+                                 const float *wx, const float *in_scale, const float *in_shift, const votenet_bn_raw *in_bn, int in_relu,
+                                 const float *w, const float *bias, float *z, double *stats, const float *wh, const int *nh_dev, void *stream)
+{
+    VN_REQUIRE(rows > 0 && c0 > 0 && cout > 0, "%s expects rows > 0, c0 > 0, cout > 0", name);
+    VN_REQUIRE(geo && P && wx && w && z, "%s: null buffer", name);
+    VN_REQUIRE(first_bn_given(in_bn, in_scale, in_shift), "%s: the first layer's BatchNorm is missing", name);
+    FastArgs a = {};
+    set_assembled(a, geo, P, wx);
+    set_in_affine(a, in_scale, in_shift, to_raw(in_bn), in_relu);
+    set_gemm(a, rows, c0, cout, w, bias, z);
+    a.stats = stats;
+    set_pieces(a, wh, nh_dev);
+    if (wh) a.xcd_chunk = g_fast_xcd_chunk; // piece layout only: its rows are in scene order, an XCD's L2 then holds the slices of P its tiles gather
+    hipStream_t st = as_stream(stream);
+    return launched(stats ? fast_dispatch<4, 0>(a, st) : fast_dispatch<4, 1>(a, st), name, not_served);
+}
 extern "C" int votenet_assembled_linear(long rows, int c0, int cout, const float *geo, const float *P, const float *wx,
                                         const float *in_scale, const float *in_shift, const votenet_bn_raw *in_bn, int in_relu,
                                         const float *w, const float *bias, float *z, double *stats, void *stream)
 {
-    VN_REQUIRE(rows > 0 && c0 > 0 && cout > 0, "assembled_linear expects rows > 0, c0 > 0, cout > 0");
-    VN_REQUIRE(geo && P && wx && w && z, "assembled_linear: null buffer");
-    VN_REQUIRE(in_bn != nullptr || (in_scale != nullptr && in_shift != nullptr), "assembled_linear: the first layer's BatchNorm is missing");
-    FastArgs a = {};
-    a.geo = geo;
-    a.ptab = P;
-    a.wx = wx;
-    a.in_scale = in_scale;
-    a.in_shift = in_shift;
-    a.in_raw = to_raw(in_bn);
-    a.in_relu = in_relu;
-    a.rows = rows;
-    a.cin = c0;
-    a.cout = cout;
-    a.w = w;
-    a.bias = bias;
-    a.z = z;
-    a.stats = stats;
-    hipStream_t st = as_stream(stream);
-    const bool ok = stats ? fast_dispatch<4, 0>(a, st) : fast_dispatch<4, 1>(a, st);
-    if (!ok) return set_error(VOTENET_E_INVALID_ARGUMENT, "assembled_linear: shape not served (rows %% 128 == 0, c0 %% 32 == 0, c0 <= 512, cout %% 64 == 0, 16-byte aligned buffers)");
-    return check_launch("assembled_linear");
+    return assembled_linear_impl("assembled_linear",
+                                 "shape not served (rows % 128 == 0, c0 % 32 == 0, c0 <= 512, cout % 64 == 0, 16-byte aligned buffers)", rows, c0,
+                                 cout, geo, P, wx, in_scale, in_shift, in_bn, in_relu, w, bias, z, stats, nullptr, nullptr, stream);
 }
 
 // votenet_assembled_linear on the piece layout (half.hip): rows = 16 x pieces, wh = the weight of every piece's row 0 in
@@ -2100,70 +2100,41 @@ extern "C" int votenet_assembled_linear_half(long rows, int c0, int cout, const 
                                              const float *w, const float *bias, float *z, double *stats, const float *wh, const int *nh_dev,
                                              void *stream)
 {
-    VN_REQUIRE(rows > 0 && c0 > 0 && cout > 0, "assembled_linear_half expects rows > 0, c0 > 0, cout > 0");
-    VN_REQUIRE(geo && P && wx && w && z && wh, "assembled_linear_half: null buffer");
-    VN_REQUIRE(in_bn != nullptr || (in_scale != nullptr && in_shift != nullptr), "assembled_linear_half: the first layer's BatchNorm is missing");
-    FastArgs a = {};
-    a.geo = geo;
-    a.ptab = P;
-    a.wx = wx;
-    a.in_scale = in_scale;
-    a.in_shift = in_shift;
-    a.in_raw = to_raw(in_bn);
-    a.in_relu = in_relu;
-    a.rows = rows;
-    a.cin = c0;
-    a.cout = cout;
-    a.w = w;
-    a.bias = bias;
-    a.z = z;
-    a.stats = stats;
-    a.wh = wh;
-    a.nh_dev = nh_dev;
-    a.xcd_chunk = g_fast_xcd_chunk; // the rows are in scene order: an XCD's L2 then holds the slices of P its tiles gather
-    hipStream_t st = as_stream(stream);
-    const bool ok = stats ? fast_dispatch<4, 0>(a, st) : fast_dispatch<4, 1>(a, st);
-    if (!ok) return set_error(VOTENET_E_INVALID_ARGUMENT, "assembled_linear_half: shape not served (as votenet_assembled_linear)");
-    return check_launch("assembled_linear_half");
+    VN_REQUIRE(wh != nullptr, "assembled_linear_half: null buffer");
+    return assembled_linear_impl("assembled_linear_half", "shape not served (as votenet_assembled_linear)", rows, c0, cout, geo, P, wx, in_scale,
+                                 in_shift, in_bn, in_relu, w, bias, z, stats, wh, nh_dev, stream);
 }
 
 // votenet_mlp_dgrad_bn_reduce for an ASSEMBLED layer below (assemble.hip): z_prev is not read but rebuilt from geo, the per-point
 // table P (points x cout, bias included; points * cout * 4 < 2^32) and wx (3 x cout).  da_prev is stored.
+// wh: the piece layout (the _half entry, which requires it).
+static int assembled_dgrad_bn_reduce_impl(const char *name, long rows, int c, int cout, const float *da, const float *zsrc, const float *coef,
+                                          int relu, const float *wT, float *da_prev, const float *geo, const float *P, const float *wx,
+                                          const float *scale_prev, const float *shift_prev, const float *mean_prev, const float *var_prev,
+                                          float eps, int relu_prev, double *sums, const votenet_coef_tail *tail, const float *wh,
+                                          const int *nh_dev, void *stream)
+{
+    FastArgs a = {};
+    if (const int rc = dgrad_bn_args(a, name, rows, c, cout, da, zsrc, coef, relu, wT, da_prev)) return rc;
+    VN_REQUIRE(da && geo && P && wx, "%s: null buffer", name);
+    VN_REQUIRE(below_given(scale_prev, shift_prev, mean_prev, var_prev, sums), "%s: null buffer of the layer below", name);
+    VN_REQUIRE(tail_complete(tail), "%s: incomplete coefficient tail", name);
+    VN_REQUIRE((uintptr_t)geo % 16 == 0, "%s: geo must be 16-byte aligned", name);
+    set_assembled(a, geo, P, wx);
+    set_below(a, scale_prev, shift_prev, mean_prev, var_prev, eps, relu_prev, sums, tail);
+    set_pieces(a, wh, nh_dev);
+    if (wh) a.xcd_chunk = g_fast_xcd_chunk; // piece layout only, as assembled_linear_impl
+    hipStream_t st = as_stream(stream);
+    return launched(!wh ? fast_dispatch<1, 6>(a, st) : fast_dispatch<5, 6>(a, st), name, "shape not served (as votenet_mlp_dgrad_bn_reduce)");
+}
 extern "C" int votenet_assembled_dgrad_bn_reduce(long rows, int c, int cout, const float *da, const float *zsrc, const float *coef, int relu,
                                                  const float *wT, float *da_prev, const float *geo, const float *P, const float *wx,
                                                  const float *scale_prev, const float *shift_prev, const float *mean_prev,
                                                  const float *var_prev, float eps, int relu_prev, double *sums,
                                                  const votenet_coef_tail *tail, void *stream)
 {
-    VN_REQUIRE(rows > 0 && c > 0 && cout > 0, "assembled_dgrad_bn_reduce expects rows > 0, c > 0, cout > 0");
-    VN_REQUIRE(da && zsrc && coef && wT && da_prev && geo && P && wx, "assembled_dgrad_bn_reduce: null buffer");
-    VN_REQUIRE(scale_prev && shift_prev && mean_prev && var_prev && sums, "assembled_dgrad_bn_reduce: null buffer of the layer below");
-    VN_REQUIRE(!tail || (tail->ticket && tail->gamma && tail->coef && tail->rows > 0), "assembled_dgrad_bn_reduce: incomplete coefficient tail");
-    VN_REQUIRE((uintptr_t)geo % 16 == 0, "assembled_dgrad_bn_reduce: geo must be 16-byte aligned");
-    FastArgs a = {};
-    a.da = da;
-    a.zsrc = zsrc;
-    a.coef = coef;
-    a.src_relu = relu;
-    a.rows = rows;
-    a.cin = c;
-    a.cout = cout;
-    a.w = wT;
-    a.z = da_prev;
-    a.geo = geo;
-    a.ptab = P;
-    a.wx = wx;
-    a.e_scale = scale_prev;
-    a.e_shift = shift_prev;
-    a.e_mean = mean_prev;
-    a.e_var = var_prev;
-    a.e_eps = eps;
-    a.e_relu = relu_prev;
-    a.stats = sums;
-    a.tail = to_tail(tail);
-    if (!fast_dispatch<1, 6>(a, as_stream(stream)))
-        return set_error(VOTENET_E_INVALID_ARGUMENT, "assembled_dgrad_bn_reduce: shape not served (as votenet_mlp_dgrad_bn_reduce)");
-    return check_launch("assembled_dgrad_bn_reduce");
+    return assembled_dgrad_bn_reduce_impl("assembled_dgrad_bn_reduce", rows, c, cout, da, zsrc, coef, relu, wT, da_prev, geo, P, wx, scale_prev,
+                                          shift_prev, mean_prev, var_prev, eps, relu_prev, sums, tail, nullptr, nullptr, stream);
 }
 
 // The same on the piece layout (half.hip): da / da_prev are TOTAL gradients per compact row; the affine part B + C z of the rebuilt
@@ -2174,36 +2145,7 @@ extern "C" int votenet_assembled_dgrad_bn_reduce_half(long rows, int c, int cout
                                                       const float *var_prev, float eps, int relu_prev, double *sums,
                                                       const votenet_coef_tail *tail, const float *wh, const int *nh_dev, void *stream)
 {
-    VN_REQUIRE(rows > 0 && c > 0 && cout > 0, "assembled_dgrad_bn_reduce_half expects rows > 0, c > 0, cout > 0");
-    VN_REQUIRE(da && zsrc && coef && wT && da_prev && geo && P && wx && wh, "assembled_dgrad_bn_reduce_half: null buffer");
-    VN_REQUIRE(scale_prev && shift_prev && mean_prev && var_prev && sums, "assembled_dgrad_bn_reduce_half: null buffer of the layer below");
-    VN_REQUIRE(!tail || (tail->ticket && tail->gamma && tail->coef && tail->rows > 0), "assembled_dgrad_bn_reduce_half: incomplete coefficient tail");
-    VN_REQUIRE((uintptr_t)geo % 16 == 0, "assembled_dgrad_bn_reduce_half: geo must be 16-byte aligned");
-    FastArgs a = {};
-    a.da = da;
-    a.zsrc = zsrc;
-    a.coef = coef;
-    a.src_relu = relu;
-    a.rows = rows;
-    a.cin = c;
-    a.cout = cout;
-    a.w = wT;
-    a.z = da_prev;
-    a.geo = geo;
-    a.ptab = P;
-    a.wx = wx;
-    a.e_scale = scale_prev;
-    a.e_shift = shift_prev;
-    a.e_mean = mean_prev;
-    a.e_var = var_prev;
-    a.e_eps = eps;
-    a.e_relu = relu_prev;
-    a.stats = sums;
-    a.tail = to_tail(tail);
-    a.wh = wh;
-    a.nh_dev = nh_dev;
-    a.xcd_chunk = g_fast_xcd_chunk;
-    if (!fast_dispatch<5, 6>(a, as_stream(stream)))
-        return set_error(VOTENET_E_INVALID_ARGUMENT, "assembled_dgrad_bn_reduce_half: shape not served (as votenet_mlp_dgrad_bn_reduce)");
-    return check_launch("assembled_dgrad_bn_reduce_half");
+    VN_REQUIRE(wh != nullptr, "assembled_dgrad_bn_reduce_half: null buffer");
+    return assembled_dgrad_bn_reduce_impl("assembled_dgrad_bn_reduce_half", rows, c, cout, da, zsrc, coef, relu, wT, da_prev, geo, P, wx,
+                                          scale_prev, shift_prev, mean_prev, var_prev, eps, relu_prev, sums, tail, wh, nh_dev, stream);
 }

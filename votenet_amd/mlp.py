@@ -733,15 +733,32 @@ def group_linear_backward_half(half, b, n, P, wx, da, coef, relu, dw_xyz):
 _masked_slots = None
 
 
-def dgrad_bn_half(z, coef, relu, wT, da, half):
-    """votenet_mlp_dgrad_bn_half: da_prev (rows, cout) = dz wT with dz rebuilt from (da, z, coef) on the piece layout (totals; the affine
-    part weighted by half.wh) -- a plain GEMM, nothing in its epilogue but the store."""
+def _flag(on):
+    return 1 if on else 0
+
+
+def _dgrad_args(z, coef, relu, wT, da):
+    """-> (rows, c, cout, da, z, coef, relu, wT, out): the leading arguments of every input-gradient entry that stores da_prev, and out."""
     rows, c = z.shape
     cout = wT.shape[1]
     out = torch.empty((rows, cout), dtype=torch.float32, device=z.device)
+    return (rows, c, cout, L.ptr(da), L.ptr(z), L.ptr(coef), _flag(relu), L.ptr(wT), L.ptr(out)), out
+
+
+def _first_bn_args(in_bn, in_relu):
+    """-> (in_scale, in_shift, in_bn, in_relu) of a rebuilt first layer: its finished scale / shift, or the raw sums they come from."""
+    if in_bn.done:
+        return L.ptr(in_bn.scale), L.ptr(in_bn.shift), None, _flag(in_relu)
+    return None, None, ctypes.byref(in_bn.raw()), _flag(in_relu)
+
+
+def dgrad_bn_half(z, coef, relu, wT, da, half):
+    """votenet_mlp_dgrad_bn_half: da_prev (rows, cout) = dz wT with dz rebuilt from (da, z, coef) on the piece layout (totals; the affine
+    part weighted by half.wh) -- a plain GEMM, nothing in its epilogue but the store."""
+    args, out = _dgrad_args(z, coef, relu, wT, da)
+    rows, c, cout = args[:3]
     with L.device_guard(z.device), _Timed("linear_dense", 2.0 * rows * c * cout, (rows, c, cout, "dgrad_bn half"), limit=half):
-        L.check(L.lib().votenet_mlp_dgrad_bn_half(rows, c, cout, L.ptr(da), L.ptr(z), L.ptr(coef), 1 if relu else 0, L.ptr(wT), L.ptr(out),
-                                                  L.ptr(half.wh), L.ptr(half.nh_limit), L.stream_ptr()))
+        L.check(L.lib().votenet_mlp_dgrad_bn_half(*args, L.ptr(half.wh), L.ptr(half.nh_limit), L.stream_ptr()))
     return out
 
 
@@ -823,61 +840,45 @@ def assembled_linear(geo, P, wx, w, bias, in_bn, in_relu=True, want_stats=True, 
     rows, c0, cout = geo.shape[0], P.shape[1], w.shape[1]
     z = torch.empty((rows, cout), dtype=torch.float32, device=P.device)
     stats = _zeros_f64(2 * cout, P.device) if want_stats else None
-    scale = shift = raw = None
-    if in_bn.done:
-        scale, shift = in_bn.scale, in_bn.shift
-    else:
-        raw = in_bn.raw()
-    if half is not None:
-        with L.device_guard(P.device), _Timed("linear_dense", 2.0 * rows * c0 * cout, (rows, c0, cout, "fwd+bn assembled half"), limit=half):
-            L.check(L.lib().votenet_assembled_linear_half(rows, c0, cout, L.ptr(geo), L.ptr(P), L.ptr(wx), L.ptr(scale), L.ptr(shift),
-                                                          ctypes.byref(raw) if raw is not None else None, 1 if in_relu else 0, L.ptr(w),
-                                                          L.ptr(bias), L.ptr(z), L.ptr(stats), L.ptr(half.wh), L.ptr(half.nh_limit), L.stream_ptr()))
-        return z, stats
-    with L.device_guard(P.device), _Timed("linear_dense", 2.0 * rows * c0 * cout, (rows, c0, cout, "fwd+bn assembled")):
-        L.check(L.lib().votenet_assembled_linear(rows, c0, cout, L.ptr(geo), L.ptr(P), L.ptr(wx), L.ptr(scale), L.ptr(shift),
-                                                 ctypes.byref(raw) if raw is not None else None, 1 if in_relu else 0, L.ptr(w),
-                                                 L.ptr(bias), L.ptr(z), L.ptr(stats), L.stream_ptr()))
+    args = (rows, c0, cout, L.ptr(geo), L.ptr(P), L.ptr(wx), *_first_bn_args(in_bn, in_relu), L.ptr(w), L.ptr(bias), L.ptr(z), L.ptr(stats))
+    note = "fwd+bn assembled" + (" half" if half is not None else "")
+    with L.device_guard(P.device), _Timed("linear_dense", 2.0 * rows * c0 * cout, (rows, c0, cout, note), limit=half):
+        if half is not None:
+            L.check(L.lib().votenet_assembled_linear_half(*args, L.ptr(half.wh), L.ptr(half.nh_limit), L.stream_ptr()))
+        else:
+            L.check(L.lib().votenet_assembled_linear(*args, L.stream_ptr()))
     return z, stats
 
 
 def assembled_wgrad_bn(geo, P, wx, in_scale, in_shift, in_relu, z, coef, relu, da, dw, half=None):
     """dw (c0, cout) += relu(bn0(z0))^T dz1 with z0 rebuilt in the loader, dz1 = BatchNorm-backward(da, z, coef)."""
     rows, c0, cout = geo.shape[0], P.shape[1], z.shape[1]
-    if half is not None:
-        with L.device_guard(P.device), _Timed("wgrad_dense", 2.0 * rows * c0 * cout, (rows, c0, cout, "wgrad_bn assembled half"), limit=half):
-            L.check(L.lib().votenet_assembled_wgrad_bn_half(rows, c0, cout, L.ptr(geo), L.ptr(P), L.ptr(wx), L.ptr(in_scale), L.ptr(in_shift),
-                                                            1 if in_relu else 0, L.ptr(da), L.ptr(z), L.ptr(coef), 1 if relu else 0,
-                                                            L.ptr(half.wh), L.ptr(dw), L.ptr(half.nh_limit), L.stream_ptr()))
-        return
-    scr = _wgrad_scratch(None, rows, c0, cout, P.device)
-    with L.device_guard(P.device), _Timed("wgrad_dense", 2.0 * rows * c0 * cout, (rows, c0, cout, "wgrad_bn assembled")):
-        L.check(L.lib().votenet_assembled_wgrad_bn(rows, c0, cout, L.ptr(geo), L.ptr(P), L.ptr(wx), L.ptr(in_scale), L.ptr(in_shift),
-                                                   1 if in_relu else 0, L.ptr(da), L.ptr(z), L.ptr(coef), 1 if relu else 0, L.ptr(dw),
-                                                   L.ptr(scr), L.stream_ptr()))
+    args = (rows, c0, cout, L.ptr(geo), L.ptr(P), L.ptr(wx), L.ptr(in_scale), L.ptr(in_shift), _flag(in_relu), L.ptr(da), L.ptr(z), L.ptr(coef),
+            _flag(relu))
+    scr = _wgrad_scratch(None, rows, c0, cout, P.device) if half is None else None  # the piece layout's entry takes none
+    note = "wgrad_bn assembled" + (" half" if half is not None else "")
+    with L.device_guard(P.device), _Timed("wgrad_dense", 2.0 * rows * c0 * cout, (rows, c0, cout, note), limit=half):
+        if half is not None:
+            L.check(L.lib().votenet_assembled_wgrad_bn_half(*args, L.ptr(half.wh), L.ptr(dw), L.ptr(half.nh_limit), L.stream_ptr()))
+        else:
+            L.check(L.lib().votenet_assembled_wgrad_bn(*args, L.ptr(dw), L.ptr(scr), L.stream_ptr()))
 
 
 def assembled_dgrad_bn_reduce(z, coef, relu, wT, da, geo, P, wx, below, eps=BN_EPS, below_tail=None, half=None):
     """dgrad_bn(..., below=...) for an assembled layer below: -> (da_prev, sums) or, with below_tail, (da_prev, coef of that layer)."""
-    rows, c = z.shape
-    cout = wT.shape[1]
     bsc, bsh, bme, bva, brelu = below
-    out = torch.empty((rows, cout), dtype=torch.float32, device=z.device)
+    args, out = _dgrad_args(z, coef, relu, wT, da)
+    rows, c, cout = args[:3]
     sums = _zeros_f64(2 * cout, z.device)
     t, coef_b = _coef_tail(below_tail, cout, z.device)
-    if half is not None:
-        with L.device_guard(z.device), _Timed("linear_dense", 2.0 * rows * c * cout, (rows, c, cout, "dgrad_bn_reduce assembled half"), limit=half):
-            L.check(L.lib().votenet_assembled_dgrad_bn_reduce_half(rows, c, cout, L.ptr(da), L.ptr(z), L.ptr(coef), 1 if relu else 0, L.ptr(wT),
-                                                                   L.ptr(out), L.ptr(geo), L.ptr(P), L.ptr(wx), L.ptr(bsc), L.ptr(bsh),
-                                                                   L.ptr(bme), L.ptr(bva), eps, 1 if brelu else 0, L.ptr(sums),
-                                                                   ctypes.byref(t) if t is not None else None, L.ptr(half.wh), L.ptr(half.nh_limit),
-                                                                   L.stream_ptr()))
-    else:
-        with L.device_guard(z.device), _Timed("linear_dense", 2.0 * rows * c * cout, (rows, c, cout, "dgrad_bn_reduce assembled")):
-            L.check(L.lib().votenet_assembled_dgrad_bn_reduce(rows, c, cout, L.ptr(da), L.ptr(z), L.ptr(coef), 1 if relu else 0, L.ptr(wT),
-                                                              L.ptr(out), L.ptr(geo), L.ptr(P), L.ptr(wx), L.ptr(bsc), L.ptr(bsh), L.ptr(bme),
-                                                              L.ptr(bva), eps, 1 if brelu else 0, L.ptr(sums),
-                                                              ctypes.byref(t) if t is not None else None, L.stream_ptr()))
+    args += (L.ptr(geo), L.ptr(P), L.ptr(wx), L.ptr(bsc), L.ptr(bsh), L.ptr(bme), L.ptr(bva), eps, _flag(brelu), L.ptr(sums),
+             ctypes.byref(t) if t is not None else None)
+    note = "dgrad_bn_reduce assembled" + (" half" if half is not None else "")
+    with L.device_guard(z.device), _Timed("linear_dense", 2.0 * rows * c * cout, (rows, c, cout, note), limit=half):
+        if half is not None:
+            L.check(L.lib().votenet_assembled_dgrad_bn_reduce_half(*args, L.ptr(half.wh), L.ptr(half.nh_limit), L.stream_ptr()))
+        else:
+            L.check(L.lib().votenet_assembled_dgrad_bn_reduce(*args, L.stream_ptr()))
     if below_tail is None:
         return out, sums
     return out, (coef_b if coef_b is not None else _coef_after(below_tail, (bsc, bsh, bme, bva), sums, eps))
@@ -951,32 +952,22 @@ def narrow_linear(u8, w0, b0, w, bias, in_bn, in_relu=True, want_stats=True, hal
     cout = w.shape[1]
     z = torch.empty((rows, cout), dtype=torch.float32, device=u8.device)
     stats = _zeros_f64(2 * cout, u8.device) if want_stats else None
-    scale = shift = raw = None
-    if in_bn.done:
-        scale, shift = in_bn.scale, in_bn.shift
-    else:
-        raw = in_bn.raw()
+    args = (rows, k0, c0, cout, L.ptr(u8), L.ptr(w0), L.ptr(b0), *_first_bn_args(in_bn, in_relu), L.ptr(w), L.ptr(bias), L.ptr(z), L.ptr(stats))
+    wh = L.ptr(half.wh) if half is not None else None
+    mask = None
     if want_mask:
         if not narrow_mask_supported(rows, c0):
             raise L.InvalidArgumentError("narrow_linear: the mask needs rows %% 128 == 0 and c0 %% 64 == 0")
         mask = torch.empty((rows, c0 // 16), dtype=torch.int16, device=u8.device)
-        with L.device_guard(u8.device), _Timed("linear_dense", 2.0 * rows * c0 * cout, (rows, c0, cout, "fwd+bn narrow" + (" half" if half else ""))):
-            L.check(L.lib().votenet_narrow_linear_masked(rows, k0, c0, cout, L.ptr(u8), L.ptr(w0), L.ptr(b0), L.ptr(scale), L.ptr(shift),
-                                                         ctypes.byref(raw) if raw is not None else None, 1 if in_relu else 0, L.ptr(w),
-                                                         L.ptr(bias), L.ptr(z), L.ptr(stats), L.ptr(half.wh) if half is not None else None,
-                                                         L.ptr(mask), L.stream_ptr()))
-        return z, stats, mask
-    if half is not None:
-        with L.device_guard(u8.device), _Timed("linear_dense", 2.0 * rows * c0 * cout, (rows, c0, cout, "fwd+bn narrow half")):
-            L.check(L.lib().votenet_narrow_linear_half(rows, k0, c0, cout, L.ptr(u8), L.ptr(w0), L.ptr(b0), L.ptr(scale), L.ptr(shift),
-                                                       ctypes.byref(raw) if raw is not None else None, 1 if in_relu else 0, L.ptr(w),
-                                                       L.ptr(bias), L.ptr(z), L.ptr(stats), L.ptr(half.wh), L.stream_ptr()))
-        return z, stats
-    with L.device_guard(u8.device), _Timed("linear_dense", 2.0 * rows * c0 * cout, (rows, c0, cout, "fwd+bn narrow")):
-        L.check(L.lib().votenet_narrow_linear(rows, k0, c0, cout, L.ptr(u8), L.ptr(w0), L.ptr(b0), L.ptr(scale), L.ptr(shift),
-                                              ctypes.byref(raw) if raw is not None else None, 1 if in_relu else 0, L.ptr(w),
-                                              L.ptr(bias), L.ptr(z), L.ptr(stats), L.stream_ptr()))
-    return z, stats
+    note = "fwd+bn narrow" + (" half" if half is not None else "")
+    with L.device_guard(u8.device), _Timed("linear_dense", 2.0 * rows * c0 * cout, (rows, c0, cout, note)):
+        if want_mask:  # on either layout: wh may be NULL
+            L.check(L.lib().votenet_narrow_linear_masked(*args, wh, L.ptr(mask), L.stream_ptr()))
+        elif half is not None:
+            L.check(L.lib().votenet_narrow_linear_half(*args, wh, L.stream_ptr()))
+        else:
+            L.check(L.lib().votenet_narrow_linear(*args, L.stream_ptr()))
+    return (z, stats, mask) if want_mask else (z, stats)
 
 
 def narrow_wgrad_bn(u8, w0, b0, in_scale, in_shift, in_relu, z, coef, relu, da, dw, half=None):
@@ -984,17 +975,15 @@ def narrow_wgrad_bn(u8, w0, b0, in_scale, in_shift, in_relu, z, coef, relu, da, 
     rows = u8.shape[0]
     k0, c0 = w0.shape
     cout = z.shape[1]
-    if half is not None:
-        with L.device_guard(u8.device), _Timed("wgrad_dense", 2.0 * rows * c0 * cout, (rows, c0, cout, "wgrad_bn narrow half")):
-            L.check(L.lib().votenet_narrow_wgrad_bn_half(rows, k0, c0, cout, L.ptr(u8), L.ptr(w0), L.ptr(b0), L.ptr(in_scale), L.ptr(in_shift),
-                                                         1 if in_relu else 0, L.ptr(da), L.ptr(z), L.ptr(coef), 1 if relu else 0,
-                                                         L.ptr(half.wh), L.ptr(dw), L.stream_ptr()))
-        return
-    scr = _wgrad_scratch(None, rows, c0, cout, u8.device)
-    with L.device_guard(u8.device), _Timed("wgrad_dense", 2.0 * rows * c0 * cout, (rows, c0, cout, "wgrad_bn narrow")):
-        L.check(L.lib().votenet_narrow_wgrad_bn(rows, k0, c0, cout, L.ptr(u8), L.ptr(w0), L.ptr(b0), L.ptr(in_scale), L.ptr(in_shift),
-                                                1 if in_relu else 0, L.ptr(da), L.ptr(z), L.ptr(coef), 1 if relu else 0, L.ptr(dw),
-                                                L.ptr(scr), L.stream_ptr()))
+    args = (rows, k0, c0, cout, L.ptr(u8), L.ptr(w0), L.ptr(b0), L.ptr(in_scale), L.ptr(in_shift), _flag(in_relu), L.ptr(da), L.ptr(z),
+            L.ptr(coef), _flag(relu))
+    scr = _wgrad_scratch(None, rows, c0, cout, u8.device) if half is None else None  # the piece layout's entry takes none
+    note = "wgrad_bn narrow" + (" half" if half is not None else "")
+    with L.device_guard(u8.device), _Timed("wgrad_dense", 2.0 * rows * c0 * cout, (rows, c0, cout, note)):
+        if half is not None:
+            L.check(L.lib().votenet_narrow_wgrad_bn_half(*args, L.ptr(half.wh), L.ptr(dw), L.stream_ptr()))
+        else:
+            L.check(L.lib().votenet_narrow_wgrad_bn(*args, L.ptr(dw), L.ptr(scr), L.stream_ptr()))
 
 
 def narrow_dgrad_bn_reduce(z, coef, relu, wT, da, u8, w0, b0, below, eps=BN_EPS, tail=None, half=None, mask=None):
@@ -1008,17 +997,12 @@ def narrow_dgrad_bn_reduce(z, coef, relu, wT, da, u8, w0, b0, below, eps=BN_EPS,
     out = _zeros_f64(10 * c0, z.device)
     sums, ug = out[:2 * c0], out[2 * c0:]
     t, coef0 = _coef_tail(tail, c0, z.device)
-    if mask is not None and t is not None and half is not None:
-        with L.device_guard(z.device), _Timed("linear_dense", 2.0 * rows * c * c0, (rows, c, c0, "dgrad_bn_reduce narrow half")):
-            L.check(L.lib().votenet_narrow_dgrad_bn_reduce_masked(rows, c, c0, k0, L.ptr(da), L.ptr(z), L.ptr(coef), 1 if relu else 0, L.ptr(wT),
-                                                                  L.ptr(u8), L.ptr(w0), L.ptr(b0), L.ptr(bsc), L.ptr(bsh), L.ptr(bme), L.ptr(bva),
-                                                                  eps, 1 if brelu else 0, L.ptr(sums), L.ptr(ug), ctypes.byref(t), L.ptr(half.wh),
-                                                                  L.ptr(mask), L.stream_ptr()))
-        return coef0, ug.view(8, c0)
+    args = (rows, c, c0, k0, L.ptr(da), L.ptr(z), L.ptr(coef), _flag(relu), L.ptr(wT), L.ptr(u8), L.ptr(w0), L.ptr(b0), L.ptr(bsc),
+            L.ptr(bsh), L.ptr(bme), L.ptr(bva), eps, _flag(brelu), L.ptr(sums), L.ptr(ug), ctypes.byref(t) if t is not None else None)
     with L.device_guard(z.device), _Timed("linear_dense", 2.0 * rows * c * c0, (rows, c, c0, "dgrad_bn_reduce narrow" + (" half" if half else ""))):
-        args = (rows, c, c0, k0, L.ptr(da), L.ptr(z), L.ptr(coef), 1 if relu else 0, L.ptr(wT), L.ptr(u8), L.ptr(w0), L.ptr(b0), L.ptr(bsc),
-                L.ptr(bsh), L.ptr(bme), L.ptr(bva), eps, 1 if brelu else 0, L.ptr(sums), L.ptr(ug), ctypes.byref(t) if t is not None else None)
-        if half is not None:
+        if mask is not None and t is not None and half is not None:  # (then tail is given and its coefficients come from the kernel)
+            L.check(L.lib().votenet_narrow_dgrad_bn_reduce_masked(*args, L.ptr(half.wh), L.ptr(mask), L.stream_ptr()))
+        elif half is not None:
             L.check(L.lib().votenet_narrow_dgrad_bn_reduce_half(*args, L.ptr(half.wh), L.stream_ptr()))
         else:
             L.check(L.lib().votenet_narrow_dgrad_bn_reduce(*args, L.stream_ptr()))
@@ -1453,18 +1437,15 @@ def dgrad_bn(z, coef, relu, wT, da=None, gout=None, argmax=None, k=0, below=None
     """da_prev = dz @ wT with dz = BatchNorm-backward(da | pooled gout, z, coef) formed in the loader.
     below = (z_prev, scale, shift, mean, var, relu) of the layer whose activation da_prev is the gradient of: the store
     epilogue then also reduces that layer's BatchNorm backward -> returns (da_prev, sums) (dense da only)."""
-    rows, c = z.shape
-    cout = wT.shape[1]
-    out = torch.empty((rows, cout), dtype=torch.float32, device=z.device)
+    args, out = _dgrad_args(z, coef, relu, wT, da)
+    rows, c, cout = args[:3]
     if below is not None:
         zp, bsc, bsh, bme, bva, brelu = below
         sums = _zeros_f64(2 * cout, z.device)
         t, coef_b = _coef_tail(below_tail, cout, z.device)
         with L.device_guard(z.device), _SplitK(rows, c, cout, z.device), _Timed("linear_dense", 2.0 * rows * c * cout, (rows, c, cout, "dgrad_bn_reduce")):
-            L.check(L.lib().votenet_mlp_dgrad_bn_reduce(rows, c, cout, L.ptr(da), L.ptr(z), L.ptr(coef), 1 if relu else 0, L.ptr(wT),
-                                                        L.ptr(out), L.ptr(zp), L.ptr(bsc), L.ptr(bsh), L.ptr(bme), L.ptr(bva), eps,
-                                                        1 if brelu else 0, L.ptr(sums), ctypes.byref(t) if t is not None else None,
-                                                        L.stream_ptr()))
+            L.check(L.lib().votenet_mlp_dgrad_bn_reduce(*args, L.ptr(zp), L.ptr(bsc), L.ptr(bsh), L.ptr(bme), L.ptr(bva), eps, _flag(brelu),
+                                                        L.ptr(sums), ctypes.byref(t) if t is not None else None, L.stream_ptr()))
         if below_tail is None:
             return out, sums
         return out, (coef_b if coef_b is not None else _coef_after(below_tail, (bsc, bsh, bme, bva), sums, eps))  # (da_prev, coef of the layer below)
